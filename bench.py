@@ -92,6 +92,9 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--deterministic", action="store_true")
     ap.add_argument("--event-stride", type=int, default=0, help="hipEvent pairs around every n-th iteration's launches (0: steps // 16)")
+    ap.add_argument("--dump-outputs", default=None, dest="dump_outputs", metavar="DIR",
+                    help="write what the K timed steps of each precision computed as DIR/<f32|f64>_<name>.npy (see dump_outputs); the "
+                         "clock-warm iterations are undone before the warm-up steps, so that equal arguments give equal inputs")
     args = ap.parse_args()
 
     import torch
@@ -131,12 +134,17 @@ def main():
     stride = args.event_stride or max(1, args.steps // 16)
 
     pre_iterations = {}
+    dumps = {}
 
     def run(precision):
         """warm-up, the timed K steps (barrier + device sync on both sides), hipEvent profile, lower bound"""
         solver = bdd_hip_parallel_mma(col, costs, precision=precision, device=local_rank,
                                       pack_width=args.pack_width, deterministic=args.deterministic,
                                       vars_per_bin=args.vars_per_bin, stage_cap=args.stage_cap, waves_per_block=args.wpb)
+        if args.dump_outputs:   # the layer order is the layout's, fixed at construction
+            initial, order = device_state(solver, local_rank), solver.bdd_major_order()
+        else:
+            initial = None
         # Clock ramp: an idle MI355X sits at its lowest shader clock (rocm-smi: sclk 98 MHz) and needs tens of milliseconds of load to
         # come up; W = 5 warm-up steps are 0.6 ms and a K = 20 run 2.5 ms, and such runs measured 6.5 k instead of 7.9 k it/s from time
         # to time.  So the device is kept busy with the same iterations for args.clock_warm seconds first (untimed, counted in
@@ -156,10 +164,18 @@ def main():
                 pre += 64
             pre_iterations["n"] = pre
             pre_iterations["s"] = time.perf_counter() - t_pre
+        if initial is not None:   # the clock-warm loop ran for a time, not a count: back to the seeded instance's state
+            lo, hi, mm, delta = initial
+            solver.set_solver_costs(lo, hi, mm)
+            solver.set_delta(delta)
+            del initial, lo, hi, mm, delta
         solver.iterations(args.warmup)
         solver.synchronize()
         dt = timed_region(lambda: solver.iterations(args.steps),
                           lambda: (solver.synchronize(), torch.cuda.synchronize()), dist)
+        if args.dump_outputs and rank == 0:   # copied on the device now, written to files after the timed regions
+            dumps[precision] = (solver.lower_bound(), solver.lower_bound_per_bdd(out=_device_buffer(solver, solver.nr_bdds(), local_rank)),
+                                device_state(solver, local_rank), order)
         # `value` is that region.  K = 20 steps are a 2.3 ms sample: the same region again, a few times, shows its spread (repeat_samples)
         repeats = [timed_region(lambda: solver.iterations(args.steps), lambda: (solver.synchronize(), torch.cuda.synchronize()), dist)
                    for _ in range(max(0, args.repeats))]
@@ -184,6 +200,11 @@ def main():
         second = (dt2, prof2, lb2, s2.device_bytes())
         s2.close()
     solver, dt, prof, lb = run(args.precision)
+    if dumps:
+        dump_outputs(args.dump_outputs, dumps)
+        dumps.clear()
+    # the solver state the bounds below belong to: --dump-outputs undoes the clock-warm iterations
+    iterations_after = (0 if args.dump_outputs else pre_iterations.get("n", 0)) + args.warmup + (2 + max(0, args.repeats)) * args.steps
 
     triad_gbs = copy_gbs = lb_rate = lb_rate_host_loop = None
     if rank == 0:
@@ -248,7 +269,7 @@ def main():
             "roofline": roofline(prof, sizes, R, its / world, args, sfx, triad_gbs, copy_gbs, resident),
             "value_with_lower_bound_every_iteration": lb_rate,
             "value_with_lower_bound_every_iteration_host_loop": lb_rate_host_loop,
-            "lower_bound_after": {"iterations": pre_iterations.get("n", 0) + args.warmup + (2 + max(0, args.repeats)) * args.steps, "value": lb},
+            "lower_bound_after": {"iterations": iterations_after, "value": lb},
             # what ran, untimed, before the K timed steps: the clock-warm loop (seconds / iterations of the same step), then the W warm-up steps
             "clock_warm_iterations": pre_iterations.get("n", 0),
             "clock_warm_s": pre_iterations.get("s", 0.0),
@@ -263,7 +284,7 @@ def main():
             out["value_" + sfx2] = its2
             out["ms_per_step_" + sfx2] = dt2 / args.steps * 1e3
             out["roofline_" + sfx2] = roofline(prof2, sizes, R2, its2 / world, args, sfx2, triad_gbs, copy_gbs, second[3])
-            out["lower_bound_after_" + sfx2] = {"iterations": pre_iterations.get("n", 0) + args.warmup + (2 + max(0, args.repeats)) * args.steps, "value": lb2,
+            out["lower_bound_after_" + sfx2] = {"iterations": iterations_after, "value": lb2,
                                                "rel_diff_to_" + sfx: abs(lb2 - lb) / max(abs(lb), 1e-300)}
         if lbfgs is not None:
             out["lbfgs"] = {"what": "BASELINE.json configs[3]: L-BFGS around the same solver on the same instance (history 5, the reference's default "
@@ -456,6 +477,38 @@ def hbm_only_fractions():
         return {"f32": d.get("f32"), "f64": d.get("f64"), "source": "profiles/" + os.path.basename(path), "sources_hash": d.get("_source_hash"),
                 "matches_these_sources": d.get("_source_hash") == source_hash() if d.get("_source_hash") else None}
     return None
+
+
+DUMP_SAMPLE = 1 << 19   # elements kept of a longer array: five arrays of <= 2^19 elements per precision, <= 32 MB for both
+
+
+def _device_buffer(solver, n, device):
+    import torch
+    return torch.empty(n, dtype=torch.float64 if solver.value_type == np.float64 else torch.float32, device=f"cuda:{device}")
+
+
+def device_state(solver, device):
+    """the solver's dual state, copied on the device: costs (lo, hi), deferred min-marginals (layers, internal order), delta (2 V)"""
+    lo, hi, mm = (_device_buffer(solver, solver.nr_layers(), device) for _ in range(3))
+    solver.get_solver_costs(out=(lo, hi, mm))
+    delta = solver.get_delta(out=_device_buffer(solver, 2 * solver.nr_variables(), device))
+    return lo, hi, mm, delta
+
+
+def dump_outputs(out_dir, dumps):
+    """DIR/<f32|f64>_<name>.npy in the solver's precision: lower_bound (one value), lower_bound_per_bdd (BDD order), lo_cost, hi_cost,
+    deferred_mm (layers in BDD-major order, the reference CPU solver's) and delta (2 V).  An array longer than DUMP_SAMPLE is reduced to
+    the DUMP_SAMPLE elements at sorted indices drawn with numpy's default_rng(0): the same indices for every array of one length."""
+    os.makedirs(out_dir, exist_ok=True)
+    for precision, (lb, per_bdd, (lo, hi, mm, delta), order) in dumps.items():
+        sfx = "f32" if precision == "float" else "f64"
+        arrays = {"lower_bound": np.array([lb], np.float64), "lower_bound_per_bdd": per_bdd.cpu().numpy(),
+                  "lo_cost": lo.cpu().numpy()[order], "hi_cost": hi.cpu().numpy()[order], "deferred_mm": mm.cpu().numpy()[order],
+                  "delta": delta.cpu().numpy()}
+        for name, a in arrays.items():
+            if a.size > DUMP_SAMPLE:
+                a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+            np.save(os.path.join(out_dir, f"{sfx}_{name}.npy"), a)
 
 
 def timed_region(run_steps, device_sync, dist):

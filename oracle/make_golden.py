@@ -135,6 +135,64 @@ def record_exports():
     print("exports.json:", rc.nr_bdds(), "BDDs,", len(out["bdd_lp"]), "bytes of LP")
 
 
+def record_builders():
+    """tests/golden/builders_reference.npz: the reference's bdd_collection on the inputs of tests/test_bdd_builders.py and of
+    tests/test_split_qbdd.py::test_split_matches_reference_live (the same seeded draws those tests made against oracle/_ref), each
+    case's inputs next to the reference's result, so that the tests compare without the reference being built."""
+    out = {}
+
+    def put(key, rc):
+        col = rc.export()
+        out[key + "_instr"], out[key + "_delims"] = col.instr, col.delims
+
+    for n in (1, 2, 3, 4, 7, 10):
+        vs = np.arange(3, 3 + 2 * n, 2)
+        rc = RefCollection(); rc.add_simplex(vs); rc.add_covering(vs)
+        put(f"simplex_covering_{n}", rc)
+    rng = np.random.Generator(np.random.PCG64(3))
+    for i in range(40):
+        k = int(rng.integers(2, 9))
+        vs = np.sort(rng.choice(12, size=k, replace=False))
+        co = rng.integers(-4, 5, size=k)
+        co[co == 0] = 1
+        rhs = int(rng.integers(co[co < 0].sum(), co[co > 0].sum() + 1))
+        ineq = ["<=", "=", ">="][int(rng.integers(0, 3))]
+        rc = RefCollection()
+        r = rc.add_linear(co, ineq, rhs, vs)
+        out.update({f"linear_{i}_vars": vs, f"linear_{i}_coeffs": co, f"linear_{i}_rhs": rhs, f"linear_{i}_ineq": ineq, f"linear_{i}_result": r})
+        if r >= 0:
+            put(f"linear_{i}", rc)
+    out["linear_count"] = 40
+    for n, k in ((3, 2), (5, 2), (6, 3)):
+        rc = RefCollection(); rc.add_cardinality(list(range(n)), k)
+        put(f"cardinality_{n}_{k}", rc)
+    rng = np.random.Generator(np.random.PCG64(5))
+    cases = 0
+    for _ in range(12):
+        k = int(rng.integers(6, 14))
+        co = rng.integers(1, 5, size=k)
+        rhs = int(co.sum() // 2)
+        rc = RefCollection()
+        assert rc.add_linear(co, ["<=", ">=", "="][int(rng.integers(0, 3))], rhs, np.arange(k)) >= -2
+        if rc.nr_bdds() == 0:
+            continue
+        col = rc.export()
+        widths = col.layer_widths(0)
+        chunk = int(rng.integers(2, max(3, k - 1)))
+        # the reference asserts that cut layers have more than one node (bdd_collection.cpp:583)
+        if any(widths[c] == 1 for c in range(chunk, len(widths), chunk)):
+            continue
+        key = f"split_{cases}"
+        put(key + "_in", rc)
+        n, na = rc.split_qbdd(0, chunk, k + 3)
+        put(key + "_out", rc)
+        out.update({key + "_chunk": chunk, key + "_aux0": k + 3, key + "_n_new": n, key + "_next_aux": na})
+        cases += 1
+    out["split_count"] = cases
+    np.savez_compressed(os.path.join(OUT, "builders_reference.npz"), **out)
+    print("builders_reference.npz:", len(out), "arrays,", cases, "split cases")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     if "--fullsize" in sys.argv:
@@ -142,6 +200,9 @@ def main():
         return
     if "--exports" in sys.argv:
         record_exports()
+        return
+    if "--builders" in sys.argv:
+        record_builders()
         return
     record_split("split_covering_10", lambda x: x.add_covering(list(range(10))), 3, 10)
     record_split("split_simplex_9", lambda x: x.add_simplex(list(range(9))), 4, 20)

@@ -1,37 +1,36 @@
-"""Closed-form QBDD builders and the linear-row converter vs the reference's own bdd_collection — CPU only."""
+"""Closed-form QBDD builders and the linear-row converter vs the reference's own bdd_collection — CPU only.
+The reference's results are stored in tests/golden/builders_reference.npz (oracle/make_golden.py --builders), each next to its inputs."""
+import os
+
 import numpy as np
 import pytest
 
 from bdd_amd import BddCollection
 from oracle import oracle as O
-from util import same_function
+from util import GOLDEN_DIR, collection_from_arrays, same_function
 
 needs_ref = pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built (needs /root/reference)")
+REF = np.load(os.path.join(GOLDEN_DIR, "builders_reference.npz"))
 
 
-@needs_ref
+def ref_collection(key):
+    return collection_from_arrays(REF[key + "_instr"], REF[key + "_delims"])
+
+
 @pytest.mark.parametrize("n", [1, 2, 3, 4, 7, 10])
 def test_simplex_and_covering_node_for_node(n):
     vs = np.arange(3, 3 + 2 * n, 2)
     mine = BddCollection(); mine.add_simplex(vs); mine.add_covering(vs)
-    rc = O.RefCollection(); rc.add_simplex(vs); rc.add_covering(vs)
-    ref = rc.export()
+    ref = ref_collection(f"simplex_covering_{n}")
     np.testing.assert_array_equal(mine.delims, ref.delims)
     np.testing.assert_array_equal(mine.instr, ref.instr)
 
 
-@needs_ref
 def test_linear_rows_same_function_and_size():
-    rng = np.random.Generator(np.random.PCG64(3))
-    for _ in range(40):
-        k = int(rng.integers(2, 9))
-        vs = np.sort(rng.choice(12, size=k, replace=False))
-        co = rng.integers(-4, 5, size=k)
-        co[co == 0] = 1
-        rhs = int(rng.integers(co[co < 0].sum(), co[co > 0].sum() + 1))
-        ineq = ["<=", "=", ">="][int(rng.integers(0, 3))]
-        rc = O.RefCollection()
-        r = rc.add_linear(co, ineq, rhs, vs)
+    assert int(REF["linear_count"]) == 40
+    for i in range(40):
+        vs, co, rhs = REF[f"linear_{i}_vars"], REF[f"linear_{i}_coeffs"], int(REF[f"linear_{i}_rhs"])
+        ineq, r = str(REF[f"linear_{i}_ineq"]), int(REF[f"linear_{i}_result"])
         mine = BddCollection()
         try:
             mine.add_linear(co, ineq, rhs, vs)
@@ -39,18 +38,16 @@ def test_linear_rows_same_function_and_size():
             assert (r == -1 and "trivially" in str(e)) or (r == -2 and "infeasible" in str(e))
             continue
         assert r >= 0
-        ref = rc.export()
+        ref = ref_collection(f"linear_{i}")
         assert same_function(mine, 0, ref, 0, 12)
         assert mine.nr_bdd_nodes() == ref.nr_bdd_nodes()  # both are the canonical (minimal) QBDD
 
 
-@needs_ref
 def test_cardinality_matches_reference():
     for n, k in [(3, 2), (5, 2), (6, 3)]:
         vs = list(range(n))
-        rc = O.RefCollection(); rc.add_cardinality(vs, k)
         mine = BddCollection(); mine.add_cardinality(vs, k)
-        ref = rc.export()
+        ref = ref_collection(f"cardinality_{n}_{k}")
         assert same_function(mine, 0, ref, 0, n)
         assert mine.nr_bdd_nodes() == ref.nr_bdd_nodes()
 

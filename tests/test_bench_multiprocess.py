@@ -88,3 +88,39 @@ def test_lbfgs_bytes_and_hbm_only_source():
     newest = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_hbm_only_105m.json")))[-1]
     h = bench.hbm_only_fractions()
     assert h["source"] == "profiles/" + os.path.basename(newest) and 0.3 < h["f32"] < 1.0 and 0.3 < h["f64"] < 1.0
+
+
+def test_dump_outputs_names_dtypes_and_sample(tmp_path):
+    """bench.py --dump-outputs: one file per array and precision in the solver's precision, layer arrays in BDD-major order, arrays longer
+    than DUMP_SAMPLE cut to the same seeded sample in every run, and the 10.5 M-node workload within 64 MB.  CPU tensors stand in for the
+    device copies."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    from bdd_amd.instances import set_cover_sizes
+    sz = set_cover_sizes(1_000_000, 500_000, 10)
+    L, V, B = sz["L_nt"], sz["V"], sz["B"]
+    order = np.random.default_rng(1).permutation(L)
+    dumps = {}
+    for precision, dt in (("float", torch.float32), ("double", torch.float64)):
+        dumps[precision] = (-3.25, torch.arange(B, dtype=dt), tuple(torch.arange(n, dtype=dt) + i for i, n in enumerate((L, L, L, 2 * V))), order)
+    bench.dump_outputs(str(tmp_path / "a"), dumps)
+    bench.dump_outputs(str(tmp_path / "b"), dumps)
+    names = ["lower_bound", "lower_bound_per_bdd", "lo_cost", "hi_cost", "deferred_mm", "delta"]
+    want = sorted(f"{s}_{n}.npy" for s in ("f32", "f64") for n in names)
+    assert sorted(os.listdir(tmp_path / "a")) == want
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in want) <= 64 << 20
+    for s, dt in (("f32", np.float32), ("f64", np.float64)):
+        got = {n: np.load(tmp_path / "a" / f"{s}_{n}.npy") for n in names}
+        assert got["lower_bound"].dtype == np.float64 and got["lower_bound"].tolist() == [-3.25]
+        assert all(got[n].dtype == dt for n in names[1:])
+        np.testing.assert_array_equal(got["lower_bound_per_bdd"], np.arange(B))            # short enough: whole
+        assert got["lo_cost"].size == bench.DUMP_SAMPLE and got["delta"].size == bench.DUMP_SAMPLE
+        # one sample of the BDD-major layer positions for lo, hi and deferred mm; the values are those of the internal layers `order` maps there
+        pos = got["lo_cost"].astype(np.int64)
+        assert np.all(np.diff(order.argsort()[pos]) > 0)
+        np.testing.assert_array_equal(got["hi_cost"], pos + 1)
+        np.testing.assert_array_equal(got["deferred_mm"], pos + 2)
+        for n in names:
+            np.testing.assert_array_equal(got[n], np.load(tmp_path / "b" / f"{s}_{n}.npy"))

@@ -172,24 +172,26 @@ def test_batch_farm_command_line(tmp_path):
 
 
 def test_eight_slot_rehearsal_on_one_gpu(tmp_path):
-    """BASELINE.json configs[4] (8 instances, one per GPU) cannot be run here: both N = 8 paths are rehearsed with all eight slots on the
-    one GPU of this box — the line shapes, the per-rank work and the host-thread budget are what an 8-GPU node would see, the
-    numbers are not.  (1) bench.py under torch.distributed.run, 8 ranks, gloo barrier, max over ranks, ONE JSON line from rank 0;
-    (2) bdd_solver_cl --bench-set-cover with --devices 0,0,0,0,0,0,0,0: eight host threads, each builds and times its own instance."""
+    """BASELINE.json configs[4] (8 instances, one per GPU) cannot be run here: both N > 1 paths are rehearsed with all slots on the
+    one GPU of this box — the line shapes, the per-rank work and the host-thread budget are what a multi-GPU node would see, the
+    numbers are not.  (1) bench.py under torch.distributed.run, 4 ranks, gloo barrier, max over ranks, ONE JSON line from rank 0
+    (with this process, at most five processes have the GPU open at once);
+    (2) bdd_solver_cl --bench-set-cover with --devices 0,0,0,0,0,0,0,0: eight host threads in one process, each builds and times its own instance."""
     import os
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    ranks = 4
     env = dict(os.environ, BDDMMA_BENCH_SHARE_GPUS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-                          "--master-port", "29741", os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--vars", "100000",
+    out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
+                          "--master-port", "29741", os.path.join(root, "bench.py"), "--gpus", str(ranks), "--steps", "20", "--warmup", "5", "--vars", "100000",
                           "--rows", "50000", "--no-second-precision", "--clock-warm", "0.05"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
     d = json.loads(lines[0])
     one = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"}
-    assert one <= set(d) and d["n_gpus"] == 8 and d["steps"] == 20 and d["scaling"] == "weak" and d["value"] > 0
-    assert abs(d["value"] - 8 * 20 / (d["ms_per_step"] * 20e-3)) <= 1e-6 * d["value"]       # whole-job rate = all ranks' steps / max time
+    assert one <= set(d) and d["n_gpus"] == ranks and d["steps"] == 20 and d["scaling"] == "weak" and d["value"] > 0
+    assert abs(d["value"] - ranks * 20 / (d["ms_per_step"] * 20e-3)) <= 1e-6 * d["value"]       # whole-job rate = all ranks' steps / max time
     assert "cpu_baseline" not in d                                                          # the CPU leg is timed at N = 1 only
     exe = os.path.join(root, "bdd_amd", "csrc", "bdd_solver_cl")
     out = subprocess.run([exe, "--bench-set-cover", "100000", "50000", "10", "--iterations", "200", "--warmup", "20", "--seeds", "12345-12352",
@@ -326,3 +328,34 @@ def test_bounds_fixations_known_answers(front_end, tmp_path):
             else:
                 from bdd_amd import bdd_solver_py
                 bdd_solver_py.bdd_solver(bad, quiet=True).solve()
+
+
+def test_bench_dump_outputs_are_the_timed_steps(tmp_path):
+    """bench.py --dump-outputs: the state after exactly W warm-up + K timed steps from the seeded instance, whatever number of iterations
+    the clock-warm loop ran before them — the same as a fresh solver's after W + K iterations, in both precisions (the exchange's sums
+    may run in another order: tolerances, not equality)."""
+    import os
+    from bdd_amd.instances import random_set_cover_mt
+    from bdd_amd.solver import bdd_hip_parallel_mma
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3", "--vars", "3000", "--rows", "2000",
+                          "--no-cpu-baseline", "--no-lbfgs", "--no-configs", "--repeats", "1", "--clock-warm", "0.05", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 7 and d["clock_warm_iterations"] > 0
+    col, costs = random_set_cover_mt(3000, 2000, 10, seed=12345)
+    for precision, sfx, rel in (("float", "f32", 1e-4), ("double", "f64", 1e-9)):
+        s = bdd_hip_parallel_mma(col, costs, precision=precision)
+        s.iterations(3 + 7)
+        lb = s.lower_bound()
+        lo, hi, mm = s.get_solver_costs()
+        order = s.bdd_major_order()
+        want = {"lower_bound_per_bdd": s.lower_bound_per_bdd(), "lo_cost": lo[order], "hi_cost": hi[order], "deferred_mm": mm[order], "delta": s.get_delta()}
+        s.close()
+        got = np.load(tmp_path / f"{sfx}_lower_bound.npy")
+        assert got.shape == (1,) and abs(got[0] - lb) <= rel * abs(lb), (precision, got, lb)
+        for name, w in want.items():
+            g = np.load(tmp_path / f"{sfx}_{name}.npy")
+            assert g.dtype == w.dtype and g.shape == w.shape, name     # 20 000 layers, 6 000 delta entries: below the sample size, whole
+            np.testing.assert_allclose(g, w, rtol=rel, atol=rel * float(np.abs(w).max()), err_msg=f"{precision} {name}")

@@ -8,10 +8,7 @@ import pytest
 
 from bdd_amd import BddCollection
 from bdd_amd.ilp import compute_split_length, split_long_bdds
-from oracle import oracle as O
 from util import GOLDEN_DIR, SPLIT_GOLDEN, canonical_nodes, collection_from_arrays
-
-needs_ref = pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built (needs /root/reference)")
 
 
 @pytest.mark.parametrize("name", SPLIT_GOLDEN)
@@ -60,31 +57,20 @@ def test_implication_bdd_semantics():
     assert 0 < accepted < 2 ** aux_n
 
 
-@needs_ref
 def test_split_matches_reference_live():
-    rng = np.random.Generator(np.random.PCG64(5))
-    for _ in range(12):
-        k = int(rng.integers(6, 14))
-        co = rng.integers(1, 5, size=k)
-        rhs = int(co.sum() // 2)
-        rc = O.RefCollection()
-        assert rc.add_linear(co, ["<=", ">=", "="][int(rng.integers(0, 3))], rhs, np.arange(k)) >= -2
-        if rc.nr_bdds() == 0:
-            continue
-        col = rc.export()
-        widths = col.layer_widths(0)
-        chunk = int(rng.integers(2, max(3, k - 1)))
-        # the reference asserts that cut layers have more than one node (bdd_collection.cpp:583)
-        if any(widths[c] == 1 for c in range(chunk, len(widths), chunk)):
-            continue
-        n, na = rc.split_qbdd(0, chunk, k + 3)
-        new_nrs, na2 = col.split_qbdd(0, chunk, k + 3)
+    """split_qbdd on random knapsack rows, against the reference's split of the same rows (tests/golden/builders_reference.npz,
+    oracle/make_golden.py --builders: the seeded draws this test made against oracle/_ref, with the cases the reference refuses left out)"""
+    z = np.load(f"{GOLDEN_DIR}/builders_reference.npz")
+    assert int(z["split_count"]) == 12
+    for i in range(int(z["split_count"])):
+        key = f"split_{i}"
+        col = collection_from_arrays(z[key + "_in_instr"], z[key + "_in_delims"])
+        new_nrs, na2 = col.split_qbdd(0, int(z[key + "_chunk"]), int(z[key + "_aux0"]))
         if len(new_nrs) > 1:
             col.remove([0])
-        ref = rc.export()
-        assert (n, na) == (len(new_nrs), na2)
-        np.testing.assert_array_equal(col.instr, ref.instr)
-        np.testing.assert_array_equal(col.delims, ref.delims)
+        assert (int(z[key + "_n_new"]), int(z[key + "_next_aux"])) == (len(new_nrs), na2)
+        np.testing.assert_array_equal(col.instr, z[key + "_out_instr"])
+        np.testing.assert_array_equal(col.delims, z[key + "_out_delims"])
 
 
 def feasible_projection(col, n_orig, n_all):
