@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.abspath(os.environ["BDDMMA_LIB"]) if os.environ.get("BDDMMA_LIB") else os.path.join(_HERE, "csrc", "libbdd_mma_hip.so")
 
 OK = 0
+ERR_INVALID_ARGUMENT, ERR_INVALID_BDD, ERR_DEVICE, ERR_STATE, ERR_UNSUPPORTED, ERR_IO = -1, -2, -3, -4, -5, -6   # include/bdd_mma.h
 F32, F64 = 0, 1
 K_FORWARD_MM, K_BACKWARD_MM, K_FINISH_DELTA, K_OTHER, K_COUNT = 0, 1, 2, 3, 4
 
@@ -84,6 +85,8 @@ SIGNATURES = {
     "bddmma_lower_bound_per_bdd": (_I, [_V, _V, _I]),
     "bddmma_iteration": (_I, [_V, _D]),
     "bddmma_iterations": (_I, [_V, _D, _U64]),
+    "bddmma_learned_iterations": (_I, [_V, _V, _I, _U64, _D, _D, _V, _V, _V, _U64, _D, _I, C.POINTER(_U64)]),
+    "bddmma_isotropic_dist_weights": (_I, [_V, _V, _I]),
     "bddmma_forward_mm": (_I, [_V, _D, _V, _I]),
     "bddmma_backward_mm": (_I, [_V, _D, _V, _I]),
     "bddmma_normalize_delta": (_I, [_V, _V, _I]),

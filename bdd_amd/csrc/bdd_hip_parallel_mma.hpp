@@ -6,6 +6,7 @@
 // LPMP::bdd_cuda_parallel_mma<REAL> / bdd_cuda_base<REAL>.  Needs no HIP headers: device vectors are
 // raw device pointers (`device_ptr<REAL>`) owned by the caller or by the handle.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <stdexcept>
@@ -176,6 +177,54 @@ class bdd_hip_parallel_mma {
     void backward_mm(const REAL omega, REAL* dev_delta_lo_hi) { check(bddmma_backward_mm(h_, omega, dev_delta_lo_hi, 1)); }
     void normalize_delta(REAL* dev_delta_lo_hi) const { check(bddmma_normalize_delta(h_, dev_delta_lo_hi, 1)); }
     void distribute_delta() { check(bddmma_distribute_delta(h_)); }
+
+    // learned iterations (bdd_cuda_learned_mma.h: iterations; include/bdd_mma.h: bddmma_learned_iterations): device pointers, as the
+    // reference's thrust::device_ptr arguments; dist_weights REAL[nr_layers], sol_avg REAL[nr_layers], the two lb averages REAL[nr_bdds]
+    // (may be null when compute_history_for_itr = 0).  Returns the number of iterations run.
+    int iterations(const REAL* dev_dist_weights, const int num_itr, const REAL omega, const double improvement_slope = 1e-6,
+                   REAL* dev_sol_avg = nullptr, REAL* dev_lb_first_diff_avg = nullptr, REAL* dev_lb_second_diff_avg = nullptr,
+                   const int compute_history_for_itr = 0, const REAL history_avg_beta = 0.9)
+    {
+        uint64_t done = 0;
+        check(bddmma_learned_iterations(h_, dev_dist_weights, 1, (uint64_t)std::max(num_itr, 0), omega, improvement_slope, dev_sol_avg,
+                                        dev_lb_first_diff_avg, dev_lb_second_diff_avg, (uint64_t)std::max(compute_history_for_itr, 0),
+                                        history_avg_beta, 1, &done));
+        return (int)done;
+    }
+    // host weights without a history (dist_weights.size() must be nr_layers())
+    int iterations(const std::vector<REAL>& dist_weights, const int num_itr, const REAL omega, const double improvement_slope = 1e-6)
+    {
+        if (dist_weights.size() != nr_layers()) throw std::runtime_error("bdd_mma: dist_weights must hold nr_layers() values");
+        uint64_t done = 0;
+        check(bddmma_learned_iterations(h_, dist_weights.data(), 0, (uint64_t)std::max(num_itr, 0), omega, improvement_slope, nullptr, nullptr,
+                                        nullptr, 0, 0.9, 0, &done));
+        return (int)done;
+    }
+    // host weights with a history (dist_weights.size() must be nr_layers(); the outputs are resized when a history is asked for)
+    int iterations(const std::vector<REAL>& dist_weights, const int num_itr, const REAL omega, const double improvement_slope,
+                   std::vector<REAL>& sol_avg, std::vector<REAL>& lb_first_diff_avg, std::vector<REAL>& lb_second_diff_avg,
+                   const int compute_history_for_itr = 0, const REAL history_avg_beta = 0.9)
+    {
+        if (dist_weights.size() != nr_layers()) throw std::runtime_error("bdd_mma: dist_weights must hold nr_layers() values");
+        if (compute_history_for_itr > 0) {
+            sol_avg.resize(nr_layers());
+            lb_first_diff_avg.resize(nr_bdds());
+            lb_second_diff_avg.resize(nr_bdds());
+        }
+        uint64_t done = 0;
+        check(bddmma_learned_iterations(h_, dist_weights.data(), 0, (uint64_t)std::max(num_itr, 0), omega, improvement_slope, sol_avg.data(),
+                                        lb_first_diff_avg.data(), lb_second_diff_avg.data(), (uint64_t)std::max(compute_history_for_itr, 0),
+                                        history_avg_beta, 0, &done));
+        return (int)done;
+    }
+    // 1 / nr_bdds(variable) per layer, public layer order (the weights with which iterations(...) above is iteration())
+    std::vector<REAL> isotropic_dist_weights()
+    {
+        std::vector<REAL> w(nr_layers());
+        check(bddmma_isotropic_dist_weights(h_, w.data(), 0));
+        return w;
+    }
+    void isotropic_dist_weights(REAL* dev_out) { check(bddmma_isotropic_dist_weights(h_, dev_out, 1)); }
 
     // ---- min-marginals [var][bdd] -> {mm0, mm1} (bdd_cuda_base.cu:751-786)
     std::vector<std::vector<std::array<double, 2>>> min_marginals()

@@ -215,6 +215,19 @@ int bddmma_iterations(bddmma_solver* s, double omega, uint64_t n)
 {
     return guarded(s, [&](SolverBase* b) { return b->iterations(omega, n); });
 }
+int bddmma_learned_iterations(bddmma_solver* s, const void* dist_weights, int weights_on_device, uint64_t num_itr, double omega,
+                              double improvement_slope, void* sol_avg, void* lb_first_diff_avg, void* lb_second_diff_avg,
+                              uint64_t compute_history_for_itr, double history_avg_beta, int outputs_on_device, uint64_t* itr_done)
+{
+    return guarded(s, [&](SolverBase* b) {
+        return b->learned_iterations(dist_weights, weights_on_device, num_itr, omega, improvement_slope, sol_avg, lb_first_diff_avg,
+                                     lb_second_diff_avg, compute_history_for_itr, history_avg_beta, outputs_on_device, itr_done);
+    });
+}
+int bddmma_isotropic_dist_weights(bddmma_solver* s, void* out, int on_device)
+{
+    return guarded(s, [&](SolverBase* b) { return out ? b->isotropic_dist_weights(out, on_device) : BDDMMA_ERR_INVALID_ARGUMENT; });
+}
 int bddmma_forward_mm(bddmma_solver* s, double omega, void* d, int on_device)
 {
     return guarded(s, [&](SolverBase* b) { return d ? b->forward_mm(omega, d, on_device) : BDDMMA_ERR_INVALID_ARGUMENT; });

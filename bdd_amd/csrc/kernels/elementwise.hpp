@@ -637,4 +637,36 @@ __global__ void k_diff(TO* __restrict__ out, const TA* __restrict__ a, const TA*
     if (i < n) out[i] = TO(a[i] - b[i]);
 }
 
+// ---- learned iterations (SolverT::learned_iterations; bdd_cuda_learned_mma.cu:9-262)
+// 1 / nr_bdds(var) per layer: the isotropic weights, with which the weighted exchange is the plain one (up to the rounding of a product
+// against a quotient)
+template <typename REAL>
+__global__ void k_isotropic_alpha(const int32_t* __restrict__ layer_var, const int32_t* __restrict__ nbdds, REAL* __restrict__ out, uint32_t n)
+{
+    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l < n) out[l] = REAL(1) / REAL(nbdds[layer_var[l]]);
+}
+// counts the weights that are not finite or are negative (cnt[0]); the caller zeroes cnt
+template <typename REAL>
+__global__ void k_count_bad_weights(const REAL* __restrict__ w, uint32_t* __restrict__ cnt, uint32_t n)
+{
+    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l < n && !(w[l] >= REAL(0) && w[l] < REAL(__builtin_huge_val()))) atomicAdd(cnt, 1u);   // NaN fails both tests
+}
+// the argmin path of bdds_solution as REAL 0 / 1 (last_sol of :196-198)
+template <typename REAL>
+__global__ void k_char_to_real(const char* __restrict__ in, REAL* __restrict__ out, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = REAL(in[i]);
+}
+// compute_exp_moving_avg (:171-180): avg = beta * avg + (1.0 - beta) * cur — the first product in REAL, the rest in double (1.0 is a double
+// literal there), rounded to REAL once
+template <typename REAL>
+__global__ void k_ema(REAL* __restrict__ avg, const REAL* __restrict__ cur, REAL beta, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) avg[i] = REAL((double)(beta * avg[i]) + (1.0 - (double)beta) * (double)cur[i]);
+}
+
 }  // namespace bddmma

@@ -116,6 +116,10 @@ __device__ __forceinline__ void lds_add(REAL* p, REAL v)
 //             normalised pairs to the bin's entries (what the next sweep adds, :191-197); the per-variable
 //             result is also stored in delta_var (the solver's delta_lo_hi_).
 //   EX_RAW  : compute_delta only — un-normalised sums into delta_var (explicit forward_mm / backward_mm API).
+// WEIGHTED (learned iterations, SolverT::learned_iterations): EX_ITER without the normalisation — the broadcast stores
+// alpha[e] * REAL(sum[v]) per entry (bdd_cuda_learned_mma.cu:37,42: dist_w * delta_lo_hi_sum), alpha streamed in entry order beside the
+// entries' local variable indices.  A template parameter, not a run-time switch (a run-time switch in these kernels cost what
+// the non-temporal loads had gained).
 // The accumulators are ACC-typed: LDS f32 atomics (ds_add_f32) run at half the rate of ds_add_f64 on
 // gfx950 (measured: 33 us vs 16 us for the same 5 M entries), so float solvers accumulate in double
 // and round once per variable.
@@ -169,13 +173,15 @@ __device__ __forceinline__ void hop_store(double2 v, rsrc_t rh, uint32_t voff, u
 }
 // Entry addressing: a lane's offset is tid * size with the chunk's first entry in the scalar offset, the descriptors end at the bin's last
 // entry (lanes past it drop out by themselves); one predicated LDS atomic per entry (slot 2 v + [mm > 0], value |mm|).
-template <typename REAL, typename ACC, int MODE, int EX_THREADS, int EX_UNROLL, int NPT>
+template <typename REAL, typename ACC, int MODE, int EX_THREADS, int EX_UNROLL, int NPT, bool WEIGHTED = false>
 __device__ __forceinline__ bool exchange_reduce_body(const REAL* __restrict__ mm_binned, const uint32_t* __restrict__ bin_ptr,
                                                      const uint16_t* __restrict__ bvar, const int32_t* __restrict__ nbdds,
                                                      REAL* __restrict__ delta_var, REAL* __restrict__ delta_lay,
                                                      uint32_t vars_per_bin, uint32_t n_vars,
-                                                     uint32_t stop_word = RUN_NOT_STOPPED, uint32_t run_iter = 0)  // false: run_solver has stopped
+                                                     uint32_t stop_word = RUN_NOT_STOPPED, uint32_t run_iter = 0,  // false: run_solver has stopped
+                                                     const REAL* __restrict__ alpha = nullptr)                     // WEIGHTED: per entry
 {
+    static_assert(!WEIGHTED || MODE == EX_ITER, "the weighted exchange is an EX_ITER form");
     using P2 = typename Pair<REAL>::type;
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
     ACC* tile = reinterpret_cast<ACC*>(dyn_lds);
@@ -188,6 +194,7 @@ __device__ __forceinline__ bool exchange_reduce_body(const REAL* __restrict__ mm
     mm_binned += e0_abs;
     bvar += e0_abs;
     if (delta_lay) delta_lay += 2 * (size_t)e0_abs;
+    if (WEIGHTED) alpha += e0_abs;
     const uint32_t e1 = e1_abs - e0_abs;  // entries of the bin
     BDDMMA_STAMP(0x100000u + blockIdx.x * (EX_THREADS / 64) + (tid >> 6), 0);
     const rsrc_t rmm = make_rsrc(mm_binned, e1), rev = make_rsrc(bvar, e1);
@@ -217,7 +224,7 @@ __device__ __forceinline__ bool exchange_reduce_body(const REAL* __restrict__ mm
     if (stop_word <= run_iter) return false;  // uniform for the grid; nothing has been written yet
     // number of BDDs of the variables this thread normalises (needed only after the accumulation)
     int nb[NPT];
-    if (MODE == EX_ITER) {
+    if (MODE == EX_ITER && !WEIGHTED) {
 #pragma unroll
         for (int k = 0; k < NPT; ++k) {
             const uint32_t i = tid + k * EX_THREADS;
@@ -259,7 +266,7 @@ __device__ __forceinline__ bool exchange_reduce_body(const REAL* __restrict__ mm
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
         const uint32_t i = tid + k * EX_THREADS;
-        if (i < 2 * nv) {
+        if (!WEIGHTED && i < 2 * nv) {  // WEIGHTED: the sums stay as they are, and delta_var is not written
             REAL x = REAL(tile[i]);
             if (MODE == EX_ITER) {
                 x = nb[k] > 0 ? x / REAL(nb[k]) : REAL(0);
@@ -274,13 +281,24 @@ __device__ __forceinline__ bool exchange_reduce_body(const REAL* __restrict__ mm
     __syncthreads();
     BDDMMA_STAMP(0x100000u + blockIdx.x * (EX_THREADS / 64) + (tid >> 6), 3);
     const rsrc_t rdl = make_rsrc(delta_lay, 2ull * e1);
-#pragma unroll
-    for (int u = 0; u < EX_UNROLL; ++u) {  // first chunk: the local variable indices are still in registers
+    const rsrc_t ral = make_rsrc(alpha, WEIGHTED ? e1 : 0u);
+    // {lo, hi} of entry `es` from its variable's slot pair: the normalised pair, or (WEIGHTED) alpha[e] * the sums rounded to REAL
+    auto pair_of = [&](uint32_t lvar, REAL a) {
         P2 pr;
-        pr.x = REAL(tile[2 * lv[u]]);
-        pr.y = REAL(tile[2 * lv[u] + 1]);
-        hop_store(pr, rdl, vo_p, (u * EX_THREADS) * (uint32_t)sizeof(P2));
+        pr.x = REAL(tile[2 * lvar]);
+        pr.y = REAL(tile[2 * lvar + 1]);
+        if (WEIGHTED) { pr.x = a * pr.x; pr.y = a * pr.y; }
+        return pr;
+    };
+    REAL al[EX_UNROLL];
+#pragma unroll
+    for (int u = 0; u < EX_UNROLL; ++u) {
+        al[u] = REAL(0);
+        if (WEIGHTED) hop_load(al[u], ral, vo_m, (u * EX_THREADS) * (uint32_t)sizeof(REAL));  // past the bin: no store either
     }
+#pragma unroll
+    for (int u = 0; u < EX_UNROLL; ++u)  // first chunk: the local variable indices are still in registers
+        hop_store(pair_of(lv[u], al[u]), rdl, vo_p, (u * EX_THREADS) * (uint32_t)sizeof(P2));
     BDDMMA_STAMP(0x100000u + blockIdx.x * (EX_THREADS / 64) + (tid >> 6), 4);
     if (one_chunk) return true;
     for (uint32_t base = CH; base < e1; base += CH) {  // uniform
@@ -289,11 +307,11 @@ __device__ __forceinline__ bool exchange_reduce_body(const REAL* __restrict__ mm
         for (int u = 0; u < EX_UNROLL; ++u) lv2[u] = __builtin_amdgcn_raw_buffer_load_b16(rev, vo_v, (base + u * EX_THREADS) * 2u, 0);
 #pragma unroll
         for (int u = 0; u < EX_UNROLL; ++u) {
-            P2 pr;
-            pr.x = REAL(tile[2 * lv2[u]]);
-            pr.y = REAL(tile[2 * lv2[u] + 1]);
-            hop_store(pr, rdl, vo_p, (base + u * EX_THREADS) * (uint32_t)sizeof(P2));
+            al[u] = REAL(0);
+            if (WEIGHTED) hop_load(al[u], ral, vo_m, (base + u * EX_THREADS) * (uint32_t)sizeof(REAL));
         }
+#pragma unroll
+        for (int u = 0; u < EX_UNROLL; ++u) hop_store(pair_of(lv2[u], al[u]), rdl, vo_p, (base + u * EX_THREADS) * (uint32_t)sizeof(P2));
     }
     return true;
 }
@@ -302,14 +320,17 @@ __device__ __forceinline__ bool exchange_reduce_body(const REAL* __restrict__ mm
 // (only on the launch that ends an iteration) makes workgroup 0 reduce the lower bound and run the tests after its bin is done —
 // behind the body, where no register of the exchange is live any more (the 1024-thread double instantiation sits at its 128-VGPR limit).
 // RUN = false is the kernel every other caller launches: `stop` and `run` are not looked at, the code is the body alone.
+// WEIGHTED: the learned iterations' form (alpha in entry order; RUN = false only).
 template <typename REAL, typename ACC, int MODE, int EX_THREADS = bddmma::EX_THREADS, int EX_UNROLL = bddmma::EX_UNROLL, int NPT = bddmma::EX_NPT,
-          bool RUN = false>
+          bool RUN = false, bool WEIGHTED = false>
 __global__ void __launch_bounds__(EX_THREADS) k_exchange_reduce(const REAL* __restrict__ mm_binned, const uint32_t* __restrict__ bin_ptr,
                                                                   const uint16_t* __restrict__ bvar, const uint32_t* stop, uint32_t run_iter,
                                                                   uint32_t vars_per_bin, uint32_t n_vars, uint32_t n_entries,
                                                                   const int32_t* __restrict__ nbdds, REAL* __restrict__ delta_var,
-                                                                  REAL* __restrict__ delta_lay, RunStep run = RunStep{})
+                                                                  REAL* __restrict__ delta_lay, RunStep run = RunStep{},
+                                                                  const REAL* __restrict__ alpha = nullptr)
 {
+    static_assert(!(RUN && WEIGHTED), "learned iterations do not run under the device-resident run_solver");
     // argument order: what the first loads need comes first (the first 16 dwords of plain arguments are preloaded into SGPRs, see
     // RES_LEADING_ARGS); the stop word's load is issued at once and tested inside the body when the first chunk's loads are in flight
     const uint32_t stop_word = (RUN && stop != nullptr) ? *stop : RUN_NOT_STOPPED;
@@ -322,8 +343,8 @@ __global__ void __launch_bounds__(EX_THREADS) k_exchange_reduce(const REAL* __re
         run_ctl_step(run);
         return;
     }
-    if (!exchange_reduce_body<REAL, ACC, MODE, EX_THREADS, EX_UNROLL, NPT>(mm_binned, bin_ptr, bvar, nbdds, delta_var, delta_lay, vars_per_bin, n_vars,
-                                                                            stop_word, RUN ? run_iter : 0u))
+    if (!exchange_reduce_body<REAL, ACC, MODE, EX_THREADS, EX_UNROLL, NPT, WEIGHTED>(mm_binned, bin_ptr, bvar, nbdds, delta_var, delta_lay, vars_per_bin,
+                                                                                      n_vars, stop_word, RUN ? run_iter : 0u, alpha))
         return;
 }
 
@@ -346,11 +367,13 @@ __global__ void __launch_bounds__(EX_THREADS) k_exchange_reduce(const REAL* __re
 constexpr int SEG_MAXL = 12;  // 16-byte loads of differences per thread: a bin holds <= SEG_MAXL * T * 16 / sizeof(REAL) entries
 // G: 16-byte groups of run positions per thread (the largest bin's; the tables pad every run to it) — a template parameter so that every
 // register array below is indexed by constants (with run-time group counts and early exits the arrays went to scratch memory)
-template <typename REAL, int T, int G, bool RUN = false>
+// WEIGHTED: no normalisation; the broadcast stores alpha[e] * the pair (see exchange_reduce_body).
+template <typename REAL, int T, int G, bool RUN = false, bool WEIGHTED = false>
 __global__ void __launch_bounds__(T) k_exchange_seg(const REAL* __restrict__ mm_binned, const uint4* __restrict__ seg_bin, const uint32_t* stop, uint32_t run_iter,
                                                       const uint4* __restrict__ seg_perm, const uint2* __restrict__ seg_thr, uint32_t tile_off, uint32_t cnt_off,
-                                                      REAL* __restrict__ delta_lay, RunStep run = RunStep{})
+                                                      REAL* __restrict__ delta_lay, RunStep run = RunStep{}, const REAL* __restrict__ alpha = nullptr)
 {
+    static_assert(!(RUN && WEIGHTED), "learned iterations do not run under the device-resident run_solver");
     const uint32_t stop_word = (RUN && stop != nullptr) ? *stop : RUN_NOT_STOPPED;
     if (RUN && run.ctl != nullptr && blockIdx.x == gridDim.x - 1) {  // the extra workgroup of the launch that ends a run_solver iteration (see k_exchange_reduce)
         if (stop_word <= run_iter) return;
@@ -369,6 +392,7 @@ __global__ void __launch_bounds__(T) k_exchange_seg(const REAL* __restrict__ mm_
     const uint32_t slots = hdr.y >> 8, E = hdr.w;
     mm_binned += hdr.z;
     delta_lay += 2 * (size_t)hdr.z;
+    if (WEIGHTED) alpha += hdr.z;
     BDDMMA_STAMP(0x100000u + blockIdx.x * (T / 64) + (tid >> 6), 0);
     const rsrc_t rmm = make_rsrc(mm_binned, E);
     using u4 = decltype(__builtin_amdgcn_raw_buffer_load_b128(rmm, 0, 0, 0));
@@ -433,7 +457,7 @@ __global__ void __launch_bounds__(T) k_exchange_seg(const REAL* __restrict__ mm_
     }
     __syncthreads();
     BDDMMA_STAMP(0x100000u + blockIdx.x * (T / 64) + (tid >> 6), 2);
-    for (uint32_t i = tid; i < slots; i += T) {  // normalize_delta, :410-430
+    for (uint32_t i = tid; i < slots && !WEIGHTED; i += T) {  // normalize_delta, :410-430
         P2 pr = tile[i];
         const REAL c = REAL(cnt[i]);
         pr.x /= c;
@@ -445,17 +469,25 @@ __global__ void __launch_bounds__(T) k_exchange_seg(const REAL* __restrict__ mm_
     __syncthreads();
     BDDMMA_STAMP(0x100000u + blockIdx.x * (T / 64) + (tid >> 6), 3);
     const rsrc_t rdl = make_rsrc(delta_lay, 2ull * E);
+    const rsrc_t ral = make_rsrc(alpha, WEIGHTED ? E : 0u);
     const uint32_t vo_p = tid * (uint32_t)sizeof(P2);
     for (uint32_t base = 0; base < E; base += 4 * T) {
         uint32_t sl[4];
         P2 pr[4];
+        REAL al[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const uint32_t e = base + u * T + tid;
             sl[u] = e < E ? slot_lds[e] : 0u;
+            al[u] = REAL(0);
+            if (WEIGHTED) bload(al[u], ral, e < E ? e * (uint32_t)sizeof(REAL) : OOB);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) pr[u] = tile[sl[u]];
+        if (WEIGHTED) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { pr[u].x = al[u] * pr[u].x; pr[u].y = al[u] * pr[u].y; }
+        }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
             if (base + u * T < E) hop_store(pr[u], rdl, vo_p, (base + u * T) * (uint32_t)sizeof(P2));  // lanes past the bin's end: out of the descriptor's range
@@ -469,10 +501,11 @@ __global__ void __launch_bounds__(T) k_exchange_seg(const REAL* __restrict__ mm_
 // neighbouring addresses, there are no LDS accumulators and no barriers, and the sum has the fixed order of the reduce_by_key variant
 // the reference keeps commented out (:395-407).  One dependent round trip (var_ptr) before the values instead of the binned kernel's
 // chain of loads, LDS atomics and three workgroup barriers: 3.5 us instead of 9.7 us at 1 M nodes.
-template <typename REAL>
+// WEIGHTED: the learned iterations' form — entry e of the variable gets alpha[e] * the un-normalised pair.
+template <typename REAL, bool WEIGHTED = false>
 __global__ void __launch_bounds__(256) k_exchange_byvar(const REAL* __restrict__ mm, const uint32_t* __restrict__ var_ptr,
                                                           REAL* __restrict__ delta_lay, uint32_t n_vars, uint32_t n_entries,
-                                                          RunGate gate = RunGate{}, RunStep run = RunStep{})
+                                                          RunGate gate = RunGate{}, RunStep run = RunStep{}, const REAL* __restrict__ alpha = nullptr)
 {
     if (run_stopped(gate)) return;
     if (run.ctl != nullptr && blockIdx.x == 0) run_ctl_step(run);
@@ -498,6 +531,18 @@ __global__ void __launch_bounds__(256) k_exchange_byvar(const REAL* __restrict__
         else if (x < 0) lo += -x;
     }
     if (n == 0) return;
+    if (WEIGHTED) {
+        const rsrc_t ral = make_rsrc(alpha, n_entries);
+        for (uint32_t j = 0; j < n; ++j) {
+            REAL a;
+            bload(a, ral, (k0 + j) * (uint32_t)sizeof(REAL));
+            P2 pw;
+            pw.x = a * lo;
+            pw.y = a * hi;
+            bstore(pw, rdl, (k0 + j) * (uint32_t)sizeof(P2));
+        }
+        return;
+    }
     P2 pr;
     pr.x = lo / REAL(n);
     pr.y = hi / REAL(n);
@@ -510,10 +555,11 @@ __global__ void __launch_bounds__(256) k_exchange_byvar(const REAL* __restrict__
 // arc costs, bdd_cuda_parallel_mma.cu:191-197).  Entries of one bin are contiguous, so the pairs of
 // vars_per_bin consecutive variables are re-read from L1/L2 while the writes stream out coalesced.
 // Four entries per thread: one 16-byte index load, four independent pair gathers, 16-byte stores.
-template <typename REAL>
+// WEIGHTED: delta_var holds the un-normalised sums (k_delta_gather<REAL, false>); entry e gets alpha[e] * its variable's pair.
+template <typename REAL, bool WEIGHTED = false>
 __global__ void __launch_bounds__(256) k_exchange_bcast(const REAL* __restrict__ delta_var, const uint32_t* __restrict__ evar,
                                                           REAL* __restrict__ delta_lay, uint32_t n_entries, uint32_t n_vars,
-                                                          RunGate gate = RunGate{}, RunStep run = RunStep{})
+                                                          RunGate gate = RunGate{}, RunStep run = RunStep{}, const REAL* __restrict__ alpha = nullptr)
 {
     if (run_stopped(gate)) return;
     // the deterministic exchange is two launches (k_delta_gather, this one): the tests latch `stop` in the LAST launch of the iteration
@@ -532,6 +578,16 @@ __global__ void __launch_bounds__(256) k_exchange_bcast(const REAL* __restrict__
     P2 pr[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) bload(pr[u], rdv, v[u] != 0xFFFFFFFFu ? v[u] * (uint32_t)sizeof(P2) : OOB);
+    if (WEIGHTED) {
+        const rsrc_t ral = make_rsrc(alpha, n_entries);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            REAL a;
+            bload(a, ral, e + u < n_entries ? (e + u) * (uint32_t)sizeof(REAL) : OOB);
+            pr[u].x = a * pr[u].x;
+            pr[u].y = a * pr[u].y;
+        }
+    }
     P2* out = reinterpret_cast<P2*>(delta_lay) + e;
     if (e + 4 <= n_entries) {
 #pragma unroll

@@ -29,7 +29,11 @@ struct bddmma_lbfgs {
     bddmma_solver* s = nullptr;
     bddmma_lbfgs_params p{};
     std::string err;
-    virtual ~bddmma_lbfgs() {}
+    std::shared_ptr<int> attached;  // SolverBase::lbfgs_attached of the wrapped solver while this wrapper lives (learned iterations refuse then)
+    virtual ~bddmma_lbfgs()
+    {
+        if (attached) --*attached;
+    }
     virtual int iteration() = 0;
     virtual void flush() = 0;
     virtual void get_state(bddmma_lbfgs_state* out) const = 0;
@@ -1103,6 +1107,8 @@ int bddmma_lbfgs_create(bddmma_lbfgs** out, bddmma_solver* s, const bddmma_lbfgs
         delete l;
         return rc;
     }
+    l->attached = s->impl->lbfgs_attached;
+    ++*l->attached;
     *out = l;
     return BDDMMA_OK;
 }

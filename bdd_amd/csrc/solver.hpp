@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <limits>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -61,6 +63,16 @@ struct SolverBase {
             if (int rc = iteration(omega)) return rc;
         return BDDMMA_OK;
     }
+    // bdd_cuda_learned_mma::iterations (bdd_cuda_learned_mma.cu:184-270): iterations with per-layer distribution weights, the state
+    // contract of include/bdd_mma.h (bddmma_learned_iterations)
+    virtual int learned_iterations(const void* dist_weights, int weights_on_device, uint64_t num_itr, double omega, double improvement_slope,
+                                   void* sol_avg, void* lb_first_diff_avg, void* lb_second_diff_avg, uint64_t compute_history_for_itr,
+                                   double history_avg_beta, int outputs_on_device, uint64_t* itr_done) = 0;
+    virtual int isotropic_dist_weights(void* out, int on_device) = 0;
+    double initial_lb_change = std::numeric_limits<double>::infinity();  // set_initial_lb_change (bdd_cuda_learned_mma.h:111-116): set once
+    // number of L-BFGS wrappers attached to this solver (bddmma_lbfgs_create / _destroy); shared so that a wrapper destroyed after its
+    // solver does not touch freed memory
+    std::shared_ptr<int> lbfgs_attached = std::make_shared<int>(0);
     bool fused_small = false;   // whole iterations in one launch (diagnostics: bddmma_fused_small)
     bool nt_loads = false;      // the solve sweeps' non-temporal instantiation (diagnostics: bddmma_nontemporal_loads)
     // run_solver (include/run_solver_util.h:10-77) around iteration(): termination tests on the device, see solver_impl.hpp

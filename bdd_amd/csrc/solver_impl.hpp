@@ -70,6 +70,11 @@ struct SolverT final : SolverBase {
     REAL* d_delta_lay = nullptr;    // 2L: the same, broadcast to binned entry order (what the sweeps read)
     REAL* d_mm_binned = nullptr;    // L : deferred min-marginal differences in binned entry order
     REAL *d_delta_c = nullptr, *d_delta_lay_c = nullptr;  // scratch for the explicit forward_mm/backward_mm API
+    // learned iterations (learned_iterations): the distribution weights in binned entry order, and the history's scratch — allocated on the
+    // first call that needs them (dalloc: carved from the arena's rest or a further chunk; not part of the arena's size estimate in init)
+    REAL* d_alpha_ent = nullptr;
+    REAL* d_hist = nullptr;        // last_sol [L], three per-BDD bounds [3 B], the change [B] and the previous change [B]
+    REAL* d_hist_out = nullptr;    // device copies of the caller's host outputs: sol_avg [L], lb_first_diff_avg [B], lb_second_diff_avg [B]
     uint16_t* d_bvar = nullptr;
     uint32_t *d_evar = nullptr, *d_lpos = nullptr, *d_vpos = nullptr, *d_bin_ptr = nullptr;
     uint32_t *d_pack_group_ptr = nullptr, *d_grp_layer_off = nullptr, *d_grp_hop_end = nullptr;
@@ -440,6 +445,7 @@ struct SolverT final : SolverBase {
         SET_DYN((k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_ITER>), exch_lds);
         SET_DYN((k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_RAW>), exch_lds);
         SET_DYN((k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_ITER, EX_THREADS, EX_UNROLL, EX_NPT, true>), exch_lds);  // run_plain()'s instantiation
+        SET_DYN((k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_ITER, EX_THREADS, EX_UNROLL, EX_NPT, false, true>), exch_lds);  // learned_iterations()'s
         opts_variant = opts ? opts->variant_flags : 0u;
         mixed_fwd = (opts_variant & 2u) == 0;
         // measured in double: 7.1 M nodes (490 MB resident) lose 12 % with non-temporal potentials, 10.5 M (720 MB) gain 4 %
@@ -468,7 +474,8 @@ struct SolverT final : SolverBase {
                     seg_groups = SE.max_groups;
 #define SET_SEG_G(T_, G_)                                             \
     SET_DYN((k_exchange_seg<REAL, T_, G_, false>), seg_lds);          \
-    SET_DYN((k_exchange_seg<REAL, T_, G_, true>), seg_lds)
+    SET_DYN((k_exchange_seg<REAL, T_, G_, true>), seg_lds);           \
+    SET_DYN((k_exchange_seg<REAL, T_, G_, false, true>), seg_lds)   /* learned_iterations()'s */
 #define SET_SEG(T_) if (seg_groups <= 2) { SET_SEG_G(T_, 2); } else { SET_SEG_G(T_, 4); }
                     if (exch_small) { SET_SEG(EXS_THREADS) } else if (exch_medium) { SET_SEG(EXM_THREADS) } else { SET_SEG(EX_THREADS) }
 #undef SET_SEG
@@ -1130,6 +1137,194 @@ struct SolverT final : SolverBase {
         if ((rc = exchange())) return rc;
         if ((rc = mma_backward((REAL)omega, d_delta_lay))) return rc;
         if ((rc = exchange(true))) return rc;
+        return BDDMMA_OK;
+    }
+    // ---- learned iterations (bdd_cuda_learned_mma.cu:9-262, include/bdd_mma.h: bddmma_learned_iterations)
+    // The weighted exchange of the deferred differences: {lo, hi} of entry e = alpha[e] * the variable's sums (no division by n[v]), into
+    // d_delta_lay where the sweeps read it.  The same kernel family as exchange(), in its WEIGHTED instantiation, RUN = false.
+    void weighted_exchange()
+    {
+        const REAL* al = d_alpha_ent;
+        prof_begin(BDDMMA_K_FINISH_DELTA);
+        if (entry_by_var) {
+            hipLaunchKernelGGL((k_exchange_byvar<REAL, true>), dim3(cdiv(n_vars, 256)), dim3(256), 0, stream, d_mm_binned, d_var_ptr, d_delta_lay,
+                               (uint32_t)n_vars, (uint32_t)n_layers, RunGate{}, RunStep{}, al);
+        } else if (deterministic && !use_seg) {
+            // raw sums into the explicit API's scratch (the solver's own per-variable delta is rebuilt by the exit exchange)
+            hipLaunchKernelGGL((k_delta_gather<REAL, false>), dim3(cdiv(n_vars, 256)), dim3(256), 0, stream, d_mm_binned, d_var_ptr,
+                               d_vpos, d_delta_c, (uint32_t)n_vars, RunGate{});
+            hipLaunchKernelGGL((k_exchange_bcast<REAL, true>), dim3(cdiv(cdiv(n_layers, 4), 256)), dim3(256), 0, stream, (const REAL*)d_delta_c, d_evar,
+                               d_delta_lay, (uint32_t)n_layers, (uint32_t)n_vars, RunGate{}, RunStep{}, al);
+        } else if (use_seg) {
+#define LAUNCH_SEG_W(T_)                                                                                                                                  \
+    do {                                                                                                                                                  \
+        if (seg_groups <= 2)                                                                                                                              \
+            hipLaunchKernelGGL((k_exchange_seg<REAL, T_, 2, false, true>), dim3(n_bins), dim3(T_), seg_lds, stream, d_mm_binned,                         \
+                               reinterpret_cast<const uint4*>(d_seg_bin), (const uint32_t*)nullptr, 0u, reinterpret_cast<const uint4*>(d_seg_perm),      \
+                               reinterpret_cast<const uint2*>(d_seg_thr), seg_tile_off, seg_cnt_off, d_delta_lay, RunStep{}, al);                       \
+        else                                                                                                                                              \
+            hipLaunchKernelGGL((k_exchange_seg<REAL, T_, 4, false, true>), dim3(n_bins), dim3(T_), seg_lds, stream, d_mm_binned,                         \
+                               reinterpret_cast<const uint4*>(d_seg_bin), (const uint32_t*)nullptr, 0u, reinterpret_cast<const uint4*>(d_seg_perm),      \
+                               reinterpret_cast<const uint2*>(d_seg_thr), seg_tile_off, seg_cnt_off, d_delta_lay, RunStep{}, al);                       \
+    } while (0)
+            if (exch_small) LAUNCH_SEG_W(EXS_THREADS);
+            else if (exch_medium) LAUNCH_SEG_W(EXM_THREADS);
+            else LAUNCH_SEG_W(EX_THREADS);
+#undef LAUNCH_SEG_W
+        } else {
+#define LAUNCH_EX_W(T_, U_, N_)                                                                                                                           \
+    hipLaunchKernelGGL((k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_ITER, T_, U_, N_, false, true>), dim3(n_bins), dim3(T_), exch_lds, stream, d_mm_binned,  \
+                       d_bin_ptr, d_bvar, (const uint32_t*)nullptr, 0u, vars_per_bin, (uint32_t)n_vars, (uint32_t)n_layers, d_nbdds, (REAL*)nullptr,      \
+                       d_delta_lay, RunStep{}, al)
+            if (exch_medium) LAUNCH_EX_W(EXM_THREADS, EXM_UNROLL, EXM_NPT);
+            else if (exch_small) LAUNCH_EX_W(EXS_THREADS, EXS_UNROLL, EXS_NPT);
+            else LAUNCH_EX_W(EX_THREADS, EX_UNROLL, EX_NPT);
+#undef LAUNCH_EX_W
+        }
+        delta_var_valid = false;
+        prof_end(BDDMMA_K_FINISH_DELTA);
+    }
+    int isotropic_dist_weights(void* out, int on_device) override
+    {
+        HIPCHK(hipSetDevice(device));
+        REAL* dst = on_device ? (REAL*)out : d_tmp0;
+        hipLaunchKernelGGL((k_isotropic_alpha<REAL>), dim3(cdiv(n_layers, 256)), dim3(256), 0, stream, d_var, d_nbdds, dst, (uint32_t)n_layers);
+        HIPCHK(hipGetLastError());
+        if (!on_device) return copy_out(out, dst, n_layers * sizeof(REAL), 0);
+        HIPCHK(hipStreamSynchronize(stream));
+        return BDDMMA_OK;
+    }
+    int learned_iterations(const void* w, int w_dev, uint64_t num_itr, double omega, double slope, void* sol_avg, void* lb1_avg, void* lb2_avg,
+                           uint64_t cfi, double beta_d, int out_dev, uint64_t* itr_done) override
+    {
+        HIPCHK(hipSetDevice(device));
+        int rc;
+        if (itr_done) *itr_done = 0;
+        if (!w) { err = "learned_iterations: dist_weights is null"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if (cfi > 0 && (!sol_avg || !lb1_avg || !lb2_avg)) {
+            err = "learned_iterations: compute_history_for_itr > 0 needs sol_avg, lb_first_diff_avg and lb_second_diff_avg";
+            return BDDMMA_ERR_INVALID_ARGUMENT;
+        }
+        if (*lbfgs_attached > 0) {
+            err = "learned_iterations: an L-BFGS wrapper is attached to this solver (destroy it first: its history would not describe the costs any more)";
+            return BDDMMA_ERR_STATE;
+        }
+        if (run_stop) { err = "learned_iterations: run_solver is queueing iterations"; return BDDMMA_ERR_STATE; }
+        if (!d_alpha_ent && (rc = dalloc(&d_alpha_ent, n_layers))) return rc;
+        // the weights, layer order -> d_tmp0 (checked there) -> binned entry order
+        const size_t lbytes = n_layers * sizeof(REAL);
+        if (!w_dev) {
+            const REAL* h = (const REAL*)w;
+            for (uint64_t l = 0; l < n_layers; ++l)
+                if (!(h[l] >= REAL(0) && h[l] < std::numeric_limits<REAL>::infinity())) {
+                    err = "learned_iterations: dist_weights[" + std::to_string(l) + "] is negative or not finite";
+                    return BDDMMA_ERR_INVALID_ARGUMENT;
+                }
+        }
+        HIPCHK(hipMemcpyAsync(d_tmp0, w, lbytes, w_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+        if (w_dev) {
+            HIPCHK(hipMemsetAsync(d_counts, 0, sizeof(uint32_t), stream));
+            hipLaunchKernelGGL((k_count_bad_weights<REAL>), dim3(cdiv(n_layers, 256)), dim3(256), 0, stream, (const REAL*)d_tmp0, d_counts, (uint32_t)n_layers);
+            uint32_t bad = 0;
+            HIPCHK(hipMemcpyAsync(&bad, d_counts, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            if (bad) {
+                err = "learned_iterations: " + std::to_string(bad) + " of the dist_weights are negative or not finite";
+                return BDDMMA_ERR_INVALID_ARGUMENT;
+            }
+        }
+        hipLaunchKernelGGL((k_layers_to_entries<REAL>), dim3(cdiv(n_layers, 256)), dim3(256), 0, stream, (const REAL*)d_tmp0, d_lpos, d_alpha_ent, (uint32_t)n_layers);
+        HIPCHK(hipGetLastError());
+        // history buffers (:202-209): on the device; the caller's host outputs go through device copies, loaded first (an output the
+        // history does not reach keeps what the caller had put there, as in the reference)
+        const uint64_t B = n_bdds, L = n_layers;
+        REAL *o_sol = (REAL*)sol_avg, *o_lb1 = (REAL*)lb1_avg, *o_lb2 = (REAL*)lb2_avg;
+        REAL *last_sol = nullptr, *lb_last = nullptr, *lb_second = nullptr, *lb_third = nullptr, *chg = nullptr, *prev_chg = nullptr;
+        if (cfi > 0) {
+            if (!d_hist && (rc = dalloc(&d_hist, L + 5 * B))) return rc;
+            last_sol = d_hist; lb_last = d_hist + L; lb_second = lb_last + B; lb_third = lb_second + B; chg = lb_third + B; prev_chg = chg + B;
+            if (!out_dev) {
+                if (!d_hist_out && (rc = dalloc(&d_hist_out, L + 2 * B))) return rc;
+                o_sol = d_hist_out; o_lb1 = d_hist_out + L; o_lb2 = o_lb1 + B;
+                HIPCHK(hipMemcpyAsync(o_sol, sol_avg, L * sizeof(REAL), hipMemcpyHostToDevice, stream));
+                HIPCHK(hipMemcpyAsync(o_lb1, lb1_avg, B * sizeof(REAL), hipMemcpyHostToDevice, stream));
+                HIPCHK(hipMemcpyAsync(o_lb2, lb2_avg, B * sizeof(REAL), hipMemcpyHostToDevice, stream));
+            }
+        }
+        const REAL omega_r = (REAL)omega, beta = (REAL)beta_d;
+        const dim3 gl(cdiv(L, 256)), gb(cdiv(B, 256)), blk(256);
+        // the bound: read every iteration only where the stopping rule can fire (slope > 0); otherwise the set-once initial change is
+        // taken from two enqueued bounds, fetched after the loop (no host synchronisation inside it)
+        const bool track_lb = slope > 0;
+        const bool want_initial = !std::isfinite(initial_lb_change);
+        double lb_initial = 0.0, lb_prev = 0.0, lb_post = 0.0;
+        if (num_itr > 0) {
+            if (track_lb) {
+                if ((rc = lower_bound(&lb_initial))) return rc;
+            } else if (want_initial && (rc = lower_bound_enqueue(0))) return rc;
+        }
+        lb_post = lb_initial;
+        bool converged = false;
+        uint64_t tracked = 0, itr = 0, ran = 0;
+        for (itr = 0; itr < num_itr; ++itr) {
+            prof_active = profiling && (prof_iter++ % prof_stride == 0);
+            weighted_exchange();  // forward_iteration_learned_mm_dist: compute_delta of the deferred differences (:68)
+            if ((rc = mma_forward(omega_r, d_delta_lay))) return rc;
+            weighted_exchange();  // backward_iteration_learned_mm_dist (:143)
+            if ((rc = mma_backward(omega_r, d_delta_lay))) return rc;
+            ++ran;
+            if (cfi > 0 && (cfi >= num_itr - itr || converged)) {  // :211-254
+                HIPCHK(hipMemsetAsync(d_sol, 0, n_layers, stream));
+                if ((rc = launch_fwd<FWD_SOLUTION>(nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
+                hipLaunchKernelGGL((k_char_to_real<REAL>), gl, blk, 0, stream, (const char*)d_sol, last_sol, (uint32_t)L);
+                hipLaunchKernelGGL((k_lb_per_bdd<REAL>), gb, blk, 0, stream, d_T, d_root_slot, lb_last, (uint32_t)B);
+                if (tracked == 0) {
+                    HIPCHK(hipMemcpyAsync(o_sol, last_sol, L * sizeof(REAL), hipMemcpyDeviceToDevice, stream));
+                } else {
+                    hipLaunchKernelGGL((k_ema<REAL>), gl, blk, 0, stream, o_sol, (const REAL*)last_sol, beta, (uint32_t)L);
+                    hipLaunchKernelGGL((k_diff<REAL, REAL>), gb, blk, 0, stream, chg, (const REAL*)lb_last, (const REAL*)lb_second, (uint32_t)B);
+                    if (tracked == 1) {
+                        HIPCHK(hipMemcpyAsync(o_lb1, chg, B * sizeof(REAL), hipMemcpyDeviceToDevice, stream));
+                    } else {
+                        hipLaunchKernelGGL((k_ema<REAL>), gb, blk, 0, stream, o_lb1, (const REAL*)chg, beta, (uint32_t)B);
+                        hipLaunchKernelGGL((k_diff<REAL, REAL>), gb, blk, 0, stream, prev_chg, (const REAL*)lb_second, (const REAL*)lb_third, (uint32_t)B);
+                        hipLaunchKernelGGL((k_diff<REAL, REAL>), gb, blk, 0, stream, chg, (const REAL*)chg, (const REAL*)prev_chg, (uint32_t)B);
+                        if (tracked == 2) HIPCHK(hipMemcpyAsync(o_lb2, chg, B * sizeof(REAL), hipMemcpyDeviceToDevice, stream));
+                        else hipLaunchKernelGGL((k_ema<REAL>), gb, blk, 0, stream, o_lb2, (const REAL*)chg, beta, (uint32_t)B);
+                    }
+                }
+                HIPCHK(hipGetLastError());
+                // :251-252: second <- last, third <- second, last <- the old third (overwritten next time)
+                REAL* t = lb_third;
+                lb_third = lb_second;
+                lb_second = lb_last;
+                lb_last = t;
+                ++tracked;
+            }
+            if (track_lb) {
+                lb_prev = lb_post;
+                if ((rc = lower_bound(&lb_post))) return rc;
+                if (itr == 0 && want_initial) initial_lb_change = std::abs(lb_initial - lb_post);   // set_initial_lb_change: once per solver
+                if (!converged && std::abs(lb_prev - lb_post) < slope * initial_lb_change) converged = true;
+                if (converged && tracked == cfi) break;
+            } else if (itr == 0 && want_initial && (rc = lower_bound_enqueue(1))) {
+                return rc;
+            }
+        }
+        // exit: the isotropic exchange of the last backward pass's differences — the state bddmma_iteration leaves
+        if (ran > 0 && (rc = exchange())) return rc;
+        if (ran > 0 && !track_lb && want_initial) {
+            double a = 0.0, b = 0.0;
+            if ((rc = lower_bound_fetch(0, &a)) || (rc = lower_bound_fetch(1, &b))) return rc;
+            initial_lb_change = std::abs(a - b);
+        }
+        if (cfi > 0 && !out_dev) {
+            HIPCHK(hipMemcpyAsync(sol_avg, o_sol, L * sizeof(REAL), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(lb1_avg, o_lb1, B * sizeof(REAL), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(lb2_avg, o_lb2, B * sizeof(REAL), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+        if (itr_done) *itr_done = ran;
         return BDDMMA_OK;
     }
     // run_solver for the plain MMA iteration with the termination tests on the device (kernels.hpp: run_ctl_step).  The host

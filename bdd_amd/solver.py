@@ -221,6 +221,65 @@ class bdd_hip_parallel_mma:
     def distribute_delta(self):
         self._ck(self._L.bddmma_distribute_delta(self._h))
 
+    # ---- learned iterations (bdd_cuda_learned_mma<REAL>::iterations; Python binding bdd_cuda_learned_mma_py.cu:580-600)
+    def _learned_buf(self, x, n, what):
+        """(pointer, on_device) of a REAL[n] argument: a torch device tensor or a numpy array of the solver's precision"""
+        if _is_dev(x):
+            if x.numel() != n:
+                raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: {what} has {x.numel()} values, the solver needs {n}")
+            if not x.is_contiguous():
+                raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: {what} must be contiguous")
+            if x.element_size() != np.dtype(self.value_type).itemsize or not x.is_floating_point():
+                raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: {what} is {x.dtype}, the solver's values are "
+                                       f"{np.dtype(self.value_type).name}")
+            return _dev_ptr(x, n, self.value_type), 1
+        if not isinstance(x, np.ndarray):
+            raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: {what} must be a numpy array or a device tensor")
+        if x.dtype != self.value_type:
+            raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: {what} is {x.dtype}, the solver's values are "
+                                   f"{np.dtype(self.value_type).name}")
+        if x.size != n:
+            raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: {what} has {x.size} values, the solver needs {n}")
+        if not x.flags.c_contiguous:
+            raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: {what} must be contiguous")
+        return _ptr(x), 0
+
+    def learned_iterations(self, dist_weights, num_itr, omega=0.5, improvement_slope=1e-6, sol_avg=None, lb_first_diff_avg=None,
+                           lb_second_diff_avg=None, compute_history_for_itr=0, history_avg_beta=0.9) -> int:
+        """iterations(dist_weights, ...) of the learned solver: MMA passes that add dist_weights[l] * (sum of the deferred differences
+        of the layer's variable) instead of the sum / nr_bdds; returns the number of iterations run.  dist_weights: REAL[nr_layers] in
+        the order of get_solver_costs.  With compute_history_for_itr > 0, sol_avg (REAL[nr_layers]), lb_first_diff_avg and
+        lb_second_diff_avg (REAL[nr_bdds]) are updated in place (all three on the host or all three on the device).
+        State contract and error codes: include/bdd_mma.h, bddmma_learned_iterations."""
+        w, w_dev = self._learned_buf(dist_weights, self.nr_layers(), "dist_weights")
+        outs = [None, None, None]
+        out_dev = 0
+        if int(compute_history_for_itr) > 0:
+            bufs = (sol_avg, lb_first_diff_avg, lb_second_diff_avg)
+            if any(b is None for b in bufs):
+                raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: compute_history_for_itr > 0 needs sol_avg, "
+                                       "lb_first_diff_avg and lb_second_diff_avg")
+            devs = [_is_dev(b) for b in bufs]
+            if len(set(devs)) != 1:
+                raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: the history outputs must all be on the host or all on the device")
+            sizes = (self.nr_layers(), self.nr_bdds(), self.nr_bdds())
+            names = ("sol_avg", "lb_first_diff_avg", "lb_second_diff_avg")
+            outs = [self._learned_buf(b, n, nm)[0] for b, n, nm in zip(bufs, sizes, names)]
+            out_dev = 1 if devs[0] else 0
+        done = C.c_uint64()
+        self._ck(self._L.bddmma_learned_iterations(self._h, w, w_dev, int(num_itr), float(omega), float(improvement_slope), outs[0], outs[1],
+                                                    outs[2], int(compute_history_for_itr), float(history_avg_beta), out_dev, C.byref(done)))
+        return int(done.value)
+
+    def get_isotropic_dist_weights(self, out=None):
+        """1 / nr_bdds(variable) per layer (get_solver_costs order): the weights with which learned_iterations is iterations"""
+        if out is not None:
+            self._ck(self._L.bddmma_isotropic_dist_weights(self._h, _dev_ptr(out, self.nr_layers(), self.value_type), 1))
+            return out
+        out = np.zeros(self.nr_layers(), self.value_type)
+        self._ck(self._L.bddmma_isotropic_dist_weights(self._h, _ptr(out), 0))
+        return out
+
     def set_delta(self, delta_lo_hi):
         if _is_dev(delta_lo_hi):
             self._ck(self._L.bddmma_set_delta(self._h, _dev_ptr(delta_lo_hi, 2 * self.nr_variables(), self.value_type), 1))

@@ -223,6 +223,45 @@ int bddmma_distribute_delta(bddmma_solver* s);
 int bddmma_get_delta(const bddmma_solver* s, void* out, int on_device);
 int bddmma_set_delta(bddmma_solver* s, const void* in, int on_device);
 
+/* ---- learned iterations (bdd_cuda_learned_mma<REAL>, src/bdd_solver/bdd_cuda_learned_mma.cu:9-262; Python binding
+ * bdd_cuda_learned_mma_py.cu:300-326,580-600) -----------------------------------------------------------------------------
+ * bddmma_learned_iterations = iterations(dist_weights, num_itr, omega, improvement_slope, sol_avg, lb_first_diff_avg, lb_second_diff_avg,
+ * compute_history_for_itr, history_avg_beta) (:184-270) without the per-layer omega_vec.  Every pass (forward, then backward) starts from
+ * the sums of the deferred min-marginal differences per variable, Slo[v] = sum max(-mm, 0), Shi[v] = sum max(mm, 0) — NOT divided by
+ * nr_bdds(v) — and adds alpha[l] * S[v(l)] to layer l: lo' = lo + min(mm, 0) + alpha * Slo, hi' = hi + min(-mm, 0) + alpha * Shi (:37,:42).
+ * The product is formed in REAL from the sum rounded to REAL.  With alpha[l] = 1 / nr_bdds(v(l)) (bddmma_isotropic_dist_weights) this is
+ * bddmma_iteration up to that rounding.
+ *   dist_weights   REAL[nr_layers] in the public layer order (bddmma_get_solver_costs, bddmma_bdds_solution(sorted = 0),
+ *                  bddmma_layer_variables), host or device (weights_on_device).  A negative or non-finite weight gives
+ *                  BDDMMA_ERR_INVALID_ARGUMENT and leaves the solver untouched.  sum over the layers of a variable = 1 is NOT enforced:
+ *                  only with it is the bound a valid bound of the original problem (costs are then a reparametrisation of it).
+ *   improvement_slope  > 0: lower_bound() after every iteration (one host round trip each); stop when |lb_prev - lb_post| <
+ *                  improvement_slope * initial_lb_change and the history is complete (:261-266).  initial_lb_change = |lb before - lb after
+ *                  the first iteration| of the first call on this solver that runs an iteration (set once per solver, :263,
+ *                  bdd_cuda_learned_mma.h:111-116).  <= 0: all num_itr iterations, no host synchronisation between them.
+ *   compute_history_for_itr > 0: over the last that many iterations (and every iteration after convergence) sol_avg REAL[nr_layers]
+ *                  becomes an exponential moving average (factor history_avg_beta) of bdds_solution (public layer order, 0 / 1),
+ *                  lb_first_diff_avg REAL[nr_bdds] of the change of lower_bound_per_bdd, lb_second_diff_avg REAL[nr_bdds] of its second
+ *                  difference; the first value of each is copied in, not averaged (:211-254).  An output the history does not reach keeps
+ *                  its content.  Host or device (outputs_on_device); ignored when compute_history_for_itr = 0 (may be null then).
+ *   itr_done       the number of iterations run (the reference returns the loop index at the break, one less when it stops early).
+ * State contract (the reference leaves it open):
+ *   entry  the first pass's delta is derived from the solver's deferred differences with the given weights; a pending isotropic delta
+ *          (bddmma_get_delta), which is derived from the same differences, is ignored;
+ *   exit   the deferred differences are the last backward pass's, and the per-variable delta and its per-layer broadcast are what the
+ *          isotropic exchange of them gives — the state bddmma_iteration leaves.  So bddmma_get_delta, bddmma_distribute_delta,
+ *          bddmma_iteration(s), bddmma_run_solver, bddmma_min_marginals and bddmma_save work unchanged afterwards, and learned iterations
+ *          with isotropic weights (n) followed by bddmma_iterations (m) equal bddmma_iterations (n + m).
+ * An L-BFGS wrapper attached to the handle (bddmma_lbfgs_create without bddmma_lbfgs_destroy yet) makes the call return BDDMMA_ERR_STATE:
+ * its history would describe costs that the iterations have moved.  Synchronous when improvement_slope > 0, a history is written to the
+ * host or the initial change is still unset; otherwise returns once queued. */
+int bddmma_learned_iterations(bddmma_solver* s, const void* dist_weights, int weights_on_device, uint64_t num_itr, double omega,
+                              double improvement_slope, void* sol_avg, void* lb_first_diff_avg, void* lb_second_diff_avg,
+                              uint64_t compute_history_for_itr, double history_avg_beta, int outputs_on_device, uint64_t* itr_done);
+/* REAL[nr_layers], public layer order: 1 / nr_bdds(variable of the layer) in REAL — the weights with which learned iterations are the
+ * plain ones (the isotropic alpha of the learned solver's Python side). */
+int bddmma_isotropic_dist_weights(bddmma_solver* s, void* out, int on_device);
+
 /* ---- min-marginals and per-BDD solutions -------------------------------- */
 /* min_marginals_cuda(get_sorted) (bdd_cuda_base.cu:716-749): var int32[nr_layers], mm0/mm1 REAL[nr_layers].
  * sorted != 0: ordered by (variable, bdd) as primal_variable_sorting_order_ (bdd_cuda_base.cu:379-391). */
