@@ -86,6 +86,7 @@ SIGNATURES = {
     "bddmma_iteration": (_I, [_V, _D]),
     "bddmma_iterations": (_I, [_V, _D, _U64]),
     "bddmma_learned_iterations": (_I, [_V, _V, _I, _U64, _D, _D, _V, _V, _V, _U64, _D, _I, C.POINTER(_U64)]),
+    "bddmma_learned_iterations_omega_vec": (_I, [_V, _V, _I, _U64, _V, _I, _D, _V, _V, _V, _U64, _D, _I, C.POINTER(_U64)]),
     "bddmma_isotropic_dist_weights": (_I, [_V, _V, _I]),
     "bddmma_forward_mm": (_I, [_V, _D, _V, _I]),
     "bddmma_backward_mm": (_I, [_V, _D, _V, _I]),

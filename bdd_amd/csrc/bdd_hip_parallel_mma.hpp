@@ -181,11 +181,19 @@ class bdd_hip_parallel_mma {
     // learned iterations (bdd_cuda_learned_mma.h: iterations; include/bdd_mma.h: bddmma_learned_iterations): device pointers, as the
     // reference's thrust::device_ptr arguments; dist_weights REAL[nr_layers], sol_avg REAL[nr_layers], the two lb averages REAL[nr_bdds]
     // (may be null when compute_history_for_itr = 0).  Returns the number of iterations run.
+    // dev_omega_vec (REAL[nr_layers], same order; include/bdd_mma.h: bddmma_learned_iterations_omega_vec): one omega per layer in place of
+    // omega, as the reference's omega_vec
     int iterations(const REAL* dev_dist_weights, const int num_itr, const REAL omega, const double improvement_slope = 1e-6,
                    REAL* dev_sol_avg = nullptr, REAL* dev_lb_first_diff_avg = nullptr, REAL* dev_lb_second_diff_avg = nullptr,
-                   const int compute_history_for_itr = 0, const REAL history_avg_beta = 0.9)
+                   const int compute_history_for_itr = 0, const REAL history_avg_beta = 0.9, const REAL* dev_omega_vec = nullptr)
     {
         uint64_t done = 0;
+        if (dev_omega_vec) {
+            check(bddmma_learned_iterations_omega_vec(h_, dev_dist_weights, 1, (uint64_t)std::max(num_itr, 0), dev_omega_vec, 1, improvement_slope,
+                                                      dev_sol_avg, dev_lb_first_diff_avg, dev_lb_second_diff_avg,
+                                                      (uint64_t)std::max(compute_history_for_itr, 0), history_avg_beta, 1, &done));
+            return (int)done;
+        }
         check(bddmma_learned_iterations(h_, dev_dist_weights, 1, (uint64_t)std::max(num_itr, 0), omega, improvement_slope, dev_sol_avg,
                                         dev_lb_first_diff_avg, dev_lb_second_diff_avg, (uint64_t)std::max(compute_history_for_itr, 0),
                                         history_avg_beta, 1, &done));
@@ -215,6 +223,31 @@ class bdd_hip_parallel_mma {
         check(bddmma_learned_iterations(h_, dist_weights.data(), 0, (uint64_t)std::max(num_itr, 0), omega, improvement_slope, sol_avg.data(),
                                         lb_first_diff_avg.data(), lb_second_diff_avg.data(), (uint64_t)std::max(compute_history_for_itr, 0),
                                         history_avg_beta, 0, &done));
+        return (int)done;
+    }
+    // the same with one omega per layer, last as in the reference (bdd_cuda_learned_mma.h: iterations(..., omega_vec); include/bdd_mma.h:
+    // bddmma_learned_iterations_omega_vec): REAL[nr_layers] in the order of dist_weights; omega is then not used
+    int iterations(const std::vector<REAL>& dist_weights, const int num_itr, const REAL omega, const double improvement_slope,
+                   const std::vector<REAL>& omega_vec)
+    {
+        std::vector<REAL> none;
+        return iterations(dist_weights, num_itr, omega, improvement_slope, none, none, none, 0, REAL(0.9), omega_vec);
+    }
+    int iterations(const std::vector<REAL>& dist_weights, const int num_itr, const REAL /*omega*/, const double improvement_slope,
+                   std::vector<REAL>& sol_avg, std::vector<REAL>& lb_first_diff_avg, std::vector<REAL>& lb_second_diff_avg,
+                   const int compute_history_for_itr, const REAL history_avg_beta, const std::vector<REAL>& omega_vec)
+    {
+        if (dist_weights.size() != nr_layers()) throw std::runtime_error("bdd_mma: dist_weights must hold nr_layers() values");
+        if (omega_vec.size() != nr_layers()) throw std::runtime_error("bdd_mma: omega_vec must hold nr_layers() values");
+        if (compute_history_for_itr > 0) {
+            sol_avg.resize(nr_layers());
+            lb_first_diff_avg.resize(nr_bdds());
+            lb_second_diff_avg.resize(nr_bdds());
+        }
+        uint64_t done = 0;
+        check(bddmma_learned_iterations_omega_vec(h_, dist_weights.data(), 0, (uint64_t)std::max(num_itr, 0), omega_vec.data(), 0, improvement_slope,
+                                                  sol_avg.data(), lb_first_diff_avg.data(), lb_second_diff_avg.data(),
+                                                  (uint64_t)std::max(compute_history_for_itr, 0), history_avg_beta, 0, &done));
         return (int)done;
     }
     // 1 / nr_bdds(variable) per layer, public layer order (the weights with which iterations(...) above is iteration())

@@ -221,7 +221,23 @@ int bddmma_learned_iterations(bddmma_solver* s, const void* dist_weights, int we
 {
     return guarded(s, [&](SolverBase* b) {
         return b->learned_iterations(dist_weights, weights_on_device, num_itr, omega, improvement_slope, sol_avg, lb_first_diff_avg,
-                                     lb_second_diff_avg, compute_history_for_itr, history_avg_beta, outputs_on_device, itr_done);
+                                     lb_second_diff_avg, compute_history_for_itr, history_avg_beta, outputs_on_device, itr_done, nullptr, 0);
+    });
+}
+int bddmma_learned_iterations_omega_vec(bddmma_solver* s, const void* dist_weights, int weights_on_device, uint64_t num_itr, const void* omega_vec,
+                                        int omega_vec_on_device, double improvement_slope, void* sol_avg, void* lb_first_diff_avg,
+                                        void* lb_second_diff_avg, uint64_t compute_history_for_itr, double history_avg_beta, int outputs_on_device,
+                                        uint64_t* itr_done)
+{
+    return guarded(s, [&](SolverBase* b) {
+        if (!omega_vec) {
+            if (itr_done) *itr_done = 0;
+            b->err = "learned_iterations: omega_vec is null";
+            return BDDMMA_ERR_INVALID_ARGUMENT;
+        }
+        return b->learned_iterations(dist_weights, weights_on_device, num_itr, 0.0, improvement_slope, sol_avg, lb_first_diff_avg,
+                                     lb_second_diff_avg, compute_history_for_itr, history_avg_beta, outputs_on_device, itr_done, omega_vec,
+                                     omega_vec_on_device);
     });
 }
 int bddmma_isotropic_dist_weights(bddmma_solver* s, void* out, int on_device)

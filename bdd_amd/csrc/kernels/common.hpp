@@ -28,7 +28,13 @@ struct DevPtrs {
     double* lb_partial;      // per pack (narrow packs first, then wide)
     REAL* x_layer;           // BWD_SOLVE: net_solver_costs x = (hi' - lo') + mm (bdd_cuda_parallel_mma.cu:432-463) in layer order, formed by the sweep itself
                              // from the new arc costs and the deferred difference (nullptr: not wanted; SolverT::lbfgs_views)
-    REAL* mm0_out;           // BWD_MARGINALS outputs, per layer
+    // BWD_MARGINALS outputs, per layer.  The slot of mm0_out carries omega_lay in the SOLVE sweeps' OV instantiation (one omega per
+    // layer, in layer order; learned iterations with omega_vec): no SOLVE sweep writes mm0_out, and sharing the slot keeps every field
+    // behind it, and every kernel argument behind DevPtrs, where it was.
+    union {
+        REAL* mm0_out;
+        const REAL* omega_lay;
+    };
     REAL* mm1_out;
     char* sol_out;           // FWD_SOLUTION output, per layer
     // Device-resident run_solver (run_ctl_step): when the termination test of run_solver_util.h:56-73 has fired on the device, the
@@ -121,6 +127,15 @@ __device__ __forceinline__ REAL mm_diff(REAL m0, REAL m1, REAL omega)
     const bool fin = (int)rfinite(m0) & (int)rfinite(m1);
     const REAL t = omega * (m1 - m0);
     return fin ? t : REAL(0);
+}
+// The omega of the deferred difference of global layer `l`: the scalar argument, or in the OV instantiation of a SOLVE sweep the layer's
+// entry of DevPtrs::omega_lay (learned iterations with omega_vec).  Same product in REAL either way, so an omega_lay that holds the
+// scalar everywhere gives bit-identical results.
+template <bool OV, typename REAL>
+__device__ __forceinline__ REAL omega_of(const DevPtrs<REAL>& d, REAL omega, uint32_t l)
+{
+    if constexpr (OV) return d.omega_lay[l];
+    else return omega;
 }
 // min(x, 0) and min(-x, 0) of a min-marginal difference (never NaN).  One instruction; __builtin_fminf on a value that went through a
 // select costs a v_max x, x canonicalisation first.
@@ -398,6 +413,12 @@ __device__ __forceinline__ rsrc_t make_rsrc(const T* p, uint64_t n_elems)
 {
     const uint64_t bytes = n_elems * sizeof(T);
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(p), 0, (uint32_t)(bytes > 0xFFFFFFFEull ? 0xFFFFFFFEull : bytes), 0x00020000);
+}
+// OV sweeps (omega_of): DevPtrs::omega_lay from layer l0 on, for buffer loads with the addressing of the {lo, hi} pairs at half the stride
+template <bool OV, typename REAL>
+__device__ __forceinline__ rsrc_t omega_rsrc(const DevPtrs<REAL>& d, uint32_t l0)
+{
+    return make_rsrc(OV ? d.omega_lay + l0 : (const REAL*)nullptr, OV ? d.n_layers - l0 : 0u);
 }
 __device__ __forceinline__ uint32_t bload_u32(rsrc_t r, uint32_t off) { return __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, BDDMMA_LD_AUX); }
 __device__ __forceinline__ uint32_t bload_u16(rsrc_t r, uint32_t off) { return __builtin_amdgcn_raw_buffer_load_b16(r, off, 0, 0); }

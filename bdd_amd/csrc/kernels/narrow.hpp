@@ -210,7 +210,7 @@ __device__ __forceinline__ void store_vals(const double (&v)[R], double* dst, ui
 #endif
 // SEG = false: no pack of the launch has a layer wider than two nodes — the segmented minimum is the DPP pair, its LDS variant and the
 // per-lane-group branch on the pack's step count are compiled out.
-template <typename REAL, int R, int MODE, int WPB, int LA = BDDMMA_LOOKAHEAD, bool SEG = true, bool NT = false>
+template <typename REAL, int R, int MODE, int WPB, int LA = BDDMMA_LOOKAHEAD, bool SEG = true, bool NT = false, bool OV = false>
 __device__ __forceinline__ void fwd_narrow_body(const DevPtrs<REAL>& d, const PackDev& pk, REAL omega, uint32_t block_id)
 {
     constexpr int W = 64 * R;
@@ -248,6 +248,7 @@ __device__ __forceinline__ void fwd_narrow_body(const DevPtrs<REAL>& d, const Pa
     const uint32_t slot_first = !has_pack ? 0 : (hdr ? hp[0] : pk.hop_node_off[q0]), l0 = !has_pack ? 0 : (hdr ? hp[2] : pk.hop_layer_off[q0]);  // the pack's first slot / layer: everything below is relative to them (HopWindow)
     NarrowRs<REAL> rs(d);
     rs.rebase_layers(d, l0);
+    const rsrc_t rw = omega_rsrc<OV>(d, l0);  // OV: omega per layer, loaded at the difference (La.lg: layer relative to l0; padding lanes: harmless)
     uint32_t ent[STAGE_ITERS], esl[STAGE_ITERS];
     if (hdr && MODE == FWD_SOLVE) stage_load_tables<REAL, WPB, (NT ? 2 : BDDMMA_LD_TAB_AUX)>(ent, esl, rs, c0_h, cnt_h, tid);  // on their way while the pipeline is set up
     REAL* const Tp = d.T + slot_first;
@@ -399,7 +400,9 @@ __device__ __forceinline__ void fwd_narrow_body(const DevPtrs<REAL>& d, const Pa
                     REAL m0 = act ? (f[r] + lc) + tl[r] : INF;
                     REAL m1 = act ? (f[r] + hc) + th[r] : INF;
                     seg_min2(m0, m1, lane, nw_pos(w), nw_len(w), steps, sM);
-                    const REAL mm = mm_diff(m0, m1, omega);
+                    REAL om = omega;
+                    if constexpr (OV) hop_load(om, rw, La.lg[r] * (uint32_t)sizeof(REAL), 0u);
+                    const REAL mm = mm_diff(m0, m1, om);
                     mmv[r] = mm;
                     nlo[r] = (lc + min0(mm)) + dd[r].x;
                     nhi[r] = (hc + min0_neg(mm)) + dd[r].y;
@@ -487,13 +490,13 @@ __device__ __forceinline__ void fwd_narrow_body(const DevPtrs<REAL>& d, const Pa
 #ifndef BDDMMA_N1_WAVES
 #define BDDMMA_N1_WAVES(REAL, R, MODE, WPB) ((MODE) == 1 && sizeof(REAL) == 4 ? ((R) == 1 ? 6 : (R) == 2 && (WPB) == 1 ? 5 : 1) : 1)
 #endif
-template <typename REAL, int R, int MODE, int WPB, bool SEG = true, bool NT = false>
+template <typename REAL, int R, int MODE, int WPB, bool SEG = true, bool NT = false, bool OV = false>
 __global__ void __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(BDDMMA_N1_WAVES(REAL, R, MODE, WPB)))) k_fwd_narrow(DevPtrs<REAL> d, PackDev pk, REAL omega)
 {
-    fwd_narrow_body<REAL, R, MODE, WPB, BDDMMA_LOOKAHEAD, SEG, NT>(d, pk, omega, blockIdx.x);
+    fwd_narrow_body<REAL, R, MODE, WPB, BDDMMA_LOOKAHEAD, SEG, NT, OV>(d, pk, omega, blockIdx.x);
 }
 
-template <typename REAL, int R, int MODE, int WPB, int LA = BDDMMA_LOOKAHEAD, bool SEG = true, bool NT = false>
+template <typename REAL, int R, int MODE, int WPB, int LA = BDDMMA_LOOKAHEAD, bool SEG = true, bool NT = false, bool OV = false>
 __device__ __forceinline__ void bwd_narrow_body(const DevPtrs<REAL>& d, const PackDev& pk, REAL omega, uint32_t block_id)
 {
     constexpr int W = 64 * R;
@@ -525,6 +528,7 @@ __device__ __forceinline__ void bwd_narrow_body(const DevPtrs<REAL>& d, const Pa
     const uint32_t slot_first = !has_pack ? 0 : (hdr ? hp[0] : pk.hop_node_off[q0]), l0 = !has_pack ? 0 : (hdr ? hp[2] : pk.hop_layer_off[q0]);  // the pack's first slot / layer: everything below is relative to them (HopWindow)
     NarrowRs<REAL> rs(d);
     rs.rebase_layers(d, l0);
+    const rsrc_t rw = omega_rsrc<OV>(d, l0);  // OV: omega per layer, loaded at the difference (La.lg: layer relative to l0; padding lanes: harmless)
     uint32_t ent[STAGE_ITERS], esl[STAGE_ITERS];
     if (hdr && MODE == BWD_SOLVE) stage_load_tables<REAL, WPB, (NT ? 2 : BDDMMA_LD_TAB_AUX)>(ent, esl, rs, c0_h, cnt_h, tid);  // on their way while the pipeline is set up
     REAL* const Tp = d.T + slot_first;
@@ -637,7 +641,9 @@ __device__ __forceinline__ void bwd_narrow_body(const DevPtrs<REAL>& d, const Pa
                     REAL m0 = act ? (fa[r] + lc) + tl[r] : INF;
                     REAL m1 = act ? (fa[r] + hc) + th[r] : INF;
                     seg_min2(m0, m1, lane, nw_pos(w), nw_len(w), steps, sM);
-                    const REAL mm = mm_diff(m0, m1, omega);
+                    REAL om = omega;
+                    if constexpr (OV) hop_load(om, rw, La.lg[r] * (uint32_t)sizeof(REAL), 0u);
+                    const REAL mm = mm_diff(m0, m1, om);
                     mmv[r] = mm;
                     nlo[r] = (lc + min0(mm)) + dd[r].x;
                     nhi[r] = (hc + min0_neg(mm)) + dd[r].y;
@@ -675,6 +681,7 @@ __device__ __forceinline__ void bwd_narrow_body(const DevPtrs<REAL>& d, const Pa
                     }
                 }
                 if (MODE == BWD_MARGINALS) {
+                    // DevPtrs: mm0_out shares its slot with omega_lay, which the OV solve sweeps read: only BWD_MARGINALS sweeps may write it
                     if (nw_head(w)) {
                         d.mm0_out[l0 + La.lg[r]] = lp[r];
                         d.mm1_out[l0 + La.lg[r]] = hp[r];
@@ -727,10 +734,10 @@ __device__ __forceinline__ void bwd_narrow_body(const DevPtrs<REAL>& d, const Pa
     if (lane == 0) d.lb_partial[pk.lb_base + p] = s;
 }
 
-template <typename REAL, int R, int MODE, int WPB, bool SEG = true, bool NT = false>
+template <typename REAL, int R, int MODE, int WPB, bool SEG = true, bool NT = false, bool OV = false>
 __global__ void __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(BDDMMA_N1_WAVES(REAL, R, MODE, WPB)))) k_bwd_narrow(DevPtrs<REAL> d, PackDev pk, REAL omega)
 {
-    bwd_narrow_body<REAL, R, MODE, WPB, BDDMMA_LOOKAHEAD, SEG, NT>(d, pk, omega, blockIdx.x);
+    bwd_narrow_body<REAL, R, MODE, WPB, BDDMMA_LOOKAHEAD, SEG, NT, OV>(d, pk, omega, blockIdx.x);
 }
 
 }  // namespace bddmma

@@ -32,7 +32,8 @@ __device__ __forceinline__ void load_costs(typename Pair<REAL>::type (&c)[R], co
     for (int g = 0; g < R; ++g) hop_load(c[g], lohi, r[g][2] & 0xFFFFu, lbase * (uint32_t)sizeof(P2));
 }
 
-template <typename REAL, int R, int WPB, bool GEN, int LA = BDDMMA_LOOKAHEAD, bool NT = false>
+// OV: the learned iterations' omega per layer (DevPtrs::omega_lay), loaded at the top of the hop with the {lo, hi} addressing of the record
+template <typename REAL, int R, int WPB, bool GEN, int LA = BDDMMA_LOOKAHEAD, bool NT = false, bool OV = false>
 __device__ __forceinline__ void fwd_narrow2_body(const DevPtrs<REAL>& d, const PackDev& pk, const uint32_t* __restrict__ srec,
                                                  const uint32_t* __restrict__ srec_off, uint32_t srec_words, REAL omega, uint32_t block_id,
                                                  const uint32_t* __restrict__ hdr_pack = nullptr, const uint32_t* __restrict__ hdr_quad = nullptr)
@@ -172,6 +173,12 @@ __device__ __forceinline__ void fwd_narrow2_body(const DevPtrs<REAL>& d, const P
 #endif
             u4v (&ra)[R] = rc[0];
             P2 (&La)[R] = Lr[0];
+            REAL wv[R];  // OV: omega of the lanes' layers
+            if constexpr (OV) {
+                const rsrc_t rw = omega_rsrc<OV>(d, l0);
+#pragma unroll
+                for (int r = 0; r < R; ++r) hop_load(wv[r], rw, (ra[r][2] & 0xFFFFu) >> 1, lb[0] * S);
+            }
             // ---- the hop's LDS reads, one batch
             REAL f[R], tl[R], th[R];
             P2 dd[R];
@@ -204,7 +211,7 @@ __device__ __forceinline__ void fwd_narrow2_body(const DevPtrs<REAL>& d, const P
                 REAL m0 = (f[r] + lc) + tl[r], m1 = (f[r] + hc) + th[r];
                 if (!GEN || steps <= 1) pair_min_aligned(m0, m1, (ra[r][3] & 1u) != 0);
                 else seg_min2(m0, m1, lane, (ra[r][3] >> 8) & 63u, 0u, steps, sM);
-                const REAL mm = mm_diff1(m0, m1, omega);
+                const REAL mm = mm_diff1(m0, m1, OV ? wv[r] : omega);
                 mmv[r] = mm;
                 nc[r].x = (lc + min0(mm)) + dd[r].x;
                 nc[r].y = (hc + min0_neg(mm)) + dd[r].y;
@@ -267,14 +274,14 @@ __device__ __forceinline__ void fwd_narrow2_body(const DevPtrs<REAL>& d, const P
 #ifndef BDDMMA_N2_WAVES
 #define BDDMMA_N2_WAVES(REAL, R) ((R) <= 2 ? (sizeof(REAL) == 4 ? 5 : 4) : 1)
 #endif
-template <typename REAL, int R, int WPB, bool GEN, bool NT = false>
+template <typename REAL, int R, int WPB, bool GEN, bool NT = false, bool OV = false>
 __global__ void __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(BDDMMA_N2_WAVES(REAL, R)))) k_fwd_narrow2(DevPtrs<REAL> d, PackDev pk, const uint32_t* __restrict__ srec, const uint32_t* __restrict__ srec_off,
                                                           uint32_t srec_words, REAL omega)
 {
-    fwd_narrow2_body<REAL, R, WPB, GEN, BDDMMA_LOOKAHEAD, NT>(d, pk, srec, srec_off, srec_words, omega, blockIdx.x, pk.hdr_pack, pk.hdr_quad);
+    fwd_narrow2_body<REAL, R, WPB, GEN, BDDMMA_LOOKAHEAD, NT, OV>(d, pk, srec, srec_off, srec_words, omega, blockIdx.x, pk.hdr_pack, pk.hdr_quad);
 }
 
-template <typename REAL, int R, int WPB, bool GEN, int LA = BDDMMA_LOOKAHEAD, bool NT = false>
+template <typename REAL, int R, int WPB, bool GEN, int LA = BDDMMA_LOOKAHEAD, bool NT = false, bool OV = false>
 __device__ __forceinline__ void bwd_narrow2_body(const DevPtrs<REAL>& d, const PackDev& pk, const uint32_t* __restrict__ srec,
                                                  const uint32_t* __restrict__ srec_off, uint32_t srec_words, REAL omega, uint32_t block_id,
                                                  const uint32_t* __restrict__ hdr_pack = nullptr, const uint32_t* __restrict__ hdr_quad = nullptr)
@@ -396,6 +403,12 @@ __device__ __forceinline__ void bwd_narrow2_body(const DevPtrs<REAL>& d, const P
             u4v (&ra)[R] = rc[0];
             REAL (&fa)[R] = fr[0];
             P2 (&La)[R] = Lr[0];
+            REAL wv[R];  // OV: omega of the lanes' layers
+            if constexpr (OV) {
+                const rsrc_t rw = omega_rsrc<OV>(d, l0);
+#pragma unroll
+                for (int r = 0; r < R; ++r) hop_load(wv[r], rw, (ra[r][2] & 0xFFFFu) >> 1, lb[1] * S);
+            }
             // ---- LDS reads
             REAL tl[R], th[R];
             P2 dd[R];
@@ -417,7 +430,7 @@ __device__ __forceinline__ void bwd_narrow2_body(const DevPtrs<REAL>& d, const P
                 REAL m0 = (fa[r] + lc) + tl[r], m1 = (fa[r] + hc) + th[r];
                 if (!GEN || steps <= 1) pair_min_aligned(m0, m1, (ra[r][3] & 1u) != 0);
                 else seg_min2(m0, m1, lane, (ra[r][3] >> 8) & 63u, 0u, steps, sM);
-                const REAL mm = mm_diff1(m0, m1, omega);
+                const REAL mm = mm_diff1(m0, m1, OV ? wv[r] : omega);
                 mmv[r] = mm;
                 nc[r].x = (lc + min0(mm)) + dd[r].x;
                 nc[r].y = (hc + min0_neg(mm)) + dd[r].y;
@@ -490,11 +503,11 @@ __device__ __forceinline__ void bwd_narrow2_body(const DevPtrs<REAL>& d, const P
     if (lane == 0) d.lb_partial[pk.lb_base + p] = s;
 }
 
-template <typename REAL, int R, int WPB, bool GEN, bool NT = false>
+template <typename REAL, int R, int WPB, bool GEN, bool NT = false, bool OV = false>
 __global__ void __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(BDDMMA_N2_WAVES(REAL, R)))) k_bwd_narrow2(DevPtrs<REAL> d, PackDev pk, const uint32_t* __restrict__ srec, const uint32_t* __restrict__ srec_off,
                                                           uint32_t srec_words, REAL omega)
 {
-    bwd_narrow2_body<REAL, R, WPB, GEN, BDDMMA_LOOKAHEAD, NT>(d, pk, srec, srec_off, srec_words, omega, blockIdx.x, pk.hdr_pack, pk.hdr_quad);
+    bwd_narrow2_body<REAL, R, WPB, GEN, BDDMMA_LOOKAHEAD, NT, OV>(d, pk, srec, srec_off, srec_words, omega, blockIdx.x, pk.hdr_pack, pk.hdr_quad);
 }
 
 }  // namespace bddmma

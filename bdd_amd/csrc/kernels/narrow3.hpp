@@ -82,7 +82,8 @@ __device__ __forceinline__ void pot_store_layer(REAL a, REAL b, bool two, rsrc_t
 #ifndef BDDMMA_N3_LOOKAHEAD
 #define BDDMMA_N3_LOOKAHEAD(REAL) (sizeof(REAL) == 8 ? 2 : BDDMMA_LOOKAHEAD)
 #endif
-template <typename REAL, int WPB, bool NT = false, int LA = BDDMMA_LOOKAHEAD>
+// OV: the learned iterations' omega per layer (DevPtrs::omega_lay), prefetched with the layer's {lo, hi} pair (Wr below)
+template <typename REAL, int WPB, bool NT = false, int LA = BDDMMA_LOOKAHEAD, bool OV = false>
 __device__ __forceinline__ void fwd_narrow3_body(const DevPtrs<REAL>& d, const PackDev& pk, const uint32_t* __restrict__ lrec,
                                                  const uint32_t* __restrict__ lrec_off, uint32_t lrec_words, REAL omega, uint32_t block_id)
 {
@@ -131,6 +132,8 @@ __device__ __forceinline__ void fwd_narrow3_body(const DevPtrs<REAL>& d, const P
     u4v rc[2 * D + 1];      // records of hops q .. q + 2D
     P2 tr[D + 1];           // costs-from-terminal of hops q + 2 .. q + D + 2, slots (2 lane, 2 lane + 1): copied to LDS one hop before they are read
     P2 Lr[D + 1];           // {lo, hi} of the lane's layer in hops q .. q + D
+    REAL Wr[OV ? D + 1 : 1];  // OV: omega of the lane's layer in hops q .. q + D
+    const rsrc_t rw = omega_rsrc<OV>(d, l0);
 #pragma unroll
     for (int i = 0; i < 2 * D + 3; ++i) o[i] = 0;
 #pragma unroll
@@ -164,6 +167,10 @@ __device__ __forceinline__ void fwd_narrow3_body(const DevPtrs<REAL>& d, const P
         }
 #pragma unroll
         for (int i = 0; i < D; ++i) hop_load(Lr[i], rs.lohi, (uint32_t)lane * (uint32_t)sizeof(P2), lb[i] * (uint32_t)sizeof(P2));
+        if constexpr (OV) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) hop_load(Wr[i], rw, (uint32_t)lane * S, lb[i] * S);
+        }
         wave_sync();
     } else {
 #pragma unroll
@@ -206,6 +213,7 @@ __device__ __forceinline__ void fwd_narrow3_body(const DevPtrs<REAL>& d, const P
 #ifndef BDDMMA_EXP_NO_HOP_LOADS
         pot_pair_load<REAL, NT>(tr[D], hop_rsrc(Tp, o[D + 2], o[D + 3] - o[D + 2]), 2u * (uint32_t)lane * S, o[D + 2] * S);
         hop_load(Lr[D], rs.lohi, (uint32_t)lane * (uint32_t)sizeof(P2), lb[D] * (uint32_t)sizeof(P2));
+        if constexpr (OV) hop_load(Wr[D], rw, (uint32_t)lane * S, lb[D] * S);
 #endif
         const u4v ra = rc[0];
         const P2 c = Lr[0];
@@ -227,7 +235,7 @@ __device__ __forceinline__ void fwd_narrow3_body(const DevPtrs<REAL>& d, const P
         fb = (flags & LREC_TWO) ? fb : INF;
         const REAL m0 = rmin((fa + c.x) + tla, (fb + c.x) + tlb);
         const REAL m1 = rmin((fa + c.y) + tha, (fb + c.y) + thb);
-        const REAL mm = mm_diff1(m0, m1, omega);
+        const REAL mm = mm_diff1(m0, m1, OV ? Wr[0] : omega);
         P2 nc;
         nc.x = (c.x + min0(mm)) + dd.x;
         nc.y = (c.y + min0_neg(mm)) + dd.y;
@@ -263,6 +271,10 @@ __device__ __forceinline__ void fwd_narrow3_body(const DevPtrs<REAL>& d, const P
             Lr[i] = Lr[i + 1];
             tr[i] = tr[i + 1];
         }
+        if constexpr (OV) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) Wr[i] = Wr[i + 1];
+        }
         ++q;
     };
     while (q + HOP_UNROLL <= qe) {
@@ -282,14 +294,14 @@ __device__ __forceinline__ void fwd_narrow3_body(const DevPtrs<REAL>& d, const P
 #ifndef BDDMMA_N3_WAVES
 #define BDDMMA_N3_WAVES(REAL) (sizeof(REAL) == 4 ? 5 : 4)
 #endif
-template <typename REAL, int WPB, bool NT = false>
+template <typename REAL, int WPB, bool NT = false, bool OV = false>
 __global__ void __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(BDDMMA_N3_WAVES(REAL)))) k_fwd_narrow3(DevPtrs<REAL> d, PackDev pk, const uint32_t* __restrict__ lrec, const uint32_t* __restrict__ lrec_off,
                                                           uint32_t lrec_words, REAL omega)
 {
-    fwd_narrow3_body<REAL, WPB, NT, BDDMMA_N3_LOOKAHEAD(REAL)>(d, pk, lrec, lrec_off, lrec_words, omega, blockIdx.x);
+    fwd_narrow3_body<REAL, WPB, NT, BDDMMA_N3_LOOKAHEAD(REAL), OV>(d, pk, lrec, lrec_off, lrec_words, omega, blockIdx.x);
 }
 
-template <typename REAL, int WPB, bool NT = false, int LA = BDDMMA_LOOKAHEAD>
+template <typename REAL, int WPB, bool NT = false, int LA = BDDMMA_LOOKAHEAD, bool OV = false>
 __device__ __forceinline__ void bwd_narrow3_body(const DevPtrs<REAL>& d, const PackDev& pk, const uint32_t* __restrict__ lrec,
                                                  const uint32_t* __restrict__ lrec_off, uint32_t lrec_words, REAL omega, uint32_t block_id)
 {
@@ -338,6 +350,8 @@ __device__ __forceinline__ void bwd_narrow3_body(const DevPtrs<REAL>& d, const P
     u4v rc[2 * D + 1];
     P2 fr[D + 1];       // costs-from-root of the lane's layer (nodes a, b = a + 1) in hops q .. q-D
     P2 Lr[D + 1];
+    REAL Wr[OV ? D + 1 : 1];  // OV: omega of the lane's layer in hops q .. q-D (see k_fwd_narrow3)
+    const rsrc_t rw = omega_rsrc<OV>(d, l0);
 #pragma unroll
     for (int i = 0; i < 2 * D + 2; ++i) o[i] = 0;
 #pragma unroll
@@ -367,6 +381,7 @@ __device__ __forceinline__ void bwd_narrow3_body(const DevPtrs<REAL>& d, const P
         for (int i = 0; i < D; ++i) {
             ldf(fr[i], rc[i], o[i + 1], o[i] - o[i + 1]);                                                                 // hop q1-1-i
             hop_load(Lr[i], rs.lohi, (uint32_t)lane * (uint32_t)sizeof(P2), lb[i + 1] * (uint32_t)sizeof(P2));
+            if constexpr (OV) hop_load(Wr[i], rw, (uint32_t)lane * S, lb[i + 1] * S);
         }
     } else {
 #pragma unroll
@@ -408,6 +423,7 @@ __device__ __forceinline__ void bwd_narrow3_body(const DevPtrs<REAL>& d, const P
 #ifndef BDDMMA_EXP_NO_HOP_LOADS
         ldf(fr[D], rc[D], o[D + 1], o[D] - o[D + 1]);
         hop_load(Lr[D], rs.lohi, (uint32_t)lane * (uint32_t)sizeof(P2), lb[D + 1] * (uint32_t)sizeof(P2));
+        if constexpr (OV) hop_load(Wr[D], rw, (uint32_t)lane * S, lb[D + 1] * S);
 #endif
         const u4v ra = rc[0];
         const P2 c = Lr[0];
@@ -423,7 +439,7 @@ __device__ __forceinline__ void bwd_narrow3_body(const DevPtrs<REAL>& d, const P
         const REAL fb = (flags & LREC_TWO) ? fr[0].y : INF;
         const REAL m0 = rmin((fa + c.x) + tla, (fb + c.x) + tlb);
         const REAL m1 = rmin((fa + c.y) + tha, (fb + c.y) + thb);
-        const REAL mm = mm_diff1(m0, m1, omega);
+        const REAL mm = mm_diff1(m0, m1, OV ? Wr[0] : omega);
         P2 nc;
         nc.x = (c.x + min0(mm)) + dd.x;
         nc.y = (c.y + min0_neg(mm)) + dd.y;
@@ -464,6 +480,10 @@ __device__ __forceinline__ void bwd_narrow3_body(const DevPtrs<REAL>& d, const P
             Lr[i] = Lr[i + 1];
             fr[i] = fr[i + 1];
         }
+        if constexpr (OV) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) Wr[i] = Wr[i + 1];
+        }
     };
     while (q >= qs + HOP_UNROLL) {
 #pragma unroll
@@ -490,11 +510,11 @@ __device__ __forceinline__ void bwd_narrow3_body(const DevPtrs<REAL>& d, const P
     if (lane == 0) d.lb_partial[pk.lb_base + p] = s;
 }
 
-template <typename REAL, int WPB, bool NT = false>
+template <typename REAL, int WPB, bool NT = false, bool OV = false>
 __global__ void __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(BDDMMA_N3_WAVES(REAL)))) k_bwd_narrow3(DevPtrs<REAL> d, PackDev pk, const uint32_t* __restrict__ lrec, const uint32_t* __restrict__ lrec_off,
                                                           uint32_t lrec_words, REAL omega)
 {
-    bwd_narrow3_body<REAL, WPB, NT, BDDMMA_N3_LOOKAHEAD(REAL)>(d, pk, lrec, lrec_off, lrec_words, omega, blockIdx.x);
+    bwd_narrow3_body<REAL, WPB, NT, BDDMMA_N3_LOOKAHEAD(REAL), OV>(d, pk, lrec, lrec_off, lrec_words, omega, blockIdx.x);
 }
 
 }  // namespace bddmma

@@ -46,7 +46,7 @@ __host__ __device__ inline uint32_t res_wave_bytes(uint32_t real_size, uint32_t 
     return ns * 4u + (ns + 4u) * real_size + nl * 2u * real_size;  // words | potentials + 2 sink entries (+2 pad) | {lo, hi}
 }
 
-template <typename REAL, int R, int WPB>
+template <typename REAL, int R, int WPB, bool OV = false>  // OV: omega per layer (DevPtrs::omega_lay), a global load at the difference
 __global__ void __launch_bounds__(64 * WPB) k_fwd_res(RES_LEADING_ARGS, DevPtrs<REAL> d, PackDev pk, REAL omega)
 {
     const ResDev rd{res_pack_hdr, res_quad_hdr, res_ns, res_nl};
@@ -141,7 +141,9 @@ __global__ void __launch_bounds__(64 * WPB) k_fwd_res(RES_LEADING_ARGS, DevPtrs<
             REAL m0 = act ? (f[r] + c.x) + tl : INF;
             REAL m1 = act ? (f[r] + c.y) + th : INF;
             seg_min2(m0, m1, lane, nw_pos(w), nw_len(w), steps, sM);
-            const REAL mm = mm_diff(m0, m1, omega);
+            REAL om = omega;
+            if constexpr (OV) hop_load(om, omega_rsrc<OV>(d, layer0), ll * (uint32_t)sizeof(REAL), 0u);
+            const REAL mm = mm_diff(m0, m1, om);
             const REAL nlo = (c.x + min0(mm)) + dd.x;
             const REAL nhi = (c.y + min0_neg(mm)) + dd.y;
             const bool head = nw_head(w);
@@ -166,7 +168,7 @@ __global__ void __launch_bounds__(64 * WPB) k_fwd_res(RES_LEADING_ARGS, DevPtrs<
     BDDMMA_STAMP(p, 4);
 }
 
-template <typename REAL, int R, int WPB>
+template <typename REAL, int R, int WPB, bool OV = false>  // OV: omega per layer (DevPtrs::omega_lay), a global load at the difference
 __global__ void __launch_bounds__(64 * WPB) k_bwd_res(RES_LEADING_ARGS, DevPtrs<REAL> d, PackDev pk, REAL omega)
 {
     const ResDev rd{res_pack_hdr, res_quad_hdr, res_ns, res_nl};
@@ -243,7 +245,9 @@ __global__ void __launch_bounds__(64 * WPB) k_bwd_res(RES_LEADING_ARGS, DevPtrs<
             REAL m0 = act ? (fa + c.x) + tl : INF;
             REAL m1 = act ? (fa + c.y) + th : INF;
             seg_min2(m0, m1, lane, nw_pos(w), nw_len(w), steps, sM);
-            const REAL mm = mm_diff(m0, m1, omega);
+            REAL om = omega;
+            if constexpr (OV) hop_load(om, omega_rsrc<OV>(d, layer0), ll * (uint32_t)sizeof(REAL), 0u);
+            const REAL mm = mm_diff(m0, m1, om);
             const REAL nlo = (c.x + min0(mm)) + dd.x;
             const REAL nhi = (c.y + min0_neg(mm)) + dd.y;
             const REAL t = rmin(nhi + th, nlo + tl);
@@ -328,7 +332,7 @@ __device__ __forceinline__ REAL mm_diff1(REAL m0, REAL m1, REAL omega)
 
 #define RES2_ARGS RES_LEADING_ARGS, const uint32_t* __restrict__ res2_rec, const uint32_t* __restrict__ res2_rec_off, uint32_t res2_n_words
 
-template <typename REAL, int WPB>
+template <typename REAL, int WPB, bool OV = false>  // OV: omega per layer (DevPtrs::omega_lay), a global load at the top of the hop
 __global__ void __launch_bounds__(64 * WPB) k_fwd_res2(RES2_ARGS, DevPtrs<REAL> d, PackDev pk, REAL omega)
 {
     constexpr uint32_t S = sizeof(REAL);
@@ -378,17 +382,20 @@ __global__ void __launch_bounds__(64 * WPB) k_fwd_res2(RES2_ARGS, DevPtrs<REAL> 
     BDDMMA_STAMP(p, 2);
     // the pack's slices of the arrays the hop loop stores into: offsets past their ends are dropped
     const rsrc_t rF = make_rsrc(d.F + slot0, nslots), rC = make_rsrc(d.lohi + 2 * (size_t)layer0, 2ull * nlayers);
+    const rsrc_t rw = omega_rsrc<OV>(d, layer0);
     auto hop = [&](const u4v& r) {
         const bool real = r[3] != RES2_PAD;
         const bool two = (r[3] & 0x10000u) != 0;
         const uint32_t ll = r[2] & 0xFFFFu, fs = r[2] >> 16;
+        REAL om = omega;
+        if constexpr (OV) hop_load(om, rw, ll >> 1, 0u);  // ll: the layer's {lo, hi} offset in the pack's slice
         const REAL f = lds_ld<REAL>(dyn_lds, wbF + fs);
         const REAL tl = lds_ld<REAL>(dyn_lds, wb + (r[0] & 0xFFFFu)), th = lds_ld<REAL>(dyn_lds, wb + (r[0] >> 16));
         const P2 c = lds_ld<P2>(dyn_lds, wbC + ll);
         const P2 dd = lds_ld<P2>(dyn_lds, db + ll);
         REAL m0 = (f + c.x) + tl, m1 = (f + c.y) + th;  // padding lanes: +inf
         pair_min_aligned(m0, m1, two);
-        const REAL mm = mm_diff1(m0, m1, omega);
+        const REAL mm = mm_diff1(m0, m1, om);
         P2 nc;
         nc.x = (c.x + min0(mm)) + dd.x;
         nc.y = (c.y + min0_neg(mm)) + dd.y;
@@ -416,7 +423,7 @@ __global__ void __launch_bounds__(64 * WPB) k_fwd_res2(RES2_ARGS, DevPtrs<REAL> 
     BDDMMA_STAMP(p, 4);
 }
 
-template <typename REAL, int WPB>
+template <typename REAL, int WPB, bool OV = false>  // OV: omega per layer (DevPtrs::omega_lay), a global load at the top of the hop
 __global__ void __launch_bounds__(64 * WPB) k_bwd_res2(RES2_ARGS, DevPtrs<REAL> d, PackDev pk, REAL omega)
 {
     constexpr uint32_t S = sizeof(REAL);
@@ -459,17 +466,20 @@ __global__ void __launch_bounds__(64 * WPB) k_bwd_res2(RES2_ARGS, DevPtrs<REAL> 
     if (WPB > 1) __syncthreads(); else wave_sync();
     BDDMMA_STAMP(p, 2);
     const rsrc_t rT = make_rsrc(d.T + slot0, nslots), rC = make_rsrc(d.lohi + 2 * (size_t)layer0, 2ull * nlayers);
+    const rsrc_t rw = omega_rsrc<OV>(d, layer0);
     auto hop = [&](const u4v& r) {
         const bool real = r[3] != RES2_PAD;
         const bool two = (r[3] & 0x10000u) != 0;
         const uint32_t ll = r[2] & 0xFFFFu, fs = r[2] >> 16;
+        REAL om = omega;
+        if constexpr (OV) hop_load(om, rw, ll >> 1, 0u);
         const REAL f = lds_ld<REAL>(dyn_lds, wbF + fs);  // padding lanes: whatever the dummy entry holds; their results go nowhere
         const REAL tl = lds_ld<REAL>(dyn_lds, wb + (r[0] & 0xFFFFu)), th = lds_ld<REAL>(dyn_lds, wb + (r[0] >> 16));
         const P2 c = lds_ld<P2>(dyn_lds, wbC + ll);
         const P2 dd = lds_ld<P2>(dyn_lds, db + ll);
         REAL m0 = (f + c.x) + tl, m1 = (f + c.y) + th;
         pair_min_aligned(m0, m1, two);
-        const REAL mm = mm_diff1(m0, m1, omega);
+        const REAL mm = mm_diff1(m0, m1, om);
         P2 nc;
         nc.x = (c.x + min0(mm)) + dd.x;
         nc.y = (c.y + min0_neg(mm)) + dd.y;

@@ -39,7 +39,7 @@ __device__ __forceinline__ WideLds<REAL> carve_lds(unsigned char* base, uint32_t
 }
 
 // GLOBAL: the frontier arrays of pack p live at scratch + p * wide_lds_bytes(ww) in global memory (huge packs)
-template <typename REAL, int MODE, bool GLOBAL = false>
+template <typename REAL, int MODE, bool GLOBAL = false, bool OV = false>  // OV: omega per layer (DevPtrs::omega_lay), SOLVE only
 __global__ void __launch_bounds__(WIDE_THREADS) k_fwd_wide(DevPtrs<REAL> d, PackDev pk, REAL omega, uint32_t ww, unsigned char* scratch = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -99,7 +99,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) k_fwd_wide(DevPtrs<REAL> d, Pack
             if (MODE == FWD_SOLVE) {
                 const REAL m0 = frontier_load<GLOBAL>(&s.m0[l]), m1 = frontier_load<GLOBAL>(&s.m1[l]);
                 const uint32_t e = d.lpos[lbase + l];
-                const REAL mm = mm_diff(m0, m1, omega);
+                const REAL mm = mm_diff(m0, m1, omega_of<OV>(d, omega, lbase + l));
                 nlo = (nlo + min0(mm)) + d.delta_lay[2 * (size_t)e];
                 nhi = (nhi + min0_neg(mm)) + d.delta_lay[2 * (size_t)e + 1];
                 if (w & WW_HEAD) {
@@ -131,7 +131,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) k_fwd_wide(DevPtrs<REAL> d, Pack
     }
 }
 
-template <typename REAL, int MODE, bool GLOBAL = false>
+template <typename REAL, int MODE, bool GLOBAL = false, bool OV = false>  // OV: omega per layer (DevPtrs::omega_lay), SOLVE only
 __global__ void __launch_bounds__(WIDE_THREADS) k_bwd_wide(DevPtrs<REAL> d, PackDev pk, REAL omega, uint32_t ww, unsigned char* scratch = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -184,7 +184,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) k_bwd_wide(DevPtrs<REAL> d, Pack
             if (MODE == BWD_SOLVE) {
                 const REAL m0 = frontier_load<GLOBAL>(&s.m0[l]), m1 = frontier_load<GLOBAL>(&s.m1[l]);
                 const uint32_t e = d.lpos[lbase + l];
-                const REAL mm = mm_diff(m0, m1, omega);
+                const REAL mm = mm_diff(m0, m1, omega_of<OV>(d, omega, lbase + l));
                 const REAL nlo = (s.lc[l] + min0(mm)) + d.delta_lay[2 * (size_t)e];
                 const REAL nhi = (s.hc[l] + min0_neg(mm)) + d.delta_lay[2 * (size_t)e + 1];
                 t = rmin(nhi + th, nlo + tl);
@@ -197,6 +197,7 @@ __global__ void __launch_bounds__(WIDE_THREADS) k_bwd_wide(DevPtrs<REAL> d, Pack
             } else {
                 t = rmin(th + s.hc[l], tl + s.lc[l]);
                 if (MODE == BWD_MARGINALS && (w & WW_HEAD)) {
+                    // DevPtrs: mm0_out shares its slot with omega_lay, which the OV solve sweeps read: only BWD_MARGINALS sweeps may write it
                     d.mm0_out[lbase + l] = frontier_load<GLOBAL>(&s.m0[l]);
                     d.mm1_out[lbase + l] = frontier_load<GLOBAL>(&s.m1[l]);
                 }
@@ -298,7 +299,7 @@ __device__ __forceinline__ void wide_load_vals(REAL (&v)[NPT], rsrc_t src, uint3
 #ifndef BDDMMA_WIDE_SKIP_BWD
 #define BDDMMA_WIDE_SKIP_BWD(REAL, MODE) false
 #endif
-template <typename REAL, int MODE, int NPT>
+template <typename REAL, int MODE, int NPT, bool OV = false>  // OV: omega per layer (DevPtrs::omega_lay), a buffer load at the difference
 __device__ __forceinline__ void fwd_wide2_body(const DevPtrs<REAL>& d, const PackDev& pk, REAL omega, uint32_t ww, uint32_t p)
 {
     using P2 = typename Pair<REAL>::type;
@@ -440,7 +441,9 @@ __device__ __forceinline__ void fwd_wide2_body(const DevPtrs<REAL>& d, const Pac
             REAL nlo = C0[i].x, nhi = C0[i].y;
             if (MODE == FWD_SOLVE) {
                 const REAL m0 = lds[oMa + l], m1 = lds[oMb + l];
-                const REAL mm = mm_diff(m0, m1, omega);
+                REAL om = omega;
+                if constexpr (OV) bload(om, omega_rsrc<OV>(d, 0u), act ? (lv[0] + l) * (uint32_t)sizeof(REAL) : OOB);
+                const REAL mm = mm_diff(m0, m1, om);
                 nlo = (nlo + min0(mm)) + D0[i].x;
                 nhi = (nhi + min0_neg(mm)) + D0[i].y;
                 const bool head = act && (w & WW_HEAD);
@@ -504,13 +507,13 @@ __device__ __forceinline__ void fwd_wide2_body(const DevPtrs<REAL>& d, const Pac
 #ifndef BDDMMA_WIDE2_WAVES
 #define BDDMMA_WIDE2_WAVES(REAL, MODE, NPT) 4
 #endif
-template <typename REAL, int MODE, int NPT>
+template <typename REAL, int MODE, int NPT, bool OV = false>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(BDDMMA_WIDE2_WAVES(REAL, MODE, NPT)))) k_fwd_wide2(DevPtrs<REAL> d, PackDev pk, REAL omega, uint32_t ww)
 {
-    fwd_wide2_body<REAL, MODE, NPT>(d, pk, omega, ww, blockIdx.x);
+    fwd_wide2_body<REAL, MODE, NPT, OV>(d, pk, omega, ww, blockIdx.x);
 }
 
-template <typename REAL, int MODE, int NPT>
+template <typename REAL, int MODE, int NPT, bool OV = false>
 __device__ __forceinline__ void bwd_wide2_body(const DevPtrs<REAL>& d, const PackDev& pk, REAL omega, uint32_t ww, uint32_t p)
 {
     using P2 = typename Pair<REAL>::type;
@@ -636,7 +639,9 @@ __device__ __forceinline__ void bwd_wide2_body(const DevPtrs<REAL>& d, const Pac
             REAL t;
             if (MODE == BWD_SOLVE) {
                 const REAL m0 = lds[oMa + l], m1 = lds[oMb + l];
-                const REAL mm = mm_diff(m0, m1, omega);
+                REAL om = omega;
+                if constexpr (OV) bload(om, omega_rsrc<OV>(d, 0u), act ? (lb + l) * (uint32_t)sizeof(REAL) : OOB);
+                const REAL mm = mm_diff(m0, m1, om);
                 const REAL nlo = (C0[i].x + min0(mm)) + D0[i].x;
                 const REAL nhi = (C0[i].y + min0_neg(mm)) + D0[i].y;
                 t = rmin(nhi + th[i], nlo + tl[i]);
@@ -649,6 +654,7 @@ __device__ __forceinline__ void bwd_wide2_body(const DevPtrs<REAL>& d, const Pac
             } else {
                 t = rmin(th[i] + C0[i].y, tl[i] + C0[i].x);  // backward_step, bdd_cuda_base.cu:646-667
                 if (MODE == BWD_MARGINALS && head) {
+                    // DevPtrs: mm0_out shares its slot with omega_lay, which the OV solve sweeps read: only BWD_MARGINALS sweeps may write it
                     d.mm0_out[lb + l] = lds[oMa + l];
                     d.mm1_out[lb + l] = lds[oMb + l];
                 }
@@ -688,10 +694,10 @@ __device__ __forceinline__ void bwd_wide2_body(const DevPtrs<REAL>& d, const Pac
     }
 }
 
-template <typename REAL, int MODE, int NPT>
+template <typename REAL, int MODE, int NPT, bool OV = false>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(BDDMMA_WIDE2_WAVES(REAL, MODE, NPT)))) k_bwd_wide2(DevPtrs<REAL> d, PackDev pk, REAL omega, uint32_t ww)
 {
-    bwd_wide2_body<REAL, MODE, NPT>(d, pk, omega, ww, blockIdx.x);
+    bwd_wide2_body<REAL, MODE, NPT, OV>(d, pk, omega, ww, blockIdx.x);
 }
 
 // Instances with narrow AND wide packs: one launch for both.  The first n_wide workgroups sweep one wide pack each (they are the
@@ -710,19 +716,19 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(BDDMM
 #ifndef BDDMMA_MIXED_WAVES
 #define BDDMMA_MIXED_WAVES(REAL, R, NPT) ((NPT) == 4 ? 3 : sizeof(REAL) == 4 ? ((R) == 1 ? 6 : 5) : 4)
 #endif
-template <typename REAL, int R, int WPB, int NPT>
+template <typename REAL, int R, int WPB, int NPT, bool OV = false>
 __global__ void __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(BDDMMA_MIXED_WAVES(REAL, R, NPT)))) k_fwd_mixed(DevPtrs<REAL> d, PackDev pkn, PackDev pkw, REAL omega, uint32_t ww)
 {
     const uint32_t nw8 = (pkw.n_packs + 7u) & ~7u;  // a multiple of 8, so that the narrow workgroups keep their XCD-aware block -> pack map
-    if (blockIdx.x < nw8) fwd_wide2_body<REAL, FWD_SOLVE, NPT>(d, pkw, omega, ww, blockIdx.x);
-    else fwd_narrow_body<REAL, R, FWD_SOLVE, WPB>(d, pkn, omega, blockIdx.x - nw8);
+    if (blockIdx.x < nw8) fwd_wide2_body<REAL, FWD_SOLVE, NPT, OV>(d, pkw, omega, ww, blockIdx.x);
+    else fwd_narrow_body<REAL, R, FWD_SOLVE, WPB, BDDMMA_LOOKAHEAD, true, false, OV>(d, pkn, omega, blockIdx.x - nw8);
 }
-template <typename REAL, int R, int WPB, int NPT>
+template <typename REAL, int R, int WPB, int NPT, bool OV = false>
 __global__ void __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(BDDMMA_MIXED_WAVES(REAL, R, NPT)))) k_bwd_mixed(DevPtrs<REAL> d, PackDev pkn, PackDev pkw, REAL omega, uint32_t ww)
 {
     const uint32_t nw8 = (pkw.n_packs + 7u) & ~7u;
-    if (blockIdx.x < nw8) bwd_wide2_body<REAL, BWD_SOLVE, NPT>(d, pkw, omega, ww, blockIdx.x);
-    else bwd_narrow_body<REAL, R, BWD_SOLVE, WPB>(d, pkn, omega, blockIdx.x - nw8);
+    if (blockIdx.x < nw8) bwd_wide2_body<REAL, BWD_SOLVE, NPT, OV>(d, pkw, omega, ww, blockIdx.x);
+    else bwd_narrow_body<REAL, R, BWD_SOLVE, WPB, BDDMMA_LOOKAHEAD, true, false, OV>(d, pkn, omega, blockIdx.x - nw8);
 }
 
 }  // namespace bddmma

@@ -64,10 +64,12 @@ struct SolverBase {
         return BDDMMA_OK;
     }
     // bdd_cuda_learned_mma::iterations (bdd_cuda_learned_mma.cu:184-270): iterations with per-layer distribution weights, the state
-    // contract of include/bdd_mma.h (bddmma_learned_iterations)
+    // contract of include/bdd_mma.h (bddmma_learned_iterations); omega_vec non-null: one omega per layer in place of the scalar
+    // (bddmma_learned_iterations_omega_vec)
     virtual int learned_iterations(const void* dist_weights, int weights_on_device, uint64_t num_itr, double omega, double improvement_slope,
                                    void* sol_avg, void* lb_first_diff_avg, void* lb_second_diff_avg, uint64_t compute_history_for_itr,
-                                   double history_avg_beta, int outputs_on_device, uint64_t* itr_done) = 0;
+                                   double history_avg_beta, int outputs_on_device, uint64_t* itr_done, const void* omega_vec,
+                                   int omega_vec_on_device) = 0;
     virtual int isotropic_dist_weights(void* out, int on_device) = 0;
     double initial_lb_change = std::numeric_limits<double>::infinity();  // set_initial_lb_change (bdd_cuda_learned_mma.h:111-116): set once
     // number of L-BFGS wrappers attached to this solver (bddmma_lbfgs_create / _destroy); shared so that a wrapper destroyed after its

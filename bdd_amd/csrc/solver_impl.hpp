@@ -73,6 +73,7 @@ struct SolverT final : SolverBase {
     // learned iterations (learned_iterations): the distribution weights in binned entry order, and the history's scratch — allocated on the
     // first call that needs them (dalloc: carved from the arena's rest or a further chunk; not part of the arena's size estimate in init)
     REAL* d_alpha_ent = nullptr;
+    REAL* d_omega_lay = nullptr;   // omega_vec in layer order (the order of d_lohi): what the sweeps' OV instantiation reads
     REAL* d_hist = nullptr;        // last_sol [L], three per-BDD bounds [3 B], the change [B] and the previous change [B]
     REAL* d_hist_out = nullptr;    // device copies of the caller's host outputs: sol_avg [L], lb_first_diff_avg [B], lb_second_diff_avg [B]
     uint16_t* d_bvar = nullptr;
@@ -739,10 +740,18 @@ struct SolverT final : SolverBase {
         return c ? 8 * c * cdiv(n_quads, 8 * c) : 8 * cdiv(n_quads, 8);
     }
 
-    template <int MODE>
+    // OV: the SOLVE sweeps' instantiation that takes omega per layer from d_omega_lay (learned iterations with omega_vec).  Instantiated in
+    // its own translation units (solver_ov.hpp, solver_ov_f32.hip / solver_ov_f64.hip): these three are only declared here.
+    int ov_prepare();                                       // the OV kernels' launch attributes (as init sets the plain ones)
+    int launch_fwd_ov(const REAL* delta_lay, REAL omega);   // launch_fwd<FWD_SOLVE, true>
+    int launch_bwd_ov(const REAL* delta_lay, REAL omega);   // launch_bwd<BWD_SOLVE, true>
+    bool ov_ready = false;
+    template <int MODE, bool OV = false>
     int launch_fwd(const REAL* delta_lay, REAL omega, int kclass)
     {
+        static_assert(!OV || MODE == FWD_SOLVE, "omega per layer: solve sweeps only");
         DevPtrs<REAL> d = ptrs(delta_lay);
+        if (OV) d.omega_lay = d_omega_lay;
         prof_begin(kclass);
         hipStream_t sw = stream;
         if (mixed && mixed_fwd && MODE == FWD_SOLVE) {
@@ -751,9 +760,9 @@ struct SolverT final : SolverBase {
             const dim3 grid(nw8 + narrow_grid(cdiv(nb_.n_packs, wpb))), block(64 * wpb);
 #define LAUNCH_M(R_, W_)                                                                                                                                   \
     switch (mixed_npt) {                                                                                                                                   \
-        case 1: hipLaunchKernelGGL((k_fwd_mixed<REAL, R_, W_, 1>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;            \
-        case 2: hipLaunchKernelGGL((k_fwd_mixed<REAL, R_, W_, 2>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;            \
-        default: hipLaunchKernelGGL((k_fwd_mixed<REAL, R_, W_, 4>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;           \
+        case 1: hipLaunchKernelGGL((k_fwd_mixed<REAL, R_, W_, 1, OV>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;            \
+        case 2: hipLaunchKernelGGL((k_fwd_mixed<REAL, R_, W_, 2, OV>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;            \
+        default: hipLaunchKernelGGL((k_fwd_mixed<REAL, R_, W_, 4, OV>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;           \
     }
 #define LAUNCH_MW(R_) \
     switch (wpb) { case 1: LAUNCH_M(R_, 1) break; case 2: LAUNCH_M(R_, 2) break; case 4: LAUNCH_M(R_, 4) break; default: LAUNCH_M(R_, 8) break; }
@@ -769,9 +778,9 @@ struct SolverT final : SolverBase {
             const PackDev pk = pdev(wb_, nb_.n_packs);
             const dim3 g(wb_.n_packs), b(wide_threads);
             switch (wide_npt) {
-                case 1: hipLaunchKernelGGL((k_fwd_wide2<REAL, MODE, 1>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
-                case 2: hipLaunchKernelGGL((k_fwd_wide2<REAL, MODE, 2>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
-                default: hipLaunchKernelGGL((k_fwd_wide2<REAL, MODE, 4>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
+                case 1: hipLaunchKernelGGL((k_fwd_wide2<REAL, MODE, 1, OV>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
+                case 2: hipLaunchKernelGGL((k_fwd_wide2<REAL, MODE, 2, OV>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
+                default: hipLaunchKernelGGL((k_fwd_wide2<REAL, MODE, 4, OV>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
             }
         }
         if (nb_.n_packs) {
@@ -785,16 +794,16 @@ struct SolverT final : SolverBase {
             const dim3 grid(narrow_grid(cdiv(nb_.n_packs, w))), block(64 * w);
             const ResDev rd{d_pack_hdr, d_quad_hdr, res_ns, res_nl};
 #define LAUNCH_N(R_, W_)                                                                                                      \
-    if (res && use_res2) hipLaunchKernelGGL((k_fwd_res2<REAL, W_>), grid, block, res2_lds, stream, rd.pack_hdr, rd.quad_hdr, res2_ns, res2_nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter, d_res2_rec, d_res2_rec_off, res2_n_words, d, pk, omega); \
-    else if (res) hipLaunchKernelGGL((k_fwd_res<REAL, R_, W_>), grid, block, dyn, stream, rd.pack_hdr, rd.quad_hdr, rd.ns, rd.nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter, d, pk, omega);                           \
-    else if (MODE == FWD_SOLVE && use_narrow3 && n3_nt && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_fwd_narrow3<REAL, (W_ == 8 ? 8 : 4), sizeof(REAL) == 8>), grid, block, dyn, stream, d, pk, d_lrec, d_lrec_off, lrec_words, omega); \
-    else if (MODE == FWD_SOLVE && use_narrow3 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_fwd_narrow3<REAL, (W_ == 8 ? 8 : 4)>), grid, block, dyn, stream, d, pk, d_lrec, d_lrec_off, lrec_words, omega); \
-    else if (MODE == FWD_SOLVE && use_narrow2 && n12_nt && R_ == 2 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_fwd_narrow2<REAL, 2, (W_ == 8 ? 8 : 4), false, sizeof(REAL) == 8>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
-    else if (MODE == FWD_SOLVE && !use_narrow2 && n12_nt && R_ == 2 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_fwd_narrow<REAL, 2, FWD_SOLVE, (W_ == 8 ? 8 : 4), false, true>), grid, block, dyn, stream, d, pk, omega); \
-    else if (MODE == FWD_SOLVE && use_narrow2 && narrow_gen) hipLaunchKernelGGL((k_fwd_narrow2<REAL, R_, W_, true>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
-    else if (MODE == FWD_SOLVE && use_narrow2) hipLaunchKernelGGL((k_fwd_narrow2<REAL, R_, W_, false>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
-    else if (two_node) hipLaunchKernelGGL((k_fwd_narrow<REAL, R_, MODE, W_, MODE != FWD_SOLVE>), grid, block, dyn, stream, d, pk, omega); \
-    else hipLaunchKernelGGL((k_fwd_narrow<REAL, R_, MODE, W_>), grid, block, dyn, stream, d, pk, omega)
+    if (res && use_res2) hipLaunchKernelGGL((k_fwd_res2<REAL, W_, OV>), grid, block, res2_lds, stream, rd.pack_hdr, rd.quad_hdr, res2_ns, res2_nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter, d_res2_rec, d_res2_rec_off, res2_n_words, d, pk, omega); \
+    else if (res) hipLaunchKernelGGL((k_fwd_res<REAL, R_, W_, OV>), grid, block, dyn, stream, rd.pack_hdr, rd.quad_hdr, rd.ns, rd.nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter, d, pk, omega);                           \
+    else if (MODE == FWD_SOLVE && use_narrow3 && n3_nt && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_fwd_narrow3<REAL, (W_ == 8 ? 8 : 4), sizeof(REAL) == 8, OV>), grid, block, dyn, stream, d, pk, d_lrec, d_lrec_off, lrec_words, omega); \
+    else if (MODE == FWD_SOLVE && use_narrow3 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_fwd_narrow3<REAL, (W_ == 8 ? 8 : 4), false, OV>), grid, block, dyn, stream, d, pk, d_lrec, d_lrec_off, lrec_words, omega); \
+    else if (MODE == FWD_SOLVE && use_narrow2 && n12_nt && R_ == 2 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_fwd_narrow2<REAL, 2, (W_ == 8 ? 8 : 4), false, sizeof(REAL) == 8, OV>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
+    else if (MODE == FWD_SOLVE && !use_narrow2 && n12_nt && R_ == 2 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_fwd_narrow<REAL, 2, FWD_SOLVE, (W_ == 8 ? 8 : 4), false, true, OV>), grid, block, dyn, stream, d, pk, omega); \
+    else if (MODE == FWD_SOLVE && use_narrow2 && narrow_gen) hipLaunchKernelGGL((k_fwd_narrow2<REAL, R_, W_, true, false, OV>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
+    else if (MODE == FWD_SOLVE && use_narrow2) hipLaunchKernelGGL((k_fwd_narrow2<REAL, R_, W_, false, false, OV>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
+    else if (two_node) hipLaunchKernelGGL((k_fwd_narrow<REAL, R_, MODE, W_, MODE != FWD_SOLVE, false, OV>), grid, block, dyn, stream, d, pk, omega); \
+    else hipLaunchKernelGGL((k_fwd_narrow<REAL, R_, MODE, W_, true, false, OV>), grid, block, dyn, stream, d, pk, omega)
 #define LAUNCH_W(R_) \
     switch (w) { case 1: LAUNCH_N(R_, 1); break; case 2: LAUNCH_N(R_, 2); break; case 4: LAUNCH_N(R_, 4); break; default: LAUNCH_N(R_, 8); break; }
             switch (pack_width) {
@@ -808,18 +817,20 @@ struct SolverT final : SolverBase {
         }  // !mixed
         if (hb_.n_packs) {
             const PackDev pk = pdev(hb_, nb_.n_packs + wb_.n_packs);
-            hipLaunchKernelGGL((k_fwd_wide<REAL, MODE, true>), dim3(hb_.n_packs), dim3(WIDE_THREADS), 0, stream, d, pk, omega, huge_pack_width, d_huge_scratch);
+            hipLaunchKernelGGL((k_fwd_wide<REAL, MODE, true, OV>), dim3(hb_.n_packs), dim3(WIDE_THREADS), 0, stream, d, pk, omega, huge_pack_width, d_huge_scratch);
         }
         prof_end(kclass);
         HIPCHK(hipGetLastError());
         return BDDMMA_OK;
     }
-    template <int MODE>
+    template <int MODE, bool OV = false>
     int launch_bwd(const REAL* delta_lay, REAL omega, int kclass)
     {
+        static_assert(!OV || MODE == BWD_SOLVE, "omega per layer: solve sweeps only");
         lb_cached = false;
         ++lb_gen;
         DevPtrs<REAL> d = ptrs(delta_lay);
+        if (OV) d.omega_lay = d_omega_lay;
         prof_begin(kclass);
         hipStream_t sw = stream;
         if (mixed && MODE == BWD_SOLVE) {
@@ -828,9 +839,9 @@ struct SolverT final : SolverBase {
             const dim3 grid(nw8 + narrow_grid(cdiv(nb_.n_packs, wpb))), block(64 * wpb);
 #define LAUNCH_M(R_, W_)                                                                                                                                   \
     switch (mixed_npt) {                                                                                                                                   \
-        case 1: hipLaunchKernelGGL((k_bwd_mixed<REAL, R_, W_, 1>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;            \
-        case 2: hipLaunchKernelGGL((k_bwd_mixed<REAL, R_, W_, 2>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;            \
-        default: hipLaunchKernelGGL((k_bwd_mixed<REAL, R_, W_, 4>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;           \
+        case 1: hipLaunchKernelGGL((k_bwd_mixed<REAL, R_, W_, 1, OV>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;            \
+        case 2: hipLaunchKernelGGL((k_bwd_mixed<REAL, R_, W_, 2, OV>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;            \
+        default: hipLaunchKernelGGL((k_bwd_mixed<REAL, R_, W_, 4, OV>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;           \
     }
 #define LAUNCH_MW(R_) \
     switch (wpb) { case 1: LAUNCH_M(R_, 1) break; case 2: LAUNCH_M(R_, 2) break; case 4: LAUNCH_M(R_, 4) break; default: LAUNCH_M(R_, 8) break; }
@@ -846,9 +857,9 @@ struct SolverT final : SolverBase {
             const PackDev pk = pdev(wb_, nb_.n_packs);
             const dim3 g(wb_.n_packs), b(wide_threads);
             switch (wide_npt) {
-                case 1: hipLaunchKernelGGL((k_bwd_wide2<REAL, MODE, 1>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
-                case 2: hipLaunchKernelGGL((k_bwd_wide2<REAL, MODE, 2>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
-                default: hipLaunchKernelGGL((k_bwd_wide2<REAL, MODE, 4>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
+                case 1: hipLaunchKernelGGL((k_bwd_wide2<REAL, MODE, 1, OV>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
+                case 2: hipLaunchKernelGGL((k_bwd_wide2<REAL, MODE, 2, OV>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
+                default: hipLaunchKernelGGL((k_bwd_wide2<REAL, MODE, 4, OV>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
             }
         }
         if (nb_.n_packs) {
@@ -862,16 +873,16 @@ struct SolverT final : SolverBase {
             const dim3 grid(narrow_grid(cdiv(nb_.n_packs, w))), block(64 * w);
             const ResDev rd{d_pack_hdr, d_quad_hdr, res_ns, res_nl};
 #define LAUNCH_N(R_, W_)                                                                                                      \
-    if (res && use_res2) hipLaunchKernelGGL((k_bwd_res2<REAL, W_>), grid, block, res2_lds, stream, rd.pack_hdr, rd.quad_hdr, res2_ns, res2_nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter, d_res2_rec, d_res2_rec_off, res2_n_words, d, pk, omega); \
-    else if (res) hipLaunchKernelGGL((k_bwd_res<REAL, R_, W_>), grid, block, dyn, stream, rd.pack_hdr, rd.quad_hdr, rd.ns, rd.nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter, d, pk, omega);                           \
-    else if (MODE == BWD_SOLVE && use_narrow3 && n3_nt && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_bwd_narrow3<REAL, (W_ == 8 ? 8 : 4), sizeof(REAL) == 8>), grid, block, dyn, stream, d, pk, d_lrec, d_lrec_off, lrec_words, omega); \
-    else if (MODE == BWD_SOLVE && use_narrow3 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_bwd_narrow3<REAL, (W_ == 8 ? 8 : 4)>), grid, block, dyn, stream, d, pk, d_lrec, d_lrec_off, lrec_words, omega); \
-    else if (MODE == BWD_SOLVE && use_narrow2 && n12_nt && R_ == 2 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_bwd_narrow2<REAL, 2, (W_ == 8 ? 8 : 4), false, sizeof(REAL) == 8>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
-    else if (MODE == BWD_SOLVE && !use_narrow2 && n12_nt && R_ == 2 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_bwd_narrow<REAL, 2, BWD_SOLVE, (W_ == 8 ? 8 : 4), false, true>), grid, block, dyn, stream, d, pk, omega); \
-    else if (MODE == BWD_SOLVE && use_narrow2 && narrow_gen) hipLaunchKernelGGL((k_bwd_narrow2<REAL, R_, W_, true>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
-    else if (MODE == BWD_SOLVE && use_narrow2) hipLaunchKernelGGL((k_bwd_narrow2<REAL, R_, W_, false>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
-    else if (two_node) hipLaunchKernelGGL((k_bwd_narrow<REAL, R_, MODE, W_, MODE != BWD_SOLVE>), grid, block, dyn, stream, d, pk, omega); \
-    else hipLaunchKernelGGL((k_bwd_narrow<REAL, R_, MODE, W_>), grid, block, dyn, stream, d, pk, omega)
+    if (res && use_res2) hipLaunchKernelGGL((k_bwd_res2<REAL, W_, OV>), grid, block, res2_lds, stream, rd.pack_hdr, rd.quad_hdr, res2_ns, res2_nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter, d_res2_rec, d_res2_rec_off, res2_n_words, d, pk, omega); \
+    else if (res) hipLaunchKernelGGL((k_bwd_res<REAL, R_, W_, OV>), grid, block, dyn, stream, rd.pack_hdr, rd.quad_hdr, rd.ns, rd.nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter, d, pk, omega);                           \
+    else if (MODE == BWD_SOLVE && use_narrow3 && n3_nt && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_bwd_narrow3<REAL, (W_ == 8 ? 8 : 4), sizeof(REAL) == 8, OV>), grid, block, dyn, stream, d, pk, d_lrec, d_lrec_off, lrec_words, omega); \
+    else if (MODE == BWD_SOLVE && use_narrow3 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_bwd_narrow3<REAL, (W_ == 8 ? 8 : 4), false, OV>), grid, block, dyn, stream, d, pk, d_lrec, d_lrec_off, lrec_words, omega); \
+    else if (MODE == BWD_SOLVE && use_narrow2 && n12_nt && R_ == 2 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_bwd_narrow2<REAL, 2, (W_ == 8 ? 8 : 4), false, sizeof(REAL) == 8, OV>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
+    else if (MODE == BWD_SOLVE && !use_narrow2 && n12_nt && R_ == 2 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_bwd_narrow<REAL, 2, BWD_SOLVE, (W_ == 8 ? 8 : 4), false, true, OV>), grid, block, dyn, stream, d, pk, omega); \
+    else if (MODE == BWD_SOLVE && use_narrow2 && narrow_gen) hipLaunchKernelGGL((k_bwd_narrow2<REAL, R_, W_, true, false, OV>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
+    else if (MODE == BWD_SOLVE && use_narrow2) hipLaunchKernelGGL((k_bwd_narrow2<REAL, R_, W_, false, false, OV>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
+    else if (two_node) hipLaunchKernelGGL((k_bwd_narrow<REAL, R_, MODE, W_, MODE != BWD_SOLVE, false, OV>), grid, block, dyn, stream, d, pk, omega); \
+    else hipLaunchKernelGGL((k_bwd_narrow<REAL, R_, MODE, W_, true, false, OV>), grid, block, dyn, stream, d, pk, omega)
 #define LAUNCH_W(R_) \
     switch (w) { case 1: LAUNCH_N(R_, 1); break; case 2: LAUNCH_N(R_, 2); break; case 4: LAUNCH_N(R_, 4); break; default: LAUNCH_N(R_, 8); break; }
             switch (pack_width) {
@@ -885,7 +896,7 @@ struct SolverT final : SolverBase {
         }  // !mixed
         if (hb_.n_packs) {
             const PackDev pk = pdev(hb_, nb_.n_packs + wb_.n_packs);
-            hipLaunchKernelGGL((k_bwd_wide<REAL, MODE, true>), dim3(hb_.n_packs), dim3(WIDE_THREADS), 0, stream, d, pk, omega, huge_pack_width, d_huge_scratch);
+            hipLaunchKernelGGL((k_bwd_wide<REAL, MODE, true, OV>), dim3(hb_.n_packs), dim3(WIDE_THREADS), 0, stream, d, pk, omega, huge_pack_width, d_huge_scratch);
         }
         prof_end(kclass);
         HIPCHK(hipGetLastError());
@@ -1064,24 +1075,25 @@ struct SolverT final : SolverBase {
         return BDDMMA_OK;
     }
 
-    int mma_forward(REAL omega, const REAL* delta_lay)
+    // ov: omega per layer from d_omega_lay (learned iterations with omega_vec; launch_fwd_ov)
+    int mma_forward(REAL omega, const REAL* delta_lay, bool ov = false)
     {
         int rc;
         if (!bwd_valid && (rc = backward_run())) return rc;  // bdd_cuda_parallel_mma.cu:211-212
-        rc = launch_fwd<FWD_SOLVE>(delta_lay, omega, BDDMMA_K_FORWARD_MM);
+        rc = ov ? launch_fwd_ov(delta_lay, omega) : launch_fwd<FWD_SOLVE>(delta_lay, omega, BDDMMA_K_FORWARD_MM);
         x_layer_valid = false;  // the forward sweep rewrites the deferred values by entry only
         if (rc) return rc;
         fwd_valid = true;
         bwd_valid = false;
         return BDDMMA_OK;
     }
-    int mma_backward(REAL omega, const REAL* delta_lay)
+    int mma_backward(REAL omega, const REAL* delta_lay, bool ov = false)
     {
         if (!fwd_valid) {
             err = "backward_mm requires a valid forward state (call forward_mm first)";  // assert at :304
             return BDDMMA_ERR_STATE;
         }
-        int rc = launch_bwd<BWD_SOLVE>(delta_lay, omega, BDDMMA_K_BACKWARD_MM);
+        int rc = ov ? launch_bwd_ov(delta_lay, omega) : launch_bwd<BWD_SOLVE>(delta_lay, omega, BDDMMA_K_BACKWARD_MM);
         if (rc) return rc;
         x_layer_valid = d_x_layer != nullptr;
         fwd_valid = false;
@@ -1194,8 +1206,35 @@ struct SolverT final : SolverBase {
         HIPCHK(hipStreamSynchronize(stream));
         return BDDMMA_OK;
     }
+    // a REAL[n_layers] argument (dist_weights, omega_vec) -> dst on the device; BDDMMA_ERR_INVALID_ARGUMENT when a value is negative or not
+    // finite (host input: before anything is copied)
+    int load_layer_values(REAL* dst, const void* src, int on_dev, const char* what)
+    {
+        if (!on_dev) {
+            const REAL* h = (const REAL*)src;
+            for (uint64_t l = 0; l < n_layers; ++l)
+                if (!(h[l] >= REAL(0) && h[l] < std::numeric_limits<REAL>::infinity())) {
+                    err = std::string("learned_iterations: ") + what + "[" + std::to_string(l) + "] is negative or not finite";
+                    return BDDMMA_ERR_INVALID_ARGUMENT;
+                }
+        }
+        HIPCHK(hipMemcpyAsync(dst, src, n_layers * sizeof(REAL), on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+        if (on_dev) {
+            HIPCHK(hipMemsetAsync(d_counts, 0, sizeof(uint32_t), stream));
+            hipLaunchKernelGGL((k_count_bad_weights<REAL>), dim3(cdiv(n_layers, 256)), dim3(256), 0, stream, (const REAL*)dst, d_counts, (uint32_t)n_layers);
+            uint32_t bad = 0;
+            HIPCHK(hipMemcpyAsync(&bad, d_counts, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            if (bad) {
+                err = "learned_iterations: " + std::to_string(bad) + " of the " + what + " are negative or not finite";
+                return BDDMMA_ERR_INVALID_ARGUMENT;
+            }
+        }
+        return BDDMMA_OK;
+    }
+    // omega_vec (bddmma_learned_iterations_omega_vec): null = the scalar omega; otherwise REAL[n_layers] in layer order, replacing it
     int learned_iterations(const void* w, int w_dev, uint64_t num_itr, double omega, double slope, void* sol_avg, void* lb1_avg, void* lb2_avg,
-                           uint64_t cfi, double beta_d, int out_dev, uint64_t* itr_done) override
+                           uint64_t cfi, double beta_d, int out_dev, uint64_t* itr_done, const void* omega_vec, int ov_dev) override
     {
         HIPCHK(hipSetDevice(device));
         int rc;
@@ -1211,28 +1250,18 @@ struct SolverT final : SolverBase {
         }
         if (run_stop) { err = "learned_iterations: run_solver is queueing iterations"; return BDDMMA_ERR_STATE; }
         if (!d_alpha_ent && (rc = dalloc(&d_alpha_ent, n_layers))) return rc;
-        // the weights, layer order -> d_tmp0 (checked there) -> binned entry order
-        const size_t lbytes = n_layers * sizeof(REAL);
-        if (!w_dev) {
-            const REAL* h = (const REAL*)w;
-            for (uint64_t l = 0; l < n_layers; ++l)
-                if (!(h[l] >= REAL(0) && h[l] < std::numeric_limits<REAL>::infinity())) {
-                    err = "learned_iterations: dist_weights[" + std::to_string(l) + "] is negative or not finite";
-                    return BDDMMA_ERR_INVALID_ARGUMENT;
-                }
-        }
-        HIPCHK(hipMemcpyAsync(d_tmp0, w, lbytes, w_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
-        if (w_dev) {
-            HIPCHK(hipMemsetAsync(d_counts, 0, sizeof(uint32_t), stream));
-            hipLaunchKernelGGL((k_count_bad_weights<REAL>), dim3(cdiv(n_layers, 256)), dim3(256), 0, stream, (const REAL*)d_tmp0, d_counts, (uint32_t)n_layers);
-            uint32_t bad = 0;
-            HIPCHK(hipMemcpyAsync(&bad, d_counts, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            if (bad) {
-                err = "learned_iterations: " + std::to_string(bad) + " of the dist_weights are negative or not finite";
-                return BDDMMA_ERR_INVALID_ARGUMENT;
+        // omega per layer: layer order is d_lohi's, so it goes to the sweeps as it is (checked before the weights touch anything)
+        const bool ov = omega_vec != nullptr;
+        if (ov) {
+            if (!ov_ready) {
+                if ((rc = ov_prepare())) return rc;
+                ov_ready = true;
             }
+            if (!d_omega_lay && (rc = dalloc(&d_omega_lay, n_layers))) return rc;
+            if ((rc = load_layer_values(d_omega_lay, omega_vec, ov_dev, "omega_vec"))) return rc;
         }
+        // the weights, layer order -> d_tmp0 (checked there) -> binned entry order
+        if ((rc = load_layer_values(d_tmp0, w, w_dev, "dist_weights"))) return rc;
         hipLaunchKernelGGL((k_layers_to_entries<REAL>), dim3(cdiv(n_layers, 256)), dim3(256), 0, stream, (const REAL*)d_tmp0, d_lpos, d_alpha_ent, (uint32_t)n_layers);
         HIPCHK(hipGetLastError());
         // history buffers (:202-209): on the device; the caller's host outputs go through device copies, loaded first (an output the
@@ -1269,9 +1298,9 @@ struct SolverT final : SolverBase {
         for (itr = 0; itr < num_itr; ++itr) {
             prof_active = profiling && (prof_iter++ % prof_stride == 0);
             weighted_exchange();  // forward_iteration_learned_mm_dist: compute_delta of the deferred differences (:68)
-            if ((rc = mma_forward(omega_r, d_delta_lay))) return rc;
+            if ((rc = mma_forward(omega_r, d_delta_lay, ov))) return rc;
             weighted_exchange();  // backward_iteration_learned_mm_dist (:143)
-            if ((rc = mma_backward(omega_r, d_delta_lay))) return rc;
+            if ((rc = mma_backward(omega_r, d_delta_lay, ov))) return rc;
             ++ran;
             if (cfi > 0 && (cfi >= num_itr - itr || converged)) {  // :211-254
                 HIPCHK(hipMemsetAsync(d_sol, 0, n_layers, stream));

@@ -245,13 +245,16 @@ class bdd_hip_parallel_mma:
         return _ptr(x), 0
 
     def learned_iterations(self, dist_weights, num_itr, omega=0.5, improvement_slope=1e-6, sol_avg=None, lb_first_diff_avg=None,
-                           lb_second_diff_avg=None, compute_history_for_itr=0, history_avg_beta=0.9) -> int:
+                           lb_second_diff_avg=None, compute_history_for_itr=0, history_avg_beta=0.9, omega_vec=None) -> int:
         """iterations(dist_weights, ...) of the learned solver: MMA passes that add dist_weights[l] * (sum of the deferred differences
         of the layer's variable) instead of the sum / nr_bdds; returns the number of iterations run.  dist_weights: REAL[nr_layers] in
         the order of get_solver_costs.  With compute_history_for_itr > 0, sol_avg (REAL[nr_layers]), lb_first_diff_avg and
         lb_second_diff_avg (REAL[nr_bdds]) are updated in place (all three on the host or all three on the device).
-        State contract and error codes: include/bdd_mma.h, bddmma_learned_iterations."""
+        omega_vec: REAL[nr_layers] in the same order (numpy array or device tensor), one omega per layer; when given, omega is ignored.
+        State contract and error codes: include/bdd_mma.h, bddmma_learned_iterations(_omega_vec)."""
         w, w_dev = self._learned_buf(dist_weights, self.nr_layers(), "dist_weights")
+        if omega_vec is not None:
+            ov, ov_dev = self._learned_buf(omega_vec, self.nr_layers(), "omega_vec")
         outs = [None, None, None]
         out_dev = 0
         if int(compute_history_for_itr) > 0:
@@ -267,6 +270,11 @@ class bdd_hip_parallel_mma:
             outs = [self._learned_buf(b, n, nm)[0] for b, n, nm in zip(bufs, sizes, names)]
             out_dev = 1 if devs[0] else 0
         done = C.c_uint64()
+        if omega_vec is not None:
+            self._ck(self._L.bddmma_learned_iterations_omega_vec(self._h, w, w_dev, int(num_itr), ov, ov_dev, float(improvement_slope), outs[0],
+                                                                  outs[1], outs[2], int(compute_history_for_itr), float(history_avg_beta),
+                                                                  out_dev, C.byref(done)))
+            return int(done.value)
         self._ck(self._L.bddmma_learned_iterations(self._h, w, w_dev, int(num_itr), float(omega), float(improvement_slope), outs[0], outs[1],
                                                     outs[2], int(compute_history_for_itr), float(history_avg_beta), out_dev, C.byref(done)))
         return int(done.value)

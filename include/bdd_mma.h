@@ -226,7 +226,7 @@ int bddmma_set_delta(bddmma_solver* s, const void* in, int on_device);
 /* ---- learned iterations (bdd_cuda_learned_mma<REAL>, src/bdd_solver/bdd_cuda_learned_mma.cu:9-262; Python binding
  * bdd_cuda_learned_mma_py.cu:300-326,580-600) -----------------------------------------------------------------------------
  * bddmma_learned_iterations = iterations(dist_weights, num_itr, omega, improvement_slope, sol_avg, lb_first_diff_avg, lb_second_diff_avg,
- * compute_history_for_itr, history_avg_beta) (:184-270) without the per-layer omega_vec.  Every pass (forward, then backward) starts from
+ * compute_history_for_itr, history_avg_beta) (:184-270) with a scalar omega (per-layer omega_vec: bddmma_learned_iterations_omega_vec).  Every pass (forward, then backward) starts from
  * the sums of the deferred min-marginal differences per variable, Slo[v] = sum max(-mm, 0), Shi[v] = sum max(mm, 0) — NOT divided by
  * nr_bdds(v) — and adds alpha[l] * S[v(l)] to layer l: lo' = lo + min(mm, 0) + alpha * Slo, hi' = hi + min(-mm, 0) + alpha * Shi (:37,:42).
  * The product is formed in REAL from the sum rounded to REAL.  With alpha[l] = 1 / nr_bdds(v(l)) (bddmma_isotropic_dist_weights) this is
@@ -258,6 +258,18 @@ int bddmma_set_delta(bddmma_solver* s, const void* in, int on_device);
 int bddmma_learned_iterations(bddmma_solver* s, const void* dist_weights, int weights_on_device, uint64_t num_itr, double omega,
                               double improvement_slope, void* sol_avg, void* lb_first_diff_avg, void* lb_second_diff_avg,
                               uint64_t compute_history_for_itr, double history_avg_beta, int outputs_on_device, uint64_t* itr_done);
+/* bddmma_learned_iterations with one omega per layer (omega_vec of iterations(..., omega_vec), bdd_cuda_learned_mma.cu:184-270 with
+ * bdd_cuda_parallel_mma.cu:45-57,117-128): the deferred difference of layer l is omega_vec[l] * (m1 - m0) — one product in REAL, the
+ * scalar call's arithmetic — in place of omega * (m1 - m0).  An omega_vec that holds omega everywhere gives the scalar call's results bit
+ * for bit.
+ *   omega_vec      REAL[nr_layers] in the public layer order (that of dist_weights), host or device (omega_vec_on_device).  Null, or a
+ *                  negative or non-finite value, gives BDDMMA_ERR_INVALID_ARGUMENT and leaves the solver untouched.
+ * Every other argument, the stopping rule, the history, the state contract on exit and the refusal while an L-BFGS wrapper is attached are
+ * those of bddmma_learned_iterations. */
+int bddmma_learned_iterations_omega_vec(bddmma_solver* s, const void* dist_weights, int weights_on_device, uint64_t num_itr, const void* omega_vec,
+                                        int omega_vec_on_device, double improvement_slope, void* sol_avg, void* lb_first_diff_avg,
+                                        void* lb_second_diff_avg, uint64_t compute_history_for_itr, double history_avg_beta, int outputs_on_device,
+                                        uint64_t* itr_done);
 /* REAL[nr_layers], public layer order: 1 / nr_bdds(variable of the layer) in REAL — the weights with which learned iterations are the
  * plain ones (the isotropic alpha of the learned solver's Python side). */
 int bddmma_isotropic_dist_weights(bddmma_solver* s, void* out, int on_device);
