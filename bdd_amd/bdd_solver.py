@@ -206,6 +206,10 @@ class bdd_solver:
         mm = self.solver.min_marginals()
         return mm[: self.ilp.nr_variables()]
 
+    def sum_marginals(self, get_log_probs=True):
+        """[var][bdd] -> (sm_lo, sm_hi) (bdd_cuda_base.cu:1066-1100)"""
+        return self.solver.sum_marginals(get_log_probs)[: self.ilp.nr_variables()]
+
     def min_marginals_with_variable_names(self):
         mm = self.min_marginals()
         return self.ilp.var_names, [m[:, 0].tolist() for m in mm], [m[:, 1].tolist() for m in mm]

@@ -96,6 +96,8 @@ SIGNATURES = {
     "bddmma_set_delta": (_I, [_V, _V, _I]),
     "bddmma_min_marginals": (_I, [_V, _I, _V, _V, _V, _I]),
     "bddmma_min_marginal_diff": (_I, [_V, _V, _I]),
+    "bddmma_sum_marginals": (_I, [_V, _I, _I, _V, _V, _V, _I]),
+    "bddmma_smooth_solution": (_I, [_V, _V, _I]),
     "bddmma_bdds_solution": (_I, [_V, _I, _V, _I]),
     "bddmma_net_solver_costs": (_I, [_V, _V, _I]),
     "bddmma_make_dual_feasible": (_I, [_V, _V, _I]),

@@ -286,6 +286,42 @@ class bdd_hip_parallel_mma {
         check(bddmma_min_marginals(h_, get_sorted ? 1 : 0, var.data(), m0.data(), m1.data(), 0));
         return {std::vector<int>(var.begin(), var.end()), std::move(m0), std::move(m1)};
     }
+    // sum_marginals_cuda(get_sorted, get_log_probs), bdd_cuda_base.h (bdd_cuda_base.cu:788-1025): (primal variable, sm_lo, sm_hi) per dual
+    // variable — log of the summed exp(-cost) over the root-to-top paths through the layer's lo / hi arcs (get_log_probs = false: the sums).
+    // Device buffers of nr_layers() entries each, owned by the caller (dev_var may be null) ...
+    void sum_marginals_cuda(int32_t* dev_var, REAL* dev_sm_lo, REAL* dev_sm_hi, bool get_sorted = true, bool get_log_probs = true)
+    {
+        check(bddmma_sum_marginals(h_, get_sorted ? 1 : 0, get_log_probs ? 1 : 0, dev_var, dev_sm_lo, dev_sm_hi, 1));
+    }
+    // ... or as host vectors
+    std::tuple<std::vector<int>, std::vector<REAL>, std::vector<REAL>> sum_marginals_cuda(bool get_sorted = true, bool get_log_probs = true)
+    {
+        const size_t L = nr_layers();
+        std::vector<int32_t> var(L);
+        std::vector<REAL> m0(L), m1(L);
+        check(bddmma_sum_marginals(h_, get_sorted ? 1 : 0, get_log_probs ? 1 : 0, var.data(), m0.data(), m1.data(), 0));
+        return {std::vector<int>(var.begin(), var.end()), std::move(m0), std::move(m1)};
+    }
+    // sum_marginals(get_log_probs) (bdd_cuda_base.cu:1066-1100): [variable][bdd] -> {sm_lo, sm_hi}, indexed like min_marginals()
+    std::vector<std::vector<std::array<double, 2>>> sum_marginals(bool get_log_probs = true)
+    {
+        const size_t L = nr_layers();
+        std::vector<int32_t> var(L);
+        std::vector<REAL> m0(L), m1(L);
+        check(bddmma_sum_marginals(h_, 1, get_log_probs ? 1 : 0, var.data(), m0.data(), m1.data(), 0));
+        std::vector<std::vector<std::array<double, 2>>> out(nr_variables());
+        for (size_t k = 0; k < L; ++k) out[var[k]].push_back({double(m0[k]), double(m1[k])});
+        return out;
+    }
+    // smooth_solution_cuda(ptr) (bdd_cuda_base.cu:1050-1064): exp(sm_hi) / (exp(sm_lo) + exp(sm_hi)) per layer into a device buffer of
+    // nr_layers() entries, the solver's layer order
+    void smooth_solution_cuda(REAL* dev_smooth_sol) { check(bddmma_smooth_solution(h_, dev_smooth_sol, 1)); }
+    std::vector<REAL> smooth_solution()   // the same as a host vector
+    {
+        std::vector<REAL> out(nr_layers());
+        check(bddmma_smooth_solution(h_, out.data(), 0));
+        return out;
+    }
     // two_dim_variable_array<REAL> bdds_solution() (bdd_cuda_base.cu:1204-1233): [variable][bdd] -> 0 / 1, the argmin path of every BDD,
     // BDDs of a variable in ascending order (primal_variable_sorting_order_, :379-391); nested vectors instead of two_dim_variable_array
     std::vector<std::vector<REAL>> bdds_solution()

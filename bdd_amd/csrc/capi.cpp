@@ -273,6 +273,14 @@ int bddmma_min_marginal_diff(bddmma_solver* s, void* out, int on_device)
 {
     return guarded(s, [&](SolverBase* b) { return out ? b->min_marginal_diff(out, on_device) : BDDMMA_ERR_INVALID_ARGUMENT; });
 }
+int bddmma_sum_marginals(bddmma_solver* s, int sorted, int log_probs, int32_t* var, void* sm0, void* sm1, int on_device)
+{
+    return guarded(s, [&](SolverBase* b) { return (sm0 && sm1) ? b->sum_marginals(sorted, log_probs, var, sm0, sm1, on_device) : BDDMMA_ERR_INVALID_ARGUMENT; });
+}
+int bddmma_smooth_solution(bddmma_solver* s, void* out, int on_device)
+{
+    return guarded(s, [&](SolverBase* b) { return out ? b->smooth_solution(out, on_device) : BDDMMA_ERR_INVALID_ARGUMENT; });
+}
 int bddmma_bdds_solution(bddmma_solver* s, int sorted, char* sol, int on_device)
 {
     return guarded(s, [&](SolverBase* b) { return sol ? b->bdds_solution(sorted, sol, on_device) : BDDMMA_ERR_INVALID_ARGUMENT; });

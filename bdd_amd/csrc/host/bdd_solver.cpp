@@ -259,6 +259,21 @@ std::vector<std::vector<std::array<double, 2>>> bdd_solver::min_marginals()
     return out;
 }
 
+std::vector<std::vector<std::array<double, 2>>> bdd_solver::sum_marginals(bool get_log_probs)
+{
+    const size_t L = bddmma_nr_layers(solver_), V = bddmma_nr_variables(solver_);
+    std::vector<int32_t> var(L);
+    const bool f64 = bddmma_precision(solver_) == BDDMMA_F64;
+    std::vector<double> m0d(f64 ? L : 0), m1d(f64 ? L : 0);
+    std::vector<float> m0f(f64 ? 0 : L), m1f(f64 ? 0 : L);
+    check(bddmma_sum_marginals(solver_, 1, get_log_probs ? 1 : 0, var.data(), f64 ? (void*)m0d.data() : (void*)m0f.data(),
+                               f64 ? (void*)m1d.data() : (void*)m1f.data(), 0));
+    std::vector<std::vector<std::array<double, 2>>> out(V);
+    for (size_t l = 0; l < L; ++l) out[var[l]].push_back({f64 ? m0d[l] : (double)m0f[l], f64 ? m1d[l] : (double)m1f[l]});
+    out.resize(ilp_.nr_variables() ? std::min(V, ilp_.nr_variables()) : V);
+    return out;
+}
+
 // ---------------------------------------------------------------------------------------------- batch farm
 // one layout build per device slot at a time: each gets its share of the host cores (8 slots x 32 builder threads would oversubscribe them)
 // (set per worker thread: the process-wide value, which an application or a second concurrent batch may own, is left alone)

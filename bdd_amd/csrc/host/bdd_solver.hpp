@@ -37,6 +37,7 @@ public:
 
     double lower_bound();                                        // incl. the objective constant
     std::vector<std::vector<std::array<double, 2>>> min_marginals();  // [var][bdd] -> {mm0, mm1}
+    std::vector<std::vector<std::array<double, 2>>> sum_marginals(bool get_log_probs = true);  // [var][bdd] -> {sm_lo, sm_hi} (bdd_cuda_base.cu:1066-1100)
 
     const ilp_input& ilp() const { return ilp_; }
     const bdd_store& bdds() const { return col_; }

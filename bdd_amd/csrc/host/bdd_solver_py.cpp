@@ -156,6 +156,7 @@ PYBIND11_MODULE(bdd_solver_py, m)
         .def("solve", [](py::object self) { self.cast<bdd_solver&>().solve(); return self; })
         .def("lower_bound", &bdd_solver::lower_bound)
         .def("min_marginals", &bdd_solver::min_marginals)   // [var][bdd] -> [mm0, mm1]
+        .def("sum_marginals", &bdd_solver::sum_marginals, py::arg("get_log_probs") = true)   // [var][bdd] -> [sm_lo, sm_hi] (bdd_cuda_base.cu:1066-1100)
         .def("min_marginals_with_variable_names",           // bdd_solver.cpp:516-527: (names, mm0 per variable, mm1 per variable)
              [](bdd_solver& s) {
                  const auto mm = s.min_marginals();

@@ -669,4 +669,30 @@ __global__ void k_ema(REAL* __restrict__ avg, const REAL* __restrict__ cur, REAL
     if (i < n) avg[i] = REAL((double)(beta * avg[i]) + (1.0 - (double)beta) * (double)cur[i]);
 }
 
+// ---- sum-marginals (SolverT::sum_marginals; the sweeps: kernels/summarg.hpp)
+// log sum-marginals -> probabilities (ProcessSumMarginals with get_log_probs = false, bdd_cuda_base.cu:1001-1006); exp(-inf) = 0.  Full-accuracy exp.
+template <typename REAL>
+__global__ void k_exp_pair(REAL* __restrict__ a, REAL* __restrict__ b, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        a[i] = sizeof(REAL) == 4 ? (REAL)expf((float)a[i]) : (REAL)exp((double)a[i]);
+        b[i] = sizeof(REAL) == 4 ? (REAL)expf((float)b[i]) : (REAL)exp((double)b[i]);
+    }
+}
+// ComputeSmoothSolution (bdd_cuda_base.cu:1027-1048): exp(hi - c) / (exp(lo - c) + exp(hi - c)), c = max(lo, hi), of the log sum-marginals.
+// A layer no root-to-top path crosses (both -inf; the reference's -1e30 sentinels give 0.5 there) gives 0.5 here too.
+template <typename REAL>
+__global__ void k_smooth_solution(const REAL* __restrict__ sm_lo, const REAL* __restrict__ sm_hi, REAL* __restrict__ out, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const REAL lo = sm_lo[i], hi = sm_hi[i];
+    const REAL c = lo > hi ? lo : hi;
+    if (!(c > REAL(-__builtin_huge_val()))) { out[i] = REAL(0.5); return; }
+    const REAL e_lo = sizeof(REAL) == 4 ? (REAL)expf((float)(lo - c)) : (REAL)exp((double)(lo - c));
+    const REAL e_hi = sizeof(REAL) == 4 ? (REAL)expf((float)(hi - c)) : (REAL)exp((double)(hi - c));
+    out[i] = e_hi / (e_lo + e_hi);
+}
+
 }  // namespace bddmma

@@ -213,6 +213,12 @@ void visit_layout_arrays(LAYOUT& L, V&& v)
     v(38, L.narrow.hop_root); v(39, L.wide.hop_root);
 }
 constexpr int LAYOUT_ARRAY_IDS = 40;
+// the ids above that code outside the checkpoint names (SolverT::sm_prepare fetches these arrays back from the device)
+enum : int {
+    LAY_NARROW_WORDS = 1, LAY_NARROW_WORD_OFF = 2, LAY_WIDE_WORDS = 3,
+    LAY_NARROW_PACK_HOP_PTR = 10, LAY_NARROW_HOP_NODE_OFF = 11, LAY_WIDE_PACK_HOP_PTR = 14, LAY_WIDE_HOP_NODE_OFF = 15,
+    LAY_HUGE_PACK_HOP_PTR = 18, LAY_HUGE_HOP_NODE_OFF = 19
+};
 
 // Host threads of the layout build: 0 = automatic (BDDMMA_THREADS, else min(cores, 32)).  Processes that build several layouts at once
 // (one per device slot: bddmma_host::solve_batch / bench_set_cover) share the cores through this.

@@ -92,6 +92,10 @@ struct SolverBase {
     virtual int primal_objective_vec(void* out, int on_device) = 0;
     virtual int min_marginals(int sorted, int32_t* var, void* mm0, void* mm1, int on_device) = 0;
     virtual int min_marginal_diff(void* out, int on_device) = 0;
+    // sum_marginals_cuda(get_sorted, get_log_probs) / smooth_solution_cuda (bdd_cuda_base.cu:788-1064): the sweeps in the (log-sum-exp, +)
+    // semiring; state contract in include/bdd_mma.h (bddmma_sum_marginals)
+    virtual int sum_marginals(int sorted, int log_probs, int32_t* var, void* sm0, void* sm1, int on_device) = 0;
+    virtual int smooth_solution(void* out, int on_device) = 0;
     virtual int bdds_solution(int sorted, char* sol, int on_device) = 0;
     virtual int net_solver_costs(void* out, int on_device) = 0;
     virtual int make_dual_feasible(void* g, int on_device) = 0;

@@ -1662,6 +1662,12 @@ struct SolverT final : SolverBase {
         if ((rc = forward_run())) return rc;  // bdd_cuda_base.cu:720
         if ((rc = launch_bwd<BWD_MARGINALS>(nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
         bwd_valid = true;
+        return marginals_out(sorted, var, mm0, mm1, on_device);
+    }
+    // the per-layer pair a marginal sweep left in d_tmp0 / d_tmp1 (min-marginals, sum-marginals) -> the caller, in layer order or gathered
+    // by primal_variable_sorting_order_
+    int marginals_out(int sorted, int32_t* var, void* mm0, void* mm1, int on_device)
+    {
         const hipMemcpyKind k = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
         if (!sorted) {
             if (var) HIPCHK(hipMemcpyAsync(var, d_var, n_layers * sizeof(int32_t), k, stream));
@@ -1689,6 +1695,21 @@ struct SolverT final : SolverBase {
         HIPCHK(e);
         return BDDMMA_OK;
     }
+    // Sum-marginals (kernels/summarg.hpp).  Defined in solver_sm.hpp and instantiated in translation units of their own (solver_sm_f32.hip /
+    // solver_sm_f64.hip), as the OV sweeps are: only declared here.
+    int sm_prepare();       // first call: the parent tables of the forward pull, derived from the node words
+    int sm_launch_fwd();    // one launch per pack family
+    int sm_launch_bwd();
+    int sm_sum_marginals(int sorted, int log_probs, int32_t* var, void* sm0, void* sm1, int on_device);
+    int sm_smooth_solution(void* out, int on_device);
+    bool sm_ready = false;
+    uint32_t *d_sm_nptr = nullptr, *d_sm_npar = nullptr, *d_sm_wptr = nullptr, *d_sm_wpar = nullptr;  // parent tables: narrow words / wide words
+    unsigned char* d_sm_scratch = nullptr;  // huge packs: the sum sweeps' per-pack arrays (sm_lds_bytes of the huge width each)
+    int sum_marginals(int sorted, int log_probs, int32_t* var, void* sm0, void* sm1, int on_device) override
+    {
+        return sm_sum_marginals(sorted, log_probs, var, sm0, sm1, on_device);
+    }
+    int smooth_solution(void* out, int on_device) override { return sm_smooth_solution(out, on_device); }
     int min_marginal_diff(void* out, int on_device) override
     {
         HIPCHK(hipSetDevice(device));
@@ -1988,10 +2009,14 @@ struct SolverT final : SolverBase {
                 case 3: return launch_bwd<BWD_SOLVE>(d_delta_lay, REAL(0.5), BDDMMA_K_OTHER);
                 case 4: return exchange();
                 case 5: launch_bcast(d_delta_c, d_delta_lay_c); return BDDMMA_OK;
+                case 8: return sm_launch_fwd();
+                case 9: return sm_launch_bwd();
                 default: err = "unknown kernel kind"; return BDDMMA_ERR_INVALID_ARGUMENT;
             }
         };
         if (kind == 6 || kind == 7) return time_stream(kind == 7, reps, ms);
+        if ((kind == 8 || kind == 9) && (rc = sm_prepare())) return rc;
+        if (kind == 9 && (rc = sm_launch_fwd())) return rc;  // the backward sum sweep reads the forward one's log-partition values
         if ((rc = once())) return rc;  // warm-up
         HIPCHK(hipEventRecord(ev_t0, stream));
         for (uint64_t i = 0; i < reps; ++i)

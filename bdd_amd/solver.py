@@ -324,6 +324,39 @@ class bdd_hip_parallel_mma:
         return [np.stack([mm0[ptr[v]:ptr[v + 1]], mm1[ptr[v]:ptr[v + 1]]], axis=1).astype(np.float64)
                 for v in range(self.nr_variables())]
 
+    # ---- sum-marginals / smooth solution (bdd_cuda_base.cu:788-1100; state contract: include/bdd_mma.h, bddmma_sum_marginals)
+    def sum_marginals_cuda(self, get_sorted=True, get_log_probs=True, out=None):
+        """(var, sm_lo, sm_hi) per layer: log of the summed exp(-cost) over the root-to-top paths through the layer's lo / hi arcs
+        (get_log_probs=False: the sums themselves); -inf / 0 where no path takes that side.  `out`: (int32, REAL, REAL) device buffers."""
+        n = self.nr_layers()
+        flags = (1 if get_sorted else 0, 1 if get_log_probs else 0)
+        if out is not None:
+            v, m0, m1 = out
+            self._ck(self._L.bddmma_sum_marginals(self._h, *flags, _dev_ptr(v, n, np.int32), _dev_ptr(m0, n, self.value_type),
+                                                  _dev_ptr(m1, n, self.value_type), 1))
+            return out
+        var = np.zeros(n, np.int32)
+        sm0, sm1 = np.zeros(n, self.value_type), np.zeros(n, self.value_type)
+        self._ck(self._L.bddmma_sum_marginals(self._h, *flags, _ptr(var), _ptr(sm0), _ptr(sm1), 0))
+        return var, sm0, sm1
+
+    def sum_marginals(self, get_log_probs=True):
+        """[var][bdd] -> (sm_lo, sm_hi) as a list of (k,2) arrays, like min_marginals() (bdd_cuda_base.cu:1066-1100)."""
+        var, sm0, sm1 = self.sum_marginals_cuda(True, get_log_probs)
+        nb = self.get_num_bdds_per_var()
+        ptr = np.concatenate([[0], np.cumsum(nb)])
+        return [np.stack([sm0[ptr[v]:ptr[v + 1]], sm1[ptr[v]:ptr[v + 1]]], axis=1).astype(np.float64)
+                for v in range(self.nr_variables())]
+
+    def smooth_solution_per_bdd(self, out=None):
+        """exp(sm_hi) / (exp(sm_lo) + exp(sm_hi)) per layer, internal layer order (smooth_solution_cuda, bdd_cuda_base.cu:1050-1064); `out`: device buffer"""
+        if out is not None:
+            self._ck(self._L.bddmma_smooth_solution(self._h, _dev_ptr(out, self.nr_layers(), self.value_type), 1))
+            return out
+        res = np.zeros(self.nr_layers(), self.value_type)
+        self._ck(self._L.bddmma_smooth_solution(self._h, _ptr(res), 0))
+        return res
+
     def min_marginal_diff(self, out=None):
         """mm1 - mm0 per layer (compute_and_set_min_marginal_diff, bdd_cuda_parallel_mma_py.cu:56-72); `out`: device buffer"""
         if out is not None:

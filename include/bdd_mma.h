@@ -281,6 +281,23 @@ int bddmma_min_marginals(bddmma_solver* s, int sorted, int32_t* var, void* mm0, 
 /* mm1 - mm0 per layer, internal layer order, REAL[nr_layers] (compute_and_set_min_marginal_diff of the reference's Python module,
  * src/bdd_solver/bdd_cuda_parallel_mma_py.cu:56-72: min_marginals_cuda(false) followed by thrust::minus into the caller's buffer). */
 int bddmma_min_marginal_diff(bddmma_solver* s, void* out, int on_device);
+/* sum_marginals_cuda(get_sorted, get_log_probs) (bdd_cuda_base<REAL>::sum_marginals_cuda, bdd_cuda_base.cu:788-1025): with the current arc
+ * costs (deferred differences NOT applied, as in the reference), per non-terminal layer l of BDD b
+ *   sm0[l] = log sum over the root -> top paths P of b that take a lo arc in layer l of exp(-cost(P)),   sm1[l]: the same with a hi arc,
+ * computed in the log domain throughout (costs of a few hundred are fine in float).  log_probs = 0: exp of both.  A side no such path
+ * takes is -inf (probability 0); the reference's -1e30 sentinel ends as about -1e30 there.  var int32[nr_layers] (may be NULL), sm0 / sm1
+ * REAL[nr_layers] (NULL: BDDMMA_ERR_INVALID_ARGUMENT, solver untouched); orders and on_device as bddmma_min_marginals.
+ * One forward and one backward launch per pack family (csrc/kernels/summarg.hpp); every sum in a fixed order: repeated calls agree bit for bit.
+ * State contract: the call overwrites the stored costs from root and to terminal with log-partition values, so it ends with both sweep
+ * states invalid and the cached lower bound dropped (the reference flushes both, :1008-1011) — the next entry point that needs them
+ * recomputes them from the costs.  Arc costs, deferred differences, delta and therefore the result of every other entry point called
+ * afterwards are unchanged, also with an L-BFGS wrapper attached and between two bddmma_learned_iterations calls. */
+int bddmma_sum_marginals(bddmma_solver* s, int sorted, int log_probs, int32_t* var, void* sm0, void* sm1, int on_device);
+/* smooth_solution_cuda (bdd_cuda_base<REAL>::smooth_solution_cuda, bdd_cuda_base.cu:1027-1064; smooth_solution_per_bdd of the learned
+ * solver): out[l] = exp(sm1) / (exp(sm0) + exp(sm1)) of the log sum-marginals, evaluated as ComputeSmoothSolution does (both shifted by
+ * their maximum); REAL[nr_layers] in internal layer order (the reference also writes 0 for terminal layers, which are not stored here).
+ * 0.5 where no path crosses the layer.  NULL: BDDMMA_ERR_INVALID_ARGUMENT, solver untouched.  State contract: bddmma_sum_marginals. */
+int bddmma_smooth_solution(bddmma_solver* s, void* out, int on_device);
 /* bdds_solution_vec() (bdd_cuda_base.cu:1139-1202): char[nr_layers] argmin path per BDD, internal
  * layer order (sorted = 0) or (variable,bdd) order (sorted = 1, as bdds_solution(), :1204-1233). */
 int bddmma_bdds_solution(bddmma_solver* s, int sorted, char* sol, int on_device);
@@ -385,7 +402,8 @@ int bddmma_get_profile(bddmma_solver* s, bddmma_profile* out);  /* synchronises 
 int bddmma_time_iterations(bddmma_solver* s, double omega, uint64_t n, double* ms);
 /* Time `reps` back-to-back launches of one kernel class with hipEvents on the handle's stream
  * (kernel-level benchmarking; leaves the sweep state invalid).  kind: 0 forward_run sweep, 1 backward_run
- * sweep, 2 forward_mm sweep, 3 backward_mm sweep, 4 exchange reduce, 5 exchange broadcast, 6 STREAM triad
+ * sweep, 2 forward_mm sweep, 3 backward_mm sweep, 4 exchange reduce, 5 exchange broadcast, 8 / 9 forward / backward sum-marginal
+ * sweep (bddmma_sum_marginals), 6 STREAM triad
  * a = b + s*c over three temporary arrays of BDDMMA_TRIAD_BYTES each (3 * BDDMMA_TRIAD_BYTES of HBM traffic
  * per launch), 7 STREAM copy a = b (2 * BDDMMA_TRIAD_BYTES per launch): the measured bandwidth ceilings of the
  * box the roofline is quoted next to. */
