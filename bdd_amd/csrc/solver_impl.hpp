@@ -16,6 +16,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include "../../include/bdd_mma.h"
 #include "kernels.hpp"
@@ -47,6 +48,15 @@ static inline void cpu_relax()
     } while (0)
 
 static inline uint32_t cdiv(uint64_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
+
+// A run-time value as a compile-time constant: f(std::integral_constant<int, V>) for the candidate V that equals v, for the LAST candidate
+// where none does (pack_width 64 / 128 / anything else, wpb 1 / 2 / 4 / anything else, ...: the kernels' instantiations).
+template <int V0, int... Vs, class F>
+decltype(auto) pick(uint32_t v, F&& f)
+{
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+    else return v == (uint32_t)V0 ? f(std::integral_constant<int, V0>{}) : pick<Vs...>(v, static_cast<F&&>(f));
+}
 
 // ---------------------------------------------------------------------------------------------
 // accumulator type of the exchange kernel's LDS tile (kernels.hpp: k_exchange_reduce); experiments: -DBDDMMA_EX_ACC=REAL
@@ -399,30 +409,12 @@ struct SolverT final : SolverBase {
         exch_lds = vars_per_bin * 2 * (uint32_t)sizeof(double);  // accumulators are double for both precisions
         // LDS of a narrow solve workgroup: the dynamic staging area + the kernel's static arrays (frontier F x2 and T per wave, the hop
         // offset windows) — k_fwd_narrow is the larger of the two.  Above the 64 KiB a launch gets by default the kernels need the
-        // attribute (pack_width 256, double, 4 waves per block is ~67 KiB); above what a CU has the options are refused here,
-        // not at the first sweep.
+        // attribute (pack_width 256, double, 4 waves per block is ~67 KiB; raise_lds_limits at the end of init); above what a
+        // CU has the options are refused here, not at the first sweep.
         const uint32_t narrow_static = L.ex.waves_per_block * (3 * (pack_width + 2) * (uint32_t)sizeof(REAL) + 2 * 64 * 4 + 2) + seg_bytes(L.ex.waves_per_block);
         if (exch_lds > lds_cu - 1024 || stage_lds + narrow_static > lds_cu - 1024) {
             err = "vars_per_bin / stage_cap / waves_per_block need more LDS than a CU has (" + std::to_string(stage_lds + narrow_static) + " B per sweep workgroup)";
             return BDDMMA_ERR_INVALID_ARGUMENT;
-        }
-        if (stage_lds + narrow_static > 64 * 1024) {
-#define SET_N1(K_) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&K_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(stage_lds + seg_bytes(L.ex.waves_per_block))));
-#define SET_N(R_, W_) SET_N1((k_fwd_narrow<REAL, R_, FWD_SOLVE, W_>)) SET_N1((k_bwd_narrow<REAL, R_, BWD_SOLVE, W_>)) SET_N1((k_fwd_narrow<REAL, R_, FWD_SOLVE, W_, false>)) SET_N1((k_bwd_narrow<REAL, R_, BWD_SOLVE, W_, false>))
-#define SET_N_W(R_) \
-    switch (L.ex.waves_per_block) { case 1: SET_N(R_, 1) break; case 2: SET_N(R_, 2) break; case 4: SET_N(R_, 4) break; default: SET_N(R_, 8) break; }
-            switch (pack_width) {
-                case 64: SET_N_W(1) break;
-                case 128: SET_N_W(2) break;
-                default: SET_N_W(4) break;
-            }
-#undef SET_N_W
-#undef SET_N
-            if (pack_width == 128) {  // the non-temporal instantiations (n12_nt)
-                if (L.ex.waves_per_block == 4) { SET_N1((k_fwd_narrow<REAL, 2, FWD_SOLVE, 4, false, true>)) SET_N1((k_bwd_narrow<REAL, 2, BWD_SOLVE, 4, false, true>)) }
-                if (L.ex.waves_per_block == 8) { SET_N1((k_fwd_narrow<REAL, 2, FWD_SOLVE, 8, false, true>)) SET_N1((k_bwd_narrow<REAL, 2, BWD_SOLVE, 8, false, true>)) }
-            }
-#undef SET_N1
         }
         if ((rc = dalloc(&d_tmp0, n_layers))) return rc;
         if ((rc = dalloc(&d_tmp1, n_layers))) return rc;
@@ -442,11 +434,6 @@ struct SolverT final : SolverBase {
         HIPCHK(hipMemsetAsync(d_mm_binned, 0, n_layers * sizeof(REAL), stream));  // bdd_cuda_base.cu:45
         for (REAL* p : {d_delta_var, d_delta_c}) HIPCHK(hipMemsetAsync(p, 0, 2 * n_vars * sizeof(REAL), stream));
         for (REAL* p : {d_delta_lay, d_delta_lay_c}) HIPCHK(hipMemsetAsync(p, 0, 2 * n_layers * sizeof(REAL), stream));
-#define SET_DYN(K, BYTES) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES)))
-        SET_DYN((k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_ITER>), exch_lds);
-        SET_DYN((k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_RAW>), exch_lds);
-        SET_DYN((k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_ITER, EX_THREADS, EX_UNROLL, EX_NPT, true>), exch_lds);  // run_plain()'s instantiation
-        SET_DYN((k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_ITER, EX_THREADS, EX_UNROLL, EX_NPT, false, true>), exch_lds);  // learned_iterations()'s
         opts_variant = opts ? opts->variant_flags : 0u;
         mixed_fwd = (opts_variant & 2u) == 0;
         // measured in double: 7.1 M nodes (490 MB resident) lose 12 % with non-temporal potentials, 10.5 M (720 MB) gain 4 %
@@ -473,18 +460,9 @@ struct SolverT final : SolverBase {
                     if ((rc = upload(&d_seg_thr, SE.thr))) return rc;
                     use_seg = true;
                     seg_groups = SE.max_groups;
-#define SET_SEG_G(T_, G_)                                             \
-    SET_DYN((k_exchange_seg<REAL, T_, G_, false>), seg_lds);          \
-    SET_DYN((k_exchange_seg<REAL, T_, G_, true>), seg_lds);           \
-    SET_DYN((k_exchange_seg<REAL, T_, G_, false, true>), seg_lds)   /* learned_iterations()'s */
-#define SET_SEG(T_) if (seg_groups <= 2) { SET_SEG_G(T_, 2); } else { SET_SEG_G(T_, 4); }
-                    if (exch_small) { SET_SEG(EXS_THREADS) } else if (exch_medium) { SET_SEG(EXM_THREADS) } else { SET_SEG(EX_THREADS) }
-#undef SET_SEG
-#undef SET_SEG_G
                 }
             }
         }
-#undef SET_DYN
         // resident sweeps: chosen when every narrow pack fits its wave's LDS slice and the instance is small enough that the streaming
         // kernels are latency-bound (few waves per SIMD); resident_sweeps = 1 turns them off, = 2 forces them on
         if ((rc = upload(&d_pack_hdr, L.res.pack_hdr, 34))) return rc;
@@ -525,27 +503,8 @@ struct SolverT final : SolverBase {
                         if ((rc = upload(&d_res2_rec_off, R2.rec_off))) return rc;
                         res2_n_words = (uint32_t)R2.rec.size();
                         use_res2 = use_res = true;
-#define SET_RES2(W_)                                                                                                                            \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwd_res2<REAL, W_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)res2_lds)); \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bwd_res2<REAL, W_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)res2_lds));
-                        switch (wpb) { case 1: SET_RES2(1) break; case 2: SET_RES2(2) break; case 4: SET_RES2(4) break; default: SET_RES2(8) break; }
-#undef SET_RES2
                     }
                 }
-            }
-            if (use_res && !use_res2) {
-#define SET_RES(R_, W_) \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwd_res<REAL, R_, W_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(res_lds + seg_bytes(wpb)))); \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bwd_res<REAL, R_, W_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(res_lds + seg_bytes(wpb))));
-#define SET_RES_W(R_) \
-    switch (wpb) { case 1: SET_RES(R_, 1) break; case 2: SET_RES(R_, 2) break; case 4: SET_RES(R_, 4) break; default: SET_RES(R_, 8) break; }
-                switch (pack_width) {
-                    case 64: SET_RES_W(1) break;
-                    case 128: SET_RES_W(2) break;
-                    default: SET_RES_W(4) break;
-                }
-#undef SET_RES_W
-#undef SET_RES
             }
         }
         // streaming solve sweeps, second generation (kernels.hpp: k_fwd_narrow2 / k_bwd_narrow2): every narrow pack; the general form (GEN) where
@@ -596,14 +555,6 @@ struct SolverT final : SolverBase {
                 // double, footprint beyond the Infinity Cache's reach (the condition of the non-temporal stores): the instantiation that LOADS what a
                 // sweep reads once — potentials, staging tables — non-temporally (profiles/r05_placement.txt #7: 10.5 M nodes +3.5 %)
                 n3_nt = sizeof(REAL) == 8 && nt_potentials != 0;
-#define SET_N3(W_, NT_)                                                                                                                              \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fwd_narrow3<REAL, W_, NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_lds)); \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bwd_narrow3<REAL, W_, NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage_lds));
-                if (L.ex.waves_per_block == 4) { SET_N3(4, false) } else { SET_N3(8, false) }
-                if constexpr (sizeof(REAL) == 8) {
-                    if (L.ex.waves_per_block == 4) { SET_N3(4, true) } else { SET_N3(8, true) }
-                }
-#undef SET_N3
             }
         }
         // First / second (double only) generation where the third stops — beyond 16 M slots, i.e. beyond the Infinity Cache's reach: the same
@@ -633,13 +584,6 @@ struct SolverT final : SolverBase {
                 err = "wide_pack_width " + std::to_string(wide_pack_width) + " needs " + std::to_string(wide_lds) + " B of LDS (> 160 KiB)";
                 return BDDMMA_ERR_UNSUPPORTED;
             }
-#define SET_LDS(K) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_lds))
-#define SET_LDS_N(N_) \
-    SET_LDS((k_fwd_wide2<REAL, FWD_PLAIN, N_>)); SET_LDS((k_fwd_wide2<REAL, FWD_SOLVE, N_>)); SET_LDS((k_fwd_wide2<REAL, FWD_SOLUTION, N_>)); \
-    SET_LDS((k_bwd_wide2<REAL, BWD_PLAIN, N_>)); SET_LDS((k_bwd_wide2<REAL, BWD_SOLVE, N_>)); SET_LDS((k_bwd_wide2<REAL, BWD_MARGINALS, N_>));
-            if (wide_npt == 1) { SET_LDS_N(1) } else if (wide_npt == 2) { SET_LDS_N(2) } else { SET_LDS_N(4) }
-#undef SET_LDS_N
-#undef SET_LDS
         }
         // one launch for narrow + wide solve sweeps when the wide packs fit the narrow workgroup size (<= 4 nodes per thread) and their
         // LDS frontier does not cost the narrow workgroups their occupancy
@@ -687,15 +631,12 @@ struct SolverT final : SolverBase {
                 small.var_ptr = d_var_ptr; small.var_lds = d_small_lds; small.var_ent = d_vpos;
                 small_lds = bytes;
                 small_nw = np <= 1 ? 1 : np <= 2 ? 2 : np <= 4 ? 4 : np <= 8 ? 8 : 16;
-#define SET_SMALL(NW_)                                                                                                                                  \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_iterate_small<REAL, NW_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds)); \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_iterate_small<REAL, NW_, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)small_lds));
-                switch (small_nw) { case 1: SET_SMALL(1) break; case 2: SET_SMALL(2) break; case 4: SET_SMALL(4) break; case 8: SET_SMALL(8) break; default: SET_SMALL(16) break; }
-#undef SET_SMALL
                 small_ok = true;
                 fused_small = true;
             }
         }
+        resolve_kernels();
+        if ((rc = raise_lds_limits(kern))) return rc;
         solve_sweep_kind = !nb_.n_packs ? BDDMMA_SWEEPS_NONE : mixed ? BDDMMA_SWEEPS_MIXED : (use_res && use_res2) ? BDDMMA_SWEEPS_RESIDENT2 : use_res ? BDDMMA_SWEEPS_RESIDENT1
                            : use_narrow3 ? BDDMMA_SWEEPS_STREAMING3 : use_narrow2 ? BDDMMA_SWEEPS_STREAMING2 : BDDMMA_SWEEPS_STREAMING1;
         HIPCHK(hipStreamSynchronize(stream));
@@ -740,168 +681,225 @@ struct SolverT final : SolverBase {
         return c ? 8 * c * cdiv(n_quads, 8 * c) : 8 * cdiv(n_quads, 8);
     }
 
-    // OV: the SOLVE sweeps' instantiation that takes omega per layer from d_omega_lay (learned iterations with omega_vec).  Instantiated in
-    // its own translation units (solver_ov.hpp, solver_ov_f32.hip / solver_ov_f64.hip): these three are only declared here.
-    int ov_prepare();                                       // the OV kernels' launch attributes (as init sets the plain ones)
-    int launch_fwd_ov(const REAL* delta_lay, REAL omega);   // launch_fwd<FWD_SOLVE, true>
-    int launch_bwd_ov(const REAL* delta_lay, REAL omega);   // launch_bwd<BWD_SOLVE, true>
+    // ---------------------------------------------------------------------------- the kernel table
+    // Which instantiation of a sweep, exchange or projection kernel this solver launches is a function of what init() has fixed
+    // (pack_width, wpb, use_res, narrow_gen, ...).  resolve_kernels() evaluates that function once, at the end of init(), into typed
+    // function pointers together with the dynamic LDS each is launched with; the launches below take both from the table, and
+    // raise_lds_limits() sets the launch attribute of exactly the table's entries: what is prepared and what is launched is one object.
+    // (A kernel family's parameter list depends on REAL only, so one pointer type serves all of its instantiations.)
+    template <typename FN>
+    struct Kern { FN fn = nullptr; uint32_t lds = 0; };
+    using NarrowFn = void (*)(DevPtrs<REAL>, PackDev, REAL);
+    using RecFn = void (*)(DevPtrs<REAL>, PackDev, const uint32_t*, const uint32_t*, uint32_t, REAL);  // second / third generation: + records
+    using ResFn = void (*)(const uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t*, uint32_t, DevPtrs<REAL>, PackDev, REAL);
+    using Res2Fn = void (*)(const uint32_t*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t*, uint32_t, const uint32_t*,
+                            const uint32_t*, uint32_t, DevPtrs<REAL>, PackDev, REAL);
+    using WideFn = void (*)(DevPtrs<REAL>, PackDev, REAL, uint32_t);
+    using HugeFn = void (*)(DevPtrs<REAL>, PackDev, REAL, uint32_t, unsigned char*);
+    using MixedFn = void (*)(DevPtrs<REAL>, PackDev, PackDev, REAL, uint32_t);
+    using ExFn = void (*)(const REAL*, const uint32_t*, const uint16_t*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, const int32_t*, REAL*, REAL*,
+                          RunStep, const REAL*);
+    using SegFn = void (*)(const REAL*, const uint4*, const uint32_t*, uint32_t, const uint4*, const uint2*, uint32_t, uint32_t, REAL*, RunStep, const REAL*);
+    using ProjFn = void (*)(REAL*, const uint32_t*, const uint16_t*, const int32_t*, uint32_t, uint32_t, uint32_t);
+    using SmallFn = void (*)(SmallDev, DevPtrs<REAL>, PackDev, REAL, uint32_t, RunStep);
+    using TransFn = void (*)(const REAL*, REAL*, PackDev, const uint32_t*, const uint16_t*, uint32_t, uint32_t, REAL*, REAL);
+    using LincombFn = void (*)(LinComb, REAL*, PackDev, const uint32_t*, const uint16_t*, uint32_t, uint32_t);
+    // one sweep (a direction and a MODE) over every pack family
+    struct Sweep {
+        // narrow packs: the one kernel the rules chose (resident 2 / resident 1 / on records / first generation), `w` packs per workgroup
+        Res2Fn res2 = nullptr;
+        ResFn res = nullptr;
+        RecFn rec = nullptr;
+        NarrowFn narrow = nullptr;
+        uint32_t narrow_lds = 0, w = 1, seg_off = 0;    // seg_off: PackDev::seg_off, where the seg_min2 scratch starts
+        const uint32_t *rec_tab = nullptr, *rec_off = nullptr;  // rec's records: the third generation's (d_lrec) or the second's (d_srec)
+        uint32_t rec_words = 0;
+        Kern<WideFn> wide;
+        Kern<MixedFn> mixed;  // SOLVE, where init() admitted `mixed`: narrow + wide in one launch
+        HugeFn huge = nullptr;
+        const void* narrow_fn() const { return res2 ? (const void*)res2 : res ? (const void*)res : rec ? (const void*)rec : (const void*)narrow; }
+    };
+    struct Kernels {
+        Sweep sweep[2][3];             // [backward][MODE]
+        uint32_t ex_threads = 0;       // workgroup size of the binned exchange and of k_project_entries
+        Kern<ExFn> ex[2], ex_w, ex_raw;  // LDS-atomic exchange: [RUN], WEIGHTED, and the raw sums of the explicit API
+        Kern<SegFn> seg[2], seg_w;     // scheduled exchange (use_seg): [RUN], WEIGHTED
+        Kern<ProjFn> project;
+        Kern<SmallFn> small;           // small_ok: whole iterations in one launch
+        Kern<TransFn> transpose[2];    // staged projection: [TO_LAYERS]
+        Kern<LincombFn> lincomb[2];    // [the five-vector form]
+    } kern;
+    Sweep ov_sweep[2];  // [backward]: the SOLVE sweeps with omega per layer (OV), filled by ov_prepare()
+    // OV: the instantiation that takes omega per layer from d_omega_lay (learned iterations with omega_vec), SOLVE only.  The <true> form is
+    // named in solver_ov.hpp alone, so that those kernels compile in translation units of their own (solver_ov_f32.hip / solver_ov_f64.hip).
+    template <int MODE, bool OV>
+    Sweep resolve_sweep(bool bwd) const
+    {
+        constexpr bool SOLVE = MODE == FWD_SOLVE;  // == BWD_SOLVE
+        static_assert(!OV || SOLVE, "omega per layer: solve sweeps only");
+        Sweep s;
+        if (hb_.n_packs) s.huge = bwd ? &k_bwd_wide<REAL, MODE, true, OV> : &k_fwd_wide<REAL, MODE, true, OV>;
+        if (wb_.n_packs)
+            s.wide = {pick<1, 2, 4>(wide_npt, [&](auto N) -> WideFn { return bwd ? &k_bwd_wide2<REAL, MODE, N.value, OV> : &k_fwd_wide2<REAL, MODE, N.value, OV>; }),
+                      wide_lds};
+        if (!nb_.n_packs) return s;
+        if constexpr (!SOLVE) {
+            // the other modes stage nothing: one pack per workgroup, the SEG = true form
+            s.narrow = pick<64, 128, 256>(pack_width, [&](auto PW) -> NarrowFn {
+                constexpr int R = PW.value / 64;
+                return bwd ? &k_bwd_narrow<REAL, R, MODE, 1, true, false, false> : &k_fwd_narrow<REAL, R, MODE, 1, true, false, false>;
+            });
+            s.narrow_lds = seg_bytes(1);
+        } else {
+            // `wpb` packs per workgroup with cooperative staging.  Precedence, top to bottom: resident 2, resident 1, third generation (NT), second
+            // generation NT, first generation NT (both: packs of 128 slots, 4 / 8 per workgroup), second generation general form, second
+            // generation, first generation two-node form (SEG = false), first generation.
+            s.w = wpb;
+            s.seg_off = use_res ? res_lds : stage_lds;
+            s.narrow_lds = (use_res && use_res2) ? res2_lds : s.seg_off + seg_bytes(wpb);
+            pick<64, 128, 256>(pack_width, [&](auto PW) {
+                pick<1, 2, 4, 8>(wpb, [&](auto W_) {
+                    constexpr int R = PW.value / 64, W = W_.value, W48 = W == 8 ? 8 : 4;  // W48: the instantiations that exist for 4 / 8 only
+                    const bool w48 = W == 4 || W == 8;
+                    if (use_res && use_res2) s.res2 = bwd ? &k_bwd_res2<REAL, W, OV> : &k_fwd_res2<REAL, W, OV>;
+                    else if (use_res) s.res = bwd ? &k_bwd_res<REAL, R, W, OV> : &k_fwd_res<REAL, R, W, OV>;
+                    else if (use_narrow3 && w48) {
+                        s.rec = bwd ? &k_bwd_narrow3<REAL, W48, false, OV> : &k_fwd_narrow3<REAL, W48, false, OV>;
+                        if constexpr (sizeof(REAL) == 8)
+                            if (n3_nt) s.rec = bwd ? &k_bwd_narrow3<REAL, W48, true, OV> : &k_fwd_narrow3<REAL, W48, true, OV>;
+                        s.rec_tab = d_lrec; s.rec_off = d_lrec_off; s.rec_words = lrec_words;
+                    } else if (use_narrow2) {
+                        if (n12_nt && R == 2 && w48) s.rec = bwd ? &k_bwd_narrow2<REAL, 2, W48, false, sizeof(REAL) == 8, OV> : &k_fwd_narrow2<REAL, 2, W48, false, sizeof(REAL) == 8, OV>;
+                        else if (narrow_gen) s.rec = bwd ? &k_bwd_narrow2<REAL, R, W, true, false, OV> : &k_fwd_narrow2<REAL, R, W, true, false, OV>;
+                        else s.rec = bwd ? &k_bwd_narrow2<REAL, R, W, false, false, OV> : &k_fwd_narrow2<REAL, R, W, false, false, OV>;
+                        s.rec_tab = d_srec; s.rec_off = d_srec_off; s.rec_words = srec_words;
+                    } else if (n12_nt && R == 2 && w48) s.narrow = bwd ? &k_bwd_narrow<REAL, 2, MODE, W48, false, true, OV> : &k_fwd_narrow<REAL, 2, MODE, W48, false, true, OV>;
+                    else if (!narrow_seg) s.narrow = bwd ? &k_bwd_narrow<REAL, R, MODE, W, false, false, OV> : &k_fwd_narrow<REAL, R, MODE, W, false, false, OV>;
+                    else s.narrow = bwd ? &k_bwd_narrow<REAL, R, MODE, W, true, false, OV> : &k_fwd_narrow<REAL, R, MODE, W, true, false, OV>;
+                });
+            });
+            if (mixed)
+                s.mixed = {pick<64, 128, 256>(pack_width, [&](auto PW) {
+                               return pick<1, 2, 4, 8>(wpb, [&](auto W) {
+                                   return pick<1, 2, 4>(mixed_npt, [&](auto N) -> MixedFn {
+                                       constexpr int R = PW.value / 64;
+                                       return bwd ? &k_bwd_mixed<REAL, R, W.value, N.value, OV> : &k_fwd_mixed<REAL, R, W.value, N.value, OV>;
+                                   });
+                               });
+                           }),
+                           mixed_lds};
+        }
+        return s;
+    }
+    // everything but the OV sweeps; called once, at the end of init()
+    void resolve_kernels()
+    {
+        for (int bwd = 0; bwd < 2; ++bwd) {
+            kern.sweep[bwd][FWD_PLAIN] = resolve_sweep<FWD_PLAIN, false>(bwd);
+            kern.sweep[bwd][FWD_SOLVE] = resolve_sweep<FWD_SOLVE, false>(bwd);
+            kern.sweep[bwd][FWD_SOLUTION] = resolve_sweep<FWD_SOLUTION, false>(bwd);  // backward: BWD_MARGINALS
+        }
+        kern.ex_threads = exch_small ? EXS_THREADS : exch_medium ? EXM_THREADS : EX_THREADS;
+        pick<EXS_THREADS, EXM_THREADS, EX_THREADS>(kern.ex_threads, [&](auto T_) {
+            constexpr int T = T_.value, U = T == EXS_THREADS ? EXS_UNROLL : T == EXM_THREADS ? EXM_UNROLL : EX_UNROLL,
+                          N = T == EXS_THREADS ? EXS_NPT : T == EXM_THREADS ? EXM_NPT : EX_NPT;
+            kern.ex[0] = {&k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_ITER, T, U, N, false>, exch_lds};
+            kern.ex[1] = {&k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_ITER, T, U, N, true>, exch_lds};          // run_plain()'s
+            kern.ex_w = {&k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_ITER, T, U, N, false, true>, exch_lds};    // learned_iterations()'s
+            kern.project = {&k_project_entries<REAL, T>, vars_per_bin * (uint32_t)sizeof(double)};
+            if (use_seg)
+                pick<2, 4>(seg_groups <= 2 ? 2 : 4, [&](auto G) {
+                    kern.seg[0] = {&k_exchange_seg<REAL, T, G.value, false>, seg_lds};
+                    kern.seg[1] = {&k_exchange_seg<REAL, T, G.value, true>, seg_lds};
+                    kern.seg_w = {&k_exchange_seg<REAL, T, G.value, false, true>, seg_lds};
+                });
+        });
+        kern.ex_raw = {&k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_RAW>, exch_lds};
+        if (small_ok)
+            kern.small = {pick<1, 2, 4, 8, 16>(small_nw, [&](auto NW) -> SmallFn {
+                              return small_rl ? &k_iterate_small<REAL, NW.value, true> : &k_iterate_small<REAL, NW.value, false>;
+                          }),
+                          small_lds};
+        if (n_narrow_layers)
+            pick<1, 2, 4, 8>(wpb, [&](auto W) {
+                const uint32_t lds = wpb * stage_cap * (uint32_t)sizeof(REAL);
+                kern.transpose[0] = {&k_stage_transpose<REAL, W.value, 0>, lds};
+                kern.transpose[1] = {&k_stage_transpose<REAL, W.value, 1>, lds};
+                kern.lincomb[0] = {&k_stage_lincomb<REAL, W.value, 0>, lds};
+                kern.lincomb[1] = {&k_stage_lincomb<REAL, W.value, 5>, lds};
+            });
+    }
+    // The dynamic-LDS limit (launch attribute) of table entries.  One rule: every entry that is launched with dynamic LDS gets exactly those
+    // bytes as its limit, whatever their number — a limit is not a reservation, and "only above the default 64 KiB" would have to know each
+    // kernel's static LDS as well.  The mixed kernels alone get none: init() admits `mixed` only where static + dynamic LDS stay within 64 KiB.
+    int raise_lds_limit(const void* fn, uint32_t lds)
+    {
+        if (fn && lds) HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        return BDDMMA_OK;
+    }
+    template <typename FN>
+    int raise_lds_limit(const Kern<FN>& k) { return raise_lds_limit(reinterpret_cast<const void*>(k.fn), k.lds); }
+    int raise_lds_limits(const Sweep& s)
+    {
+        if (int rc = raise_lds_limit(s.narrow_fn(), s.narrow_lds)) return rc;
+        return raise_lds_limit(s.wide);
+    }
+    int raise_lds_limits(const Kernels& k)
+    {
+        int rc = BDDMMA_OK;
+        for (const auto& dir : k.sweep)
+            for (const Sweep& s : dir)
+                if ((rc = raise_lds_limits(s))) return rc;
+        for (const auto* e : {&k.ex[0], &k.ex[1], &k.ex_w, &k.ex_raw})
+            if ((rc = raise_lds_limit(*e))) return rc;
+        for (const auto* e : {&k.seg[0], &k.seg[1], &k.seg_w})
+            if ((rc = raise_lds_limit(*e))) return rc;
+        for (const auto* e : {&k.transpose[0], &k.transpose[1]})
+            if ((rc = raise_lds_limit(*e))) return rc;
+        for (const auto* e : {&k.lincomb[0], &k.lincomb[1]})
+            if ((rc = raise_lds_limit(*e))) return rc;
+        if ((rc = raise_lds_limit(k.project))) return rc;
+        return raise_lds_limit(k.small);
+    }
+
+    int ov_prepare();  // fills ov_sweep and raises its limits (solver_ov.hpp)
     bool ov_ready = false;
-    template <int MODE, bool OV = false>
-    int launch_fwd(const REAL* delta_lay, REAL omega, int kclass)
+    // One sweep: the wide and the narrow packs (one launch where `mixed`; forward only with mixed_fwd), then the huge ones.
+    int launch_sweep(bool bwd, const Sweep& s, const REAL* delta_lay, REAL omega, int kclass, bool ov = false)
     {
-        static_assert(!OV || MODE == FWD_SOLVE, "omega per layer: solve sweeps only");
+        if (bwd) {  // the costs-to-terminal change: the cached bound is stale
+            lb_cached = false;
+            ++lb_gen;
+        }
         DevPtrs<REAL> d = ptrs(delta_lay);
-        if (OV) d.omega_lay = d_omega_lay;
+        if (ov) d.omega_lay = d_omega_lay;
         prof_begin(kclass);
-        hipStream_t sw = stream;
-        if (mixed && mixed_fwd && MODE == FWD_SOLVE) {
+        if (s.mixed.fn && (bwd || mixed_fwd)) {
             const PackDev pkw = pdev(wb_, nb_.n_packs), pkn = pdev(nb_, 0, stage_lds);
             const uint32_t nw8 = (wb_.n_packs + 7u) & ~7u;
             const dim3 grid(nw8 + narrow_grid(cdiv(nb_.n_packs, wpb))), block(64 * wpb);
-#define LAUNCH_M(R_, W_)                                                                                                                                   \
-    switch (mixed_npt) {                                                                                                                                   \
-        case 1: hipLaunchKernelGGL((k_fwd_mixed<REAL, R_, W_, 1, OV>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;            \
-        case 2: hipLaunchKernelGGL((k_fwd_mixed<REAL, R_, W_, 2, OV>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;            \
-        default: hipLaunchKernelGGL((k_fwd_mixed<REAL, R_, W_, 4, OV>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;           \
-    }
-#define LAUNCH_MW(R_) \
-    switch (wpb) { case 1: LAUNCH_M(R_, 1) break; case 2: LAUNCH_M(R_, 2) break; case 4: LAUNCH_M(R_, 4) break; default: LAUNCH_M(R_, 8) break; }
-            switch (pack_width) {
-                case 64: LAUNCH_MW(1) break;
-                case 128: LAUNCH_MW(2) break;
-                default: LAUNCH_MW(4) break;
-            }
-#undef LAUNCH_MW
-#undef LAUNCH_M
+            hipLaunchKernelGGL(s.mixed.fn, grid, block, s.mixed.lds, stream, d, pkn, pkw, omega, wide_pack_width);
         } else {
-        if (wb_.n_packs) {
-            const PackDev pk = pdev(wb_, nb_.n_packs);
-            const dim3 g(wb_.n_packs), b(wide_threads);
-            switch (wide_npt) {
-                case 1: hipLaunchKernelGGL((k_fwd_wide2<REAL, MODE, 1, OV>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
-                case 2: hipLaunchKernelGGL((k_fwd_wide2<REAL, MODE, 2, OV>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
-                default: hipLaunchKernelGGL((k_fwd_wide2<REAL, MODE, 4, OV>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
+            if (s.wide.fn) hipLaunchKernelGGL(s.wide.fn, dim3(wb_.n_packs), dim3(wide_threads), s.wide.lds, stream, d, pdev(wb_, nb_.n_packs), omega, wide_pack_width);
+            if (nb_.n_packs) {
+                const PackDev pk = pdev(nb_, 0, s.seg_off);
+                const dim3 grid(narrow_grid(cdiv(nb_.n_packs, s.w))), block(64 * s.w);
+                if (s.res2)
+                    hipLaunchKernelGGL(s.res2, grid, block, s.narrow_lds, stream, d_pack_hdr, d_quad_hdr, res2_ns, res2_nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter,
+                                       d_res2_rec, d_res2_rec_off, res2_n_words, d, pk, omega);
+                else if (s.res)
+                    hipLaunchKernelGGL(s.res, grid, block, s.narrow_lds, stream, d_pack_hdr, d_quad_hdr, res_ns, res_nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter, d, pk, omega);
+                else if (s.rec) hipLaunchKernelGGL(s.rec, grid, block, s.narrow_lds, stream, d, pk, s.rec_tab, s.rec_off, s.rec_words, omega);
+                else hipLaunchKernelGGL(s.narrow, grid, block, s.narrow_lds, stream, d, pk, omega);
             }
         }
-        if (nb_.n_packs) {
-            // SOLVE sweeps: `wpb` packs per workgroup with cooperative staging; the other modes stage nothing
-            const uint32_t w = (MODE == FWD_SOLVE) ? wpb : 1;
-            const bool res = use_res && MODE == FWD_SOLVE;
-            const bool two_node = MODE == FWD_SOLVE && !narrow_seg;  // SEG = false instantiation (kernels.hpp); other modes: <..., true> again
-            const uint32_t base_lds = res ? res_lds : ((MODE == FWD_SOLVE) ? stage_lds : 0);
-            const uint32_t dyn = base_lds + seg_bytes(w);
-            const PackDev pk = pdev(nb_, 0, base_lds);
-            const dim3 grid(narrow_grid(cdiv(nb_.n_packs, w))), block(64 * w);
-            const ResDev rd{d_pack_hdr, d_quad_hdr, res_ns, res_nl};
-#define LAUNCH_N(R_, W_)                                                                                                      \
-    if (res && use_res2) hipLaunchKernelGGL((k_fwd_res2<REAL, W_, OV>), grid, block, res2_lds, stream, rd.pack_hdr, rd.quad_hdr, res2_ns, res2_nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter, d_res2_rec, d_res2_rec_off, res2_n_words, d, pk, omega); \
-    else if (res) hipLaunchKernelGGL((k_fwd_res<REAL, R_, W_, OV>), grid, block, dyn, stream, rd.pack_hdr, rd.quad_hdr, rd.ns, rd.nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter, d, pk, omega);                           \
-    else if (MODE == FWD_SOLVE && use_narrow3 && n3_nt && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_fwd_narrow3<REAL, (W_ == 8 ? 8 : 4), sizeof(REAL) == 8, OV>), grid, block, dyn, stream, d, pk, d_lrec, d_lrec_off, lrec_words, omega); \
-    else if (MODE == FWD_SOLVE && use_narrow3 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_fwd_narrow3<REAL, (W_ == 8 ? 8 : 4), false, OV>), grid, block, dyn, stream, d, pk, d_lrec, d_lrec_off, lrec_words, omega); \
-    else if (MODE == FWD_SOLVE && use_narrow2 && n12_nt && R_ == 2 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_fwd_narrow2<REAL, 2, (W_ == 8 ? 8 : 4), false, sizeof(REAL) == 8, OV>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
-    else if (MODE == FWD_SOLVE && !use_narrow2 && n12_nt && R_ == 2 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_fwd_narrow<REAL, 2, FWD_SOLVE, (W_ == 8 ? 8 : 4), false, true, OV>), grid, block, dyn, stream, d, pk, omega); \
-    else if (MODE == FWD_SOLVE && use_narrow2 && narrow_gen) hipLaunchKernelGGL((k_fwd_narrow2<REAL, R_, W_, true, false, OV>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
-    else if (MODE == FWD_SOLVE && use_narrow2) hipLaunchKernelGGL((k_fwd_narrow2<REAL, R_, W_, false, false, OV>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
-    else if (two_node) hipLaunchKernelGGL((k_fwd_narrow<REAL, R_, MODE, W_, MODE != FWD_SOLVE, false, OV>), grid, block, dyn, stream, d, pk, omega); \
-    else hipLaunchKernelGGL((k_fwd_narrow<REAL, R_, MODE, W_, true, false, OV>), grid, block, dyn, stream, d, pk, omega)
-#define LAUNCH_W(R_) \
-    switch (w) { case 1: LAUNCH_N(R_, 1); break; case 2: LAUNCH_N(R_, 2); break; case 4: LAUNCH_N(R_, 4); break; default: LAUNCH_N(R_, 8); break; }
-            switch (pack_width) {
-                case 64: LAUNCH_W(1); break;
-                case 128: LAUNCH_W(2); break;
-                default: LAUNCH_W(4); break;
-            }
-#undef LAUNCH_W
-#undef LAUNCH_N
-        }
-        }  // !mixed
-        if (hb_.n_packs) {
-            const PackDev pk = pdev(hb_, nb_.n_packs + wb_.n_packs);
-            hipLaunchKernelGGL((k_fwd_wide<REAL, MODE, true, OV>), dim3(hb_.n_packs), dim3(WIDE_THREADS), 0, stream, d, pk, omega, huge_pack_width, d_huge_scratch);
-        }
+        if (s.huge) hipLaunchKernelGGL(s.huge, dim3(hb_.n_packs), dim3(WIDE_THREADS), 0, stream, d, pdev(hb_, nb_.n_packs + wb_.n_packs), omega, huge_pack_width, d_huge_scratch);
         prof_end(kclass);
         HIPCHK(hipGetLastError());
         return BDDMMA_OK;
     }
-    template <int MODE, bool OV = false>
-    int launch_bwd(const REAL* delta_lay, REAL omega, int kclass)
-    {
-        static_assert(!OV || MODE == BWD_SOLVE, "omega per layer: solve sweeps only");
-        lb_cached = false;
-        ++lb_gen;
-        DevPtrs<REAL> d = ptrs(delta_lay);
-        if (OV) d.omega_lay = d_omega_lay;
-        prof_begin(kclass);
-        hipStream_t sw = stream;
-        if (mixed && MODE == BWD_SOLVE) {
-            const PackDev pkw = pdev(wb_, nb_.n_packs), pkn = pdev(nb_, 0, stage_lds);
-            const uint32_t nw8 = (wb_.n_packs + 7u) & ~7u;
-            const dim3 grid(nw8 + narrow_grid(cdiv(nb_.n_packs, wpb))), block(64 * wpb);
-#define LAUNCH_M(R_, W_)                                                                                                                                   \
-    switch (mixed_npt) {                                                                                                                                   \
-        case 1: hipLaunchKernelGGL((k_bwd_mixed<REAL, R_, W_, 1, OV>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;            \
-        case 2: hipLaunchKernelGGL((k_bwd_mixed<REAL, R_, W_, 2, OV>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;            \
-        default: hipLaunchKernelGGL((k_bwd_mixed<REAL, R_, W_, 4, OV>), grid, block, mixed_lds, stream, d, pkn, pkw, omega, wide_pack_width); break;           \
-    }
-#define LAUNCH_MW(R_) \
-    switch (wpb) { case 1: LAUNCH_M(R_, 1) break; case 2: LAUNCH_M(R_, 2) break; case 4: LAUNCH_M(R_, 4) break; default: LAUNCH_M(R_, 8) break; }
-            switch (pack_width) {
-                case 64: LAUNCH_MW(1) break;
-                case 128: LAUNCH_MW(2) break;
-                default: LAUNCH_MW(4) break;
-            }
-#undef LAUNCH_MW
-#undef LAUNCH_M
-        } else {
-        if (wb_.n_packs) {
-            const PackDev pk = pdev(wb_, nb_.n_packs);
-            const dim3 g(wb_.n_packs), b(wide_threads);
-            switch (wide_npt) {
-                case 1: hipLaunchKernelGGL((k_bwd_wide2<REAL, MODE, 1, OV>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
-                case 2: hipLaunchKernelGGL((k_bwd_wide2<REAL, MODE, 2, OV>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
-                default: hipLaunchKernelGGL((k_bwd_wide2<REAL, MODE, 4, OV>), g, b, wide_lds, sw, d, pk, omega, wide_pack_width); break;
-            }
-        }
-        if (nb_.n_packs) {
-            // SOLVE sweeps: `wpb` packs per workgroup with cooperative staging; the other modes stage nothing
-            const uint32_t w = (MODE == BWD_SOLVE) ? wpb : 1;
-            const bool res = use_res && MODE == BWD_SOLVE;
-            const bool two_node = MODE == BWD_SOLVE && !narrow_seg;
-            const uint32_t base_lds = res ? res_lds : ((MODE == BWD_SOLVE) ? stage_lds : 0);
-            const uint32_t dyn = base_lds + seg_bytes(w);
-            const PackDev pk = pdev(nb_, 0, base_lds);
-            const dim3 grid(narrow_grid(cdiv(nb_.n_packs, w))), block(64 * w);
-            const ResDev rd{d_pack_hdr, d_quad_hdr, res_ns, res_nl};
-#define LAUNCH_N(R_, W_)                                                                                                      \
-    if (res && use_res2) hipLaunchKernelGGL((k_bwd_res2<REAL, W_, OV>), grid, block, res2_lds, stream, rd.pack_hdr, rd.quad_hdr, res2_ns, res2_nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter, d_res2_rec, d_res2_rec_off, res2_n_words, d, pk, omega); \
-    else if (res) hipLaunchKernelGGL((k_bwd_res<REAL, R_, W_, OV>), grid, block, dyn, stream, rd.pack_hdr, rd.quad_hdr, rd.ns, rd.nl, pk.n_packs, pk.xcd_chunk, d.stop, d.run_iter, d, pk, omega);                           \
-    else if (MODE == BWD_SOLVE && use_narrow3 && n3_nt && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_bwd_narrow3<REAL, (W_ == 8 ? 8 : 4), sizeof(REAL) == 8, OV>), grid, block, dyn, stream, d, pk, d_lrec, d_lrec_off, lrec_words, omega); \
-    else if (MODE == BWD_SOLVE && use_narrow3 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_bwd_narrow3<REAL, (W_ == 8 ? 8 : 4), false, OV>), grid, block, dyn, stream, d, pk, d_lrec, d_lrec_off, lrec_words, omega); \
-    else if (MODE == BWD_SOLVE && use_narrow2 && n12_nt && R_ == 2 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_bwd_narrow2<REAL, 2, (W_ == 8 ? 8 : 4), false, sizeof(REAL) == 8, OV>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
-    else if (MODE == BWD_SOLVE && !use_narrow2 && n12_nt && R_ == 2 && (W_ == 4 || W_ == 8)) hipLaunchKernelGGL((k_bwd_narrow<REAL, 2, BWD_SOLVE, (W_ == 8 ? 8 : 4), false, true, OV>), grid, block, dyn, stream, d, pk, omega); \
-    else if (MODE == BWD_SOLVE && use_narrow2 && narrow_gen) hipLaunchKernelGGL((k_bwd_narrow2<REAL, R_, W_, true, false, OV>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
-    else if (MODE == BWD_SOLVE && use_narrow2) hipLaunchKernelGGL((k_bwd_narrow2<REAL, R_, W_, false, false, OV>), grid, block, dyn, stream, d, pk, d_srec, d_srec_off, srec_words, omega); \
-    else if (two_node) hipLaunchKernelGGL((k_bwd_narrow<REAL, R_, MODE, W_, MODE != BWD_SOLVE, false, OV>), grid, block, dyn, stream, d, pk, omega); \
-    else hipLaunchKernelGGL((k_bwd_narrow<REAL, R_, MODE, W_, true, false, OV>), grid, block, dyn, stream, d, pk, omega)
-#define LAUNCH_W(R_) \
-    switch (w) { case 1: LAUNCH_N(R_, 1); break; case 2: LAUNCH_N(R_, 2); break; case 4: LAUNCH_N(R_, 4); break; default: LAUNCH_N(R_, 8); break; }
-            switch (pack_width) {
-                case 64: LAUNCH_W(1); break;
-                case 128: LAUNCH_W(2); break;
-                default: LAUNCH_W(4); break;
-            }
-#undef LAUNCH_W
-#undef LAUNCH_N
-        }
-        }  // !mixed
-        if (hb_.n_packs) {
-            const PackDev pk = pdev(hb_, nb_.n_packs + wb_.n_packs);
-            hipLaunchKernelGGL((k_bwd_wide<REAL, MODE, true, OV>), dim3(hb_.n_packs), dim3(WIDE_THREADS), 0, stream, d, pk, omega, huge_pack_width, d_huge_scratch);
-        }
-        prof_end(kclass);
-        HIPCHK(hipGetLastError());
-        return BDDMMA_OK;
-    }
+    int launch_fwd(int mode, const REAL* delta_lay, REAL omega, int kclass) { return launch_sweep(false, kern.sweep[0][mode], delta_lay, omega, kclass); }
+    int launch_bwd(int mode, const REAL* delta_lay, REAL omega, int kclass) { return launch_sweep(true, kern.sweep[1][mode], delta_lay, omega, kclass); }
     // compute_delta + normalize_delta + broadcast to the layers, see kernels.hpp (k_exchange_reduce)
     void launch_bcast(const REAL* delta_var, REAL* delta_lay, RunGate g = RunGate{}, RunStep run = RunStep{})
     {
@@ -915,9 +913,9 @@ struct SolverT final : SolverBase {
             hipLaunchKernelGGL((k_delta_gather<REAL, false>), dim3(cdiv(n_vars, 256)), dim3(256), 0, stream, d_mm_binned, d_var_ptr,
                                d_vpos, delta_var, (uint32_t)n_vars, RunGate{});
         else
-            hipLaunchKernelGGL((k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_RAW>), dim3(n_bins), dim3(EX_THREADS), exch_lds, stream, d_mm_binned,
-                               d_bin_ptr, d_bvar, (const uint32_t*)nullptr, 0u, vars_per_bin, (uint32_t)n_vars, (uint32_t)n_layers, d_nbdds, delta_var,
-                               (REAL*)nullptr, RunStep{});
+            hipLaunchKernelGGL(kern.ex_raw.fn, dim3(n_bins), dim3(EX_THREADS), kern.ex_raw.lds, stream, d_mm_binned, d_bin_ptr, d_bvar,
+                               (const uint32_t*)nullptr, 0u, vars_per_bin, (uint32_t)n_vars, (uint32_t)n_layers, d_nbdds, delta_var, (REAL*)nullptr, RunStep{},
+                               (const REAL*)nullptr);
     }
     int exchange(bool ends_iteration = false)
     {
@@ -933,31 +931,17 @@ struct SolverT final : SolverBase {
                                d_vpos, d_delta_var, (uint32_t)n_vars, gate());
             launch_bcast(d_delta_var, d_delta_lay, gate(), rstep);
             delta_var_valid = true;
-        } else if (use_seg) {
-#define LAUNCH_SEG(T_, RUN_)                                                                                                                        \
-    if (seg_groups <= 2) { LAUNCH_SEG_G(T_, 2, RUN_); } else { LAUNCH_SEG_G(T_, 4, RUN_); }
-#define LAUNCH_SEG_G(T_, G_, RUN_)                                                                                                                  \
-    hipLaunchKernelGGL((k_exchange_seg<REAL, T_, G_, RUN_>), dim3(n_bins + ((RUN_) && rstep.ctl != nullptr ? 1u : 0u)), dim3(T_), seg_lds, stream, d_mm_binned, \
-                       reinterpret_cast<const uint4*>(d_seg_bin), gate().stop, gate().iter, reinterpret_cast<const uint4*>(d_seg_perm),              \
-                       reinterpret_cast<const uint2*>(d_seg_thr), seg_tile_off, seg_cnt_off, d_delta_lay, rstep)
-#define LAUNCH_SEG_R(T_) do { if (run_stop) { LAUNCH_SEG(T_, true) } else { LAUNCH_SEG(T_, false) } } while (0)
-            if (exch_small) LAUNCH_SEG_R(EXS_THREADS);
-            else if (exch_medium) LAUNCH_SEG_R(EXM_THREADS);
-            else LAUNCH_SEG_R(EX_THREADS);
-#undef LAUNCH_SEG_R
-#undef LAUNCH_SEG
-#undef LAUNCH_SEG_G
-            delta_var_valid = false;
         } else {
-#define LAUNCH_EX(T_, U_, N_, RUN_)                                                                                                                  \
-    hipLaunchKernelGGL((k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_ITER, T_, U_, N_, RUN_>), dim3(n_bins + ((RUN_) && rstep.ctl != nullptr ? 1u : 0u)), dim3(T_), exch_lds, stream, d_mm_binned, d_bin_ptr, \
-                       d_bvar, gate().stop, gate().iter, vars_per_bin, (uint32_t)n_vars, (uint32_t)n_layers, d_nbdds, (REAL*)nullptr, d_delta_lay, rstep)
-#define LAUNCH_EX_R(T_, U_, N_) do { if (run_stop) LAUNCH_EX(T_, U_, N_, true); else LAUNCH_EX(T_, U_, N_, false); } while (0)
-            if (exch_medium) LAUNCH_EX_R(EXM_THREADS, EXM_UNROLL, EXM_NPT);
-            else if (exch_small) LAUNCH_EX_R(EXS_THREADS, EXS_UNROLL, EXS_NPT);
-            else LAUNCH_EX_R(EX_THREADS, EX_UNROLL, EX_NPT);
-#undef LAUNCH_EX_R
-#undef LAUNCH_EX
+            // RUN: the instantiation that looks at the stop word and, in the launch that ends an iteration, reduces the bound in one workgroup more
+            const bool run = run_stop != nullptr;
+            const dim3 grid(n_bins + (run && rstep.ctl != nullptr ? 1u : 0u)), block(kern.ex_threads);
+            if (use_seg)
+                hipLaunchKernelGGL(kern.seg[run].fn, grid, block, kern.seg[run].lds, stream, d_mm_binned, reinterpret_cast<const uint4*>(d_seg_bin), gate().stop,
+                                   gate().iter, reinterpret_cast<const uint4*>(d_seg_perm), reinterpret_cast<const uint2*>(d_seg_thr), seg_tile_off, seg_cnt_off,
+                                   d_delta_lay, rstep, (const REAL*)nullptr);
+            else
+                hipLaunchKernelGGL(kern.ex[run].fn, grid, block, kern.ex[run].lds, stream, d_mm_binned, d_bin_ptr, d_bvar, gate().stop, gate().iter, vars_per_bin,
+                                   (uint32_t)n_vars, (uint32_t)n_layers, d_nbdds, (REAL*)nullptr, d_delta_lay, rstep, (const REAL*)nullptr);
             delta_var_valid = false;
         }
         prof_end(BDDMMA_K_FINISH_DELTA);
@@ -970,7 +954,7 @@ struct SolverT final : SolverBase {
     {
         if (fwd_valid) return BDDMMA_OK;
         HIPCHK(hipSetDevice(device));
-        int rc = launch_fwd<FWD_PLAIN>(nullptr, REAL(0), BDDMMA_K_OTHER);
+        int rc = launch_fwd(FWD_PLAIN, nullptr, REAL(0), BDDMMA_K_OTHER);
         if (rc) return rc;
         fwd_valid = true;
         return BDDMMA_OK;
@@ -979,7 +963,7 @@ struct SolverT final : SolverBase {
     {
         if (bwd_valid) return BDDMMA_OK;
         HIPCHK(hipSetDevice(device));
-        int rc = launch_bwd<BWD_PLAIN>(nullptr, REAL(0), BDDMMA_K_OTHER);
+        int rc = launch_bwd(BWD_PLAIN, nullptr, REAL(0), BDDMMA_K_OTHER);
         if (rc) return rc;
         bwd_valid = true;
         return BDDMMA_OK;
@@ -1075,12 +1059,12 @@ struct SolverT final : SolverBase {
         return BDDMMA_OK;
     }
 
-    // ov: omega per layer from d_omega_lay (learned iterations with omega_vec; launch_fwd_ov)
+    // ov: omega per layer from d_omega_lay (learned iterations with omega_vec; ov_sweep)
     int mma_forward(REAL omega, const REAL* delta_lay, bool ov = false)
     {
         int rc;
         if (!bwd_valid && (rc = backward_run())) return rc;  // bdd_cuda_parallel_mma.cu:211-212
-        rc = ov ? launch_fwd_ov(delta_lay, omega) : launch_fwd<FWD_SOLVE>(delta_lay, omega, BDDMMA_K_FORWARD_MM);
+        rc = launch_sweep(false, ov ? ov_sweep[0] : kern.sweep[0][FWD_SOLVE], delta_lay, omega, BDDMMA_K_FORWARD_MM, ov);
         x_layer_valid = false;  // the forward sweep rewrites the deferred values by entry only
         if (rc) return rc;
         fwd_valid = true;
@@ -1093,7 +1077,7 @@ struct SolverT final : SolverBase {
             err = "backward_mm requires a valid forward state (call forward_mm first)";  // assert at :304
             return BDDMMA_ERR_STATE;
         }
-        int rc = ov ? launch_bwd_ov(delta_lay, omega) : launch_bwd<BWD_SOLVE>(delta_lay, omega, BDDMMA_K_BACKWARD_MM);
+        int rc = launch_sweep(true, ov ? ov_sweep[1] : kern.sweep[1][BWD_SOLVE], delta_lay, omega, BDDMMA_K_BACKWARD_MM, ov);
         if (rc) return rc;
         x_layer_valid = d_x_layer != nullptr;
         fwd_valid = false;
@@ -1111,11 +1095,7 @@ struct SolverT final : SolverBase {
         ++lb_gen;
         const DevPtrs<REAL> d = ptrs(d_delta_lay);
         const PackDev pk = pdev(nb_, 0, 0);
-#define LAUNCH_SMALL(NW_)                                                                                                                       \
-    if (small_rl) hipLaunchKernelGGL((k_iterate_small<REAL, NW_, true>), dim3(1), dim3(64 * NW_), small_lds, stream, small, d, pk, omega, n, rstep); \
-    else hipLaunchKernelGGL((k_iterate_small<REAL, NW_, false>), dim3(1), dim3(64 * NW_), small_lds, stream, small, d, pk, omega, n, rstep)
-        switch (small_nw) { case 1: LAUNCH_SMALL(1); break; case 2: LAUNCH_SMALL(2); break; case 4: LAUNCH_SMALL(4); break; case 8: LAUNCH_SMALL(8); break; default: LAUNCH_SMALL(16); break; }
-#undef LAUNCH_SMALL
+        hipLaunchKernelGGL(kern.small.fn, dim3(1), dim3(64 * small_nw), kern.small.lds, stream, small, d, pk, omega, n, rstep);
         HIPCHK(hipGetLastError());
         // the state the last iteration's four launches leave (mma_forward, exchange, mma_backward, exchange)
         x_layer_valid = false;
@@ -1168,30 +1148,12 @@ struct SolverT final : SolverBase {
             hipLaunchKernelGGL((k_exchange_bcast<REAL, true>), dim3(cdiv(cdiv(n_layers, 4), 256)), dim3(256), 0, stream, (const REAL*)d_delta_c, d_evar,
                                d_delta_lay, (uint32_t)n_layers, (uint32_t)n_vars, RunGate{}, RunStep{}, al);
         } else if (use_seg) {
-#define LAUNCH_SEG_W(T_)                                                                                                                                  \
-    do {                                                                                                                                                  \
-        if (seg_groups <= 2)                                                                                                                              \
-            hipLaunchKernelGGL((k_exchange_seg<REAL, T_, 2, false, true>), dim3(n_bins), dim3(T_), seg_lds, stream, d_mm_binned,                         \
-                               reinterpret_cast<const uint4*>(d_seg_bin), (const uint32_t*)nullptr, 0u, reinterpret_cast<const uint4*>(d_seg_perm),      \
-                               reinterpret_cast<const uint2*>(d_seg_thr), seg_tile_off, seg_cnt_off, d_delta_lay, RunStep{}, al);                       \
-        else                                                                                                                                              \
-            hipLaunchKernelGGL((k_exchange_seg<REAL, T_, 4, false, true>), dim3(n_bins), dim3(T_), seg_lds, stream, d_mm_binned,                         \
-                               reinterpret_cast<const uint4*>(d_seg_bin), (const uint32_t*)nullptr, 0u, reinterpret_cast<const uint4*>(d_seg_perm),      \
-                               reinterpret_cast<const uint2*>(d_seg_thr), seg_tile_off, seg_cnt_off, d_delta_lay, RunStep{}, al);                       \
-    } while (0)
-            if (exch_small) LAUNCH_SEG_W(EXS_THREADS);
-            else if (exch_medium) LAUNCH_SEG_W(EXM_THREADS);
-            else LAUNCH_SEG_W(EX_THREADS);
-#undef LAUNCH_SEG_W
+            hipLaunchKernelGGL(kern.seg_w.fn, dim3(n_bins), dim3(kern.ex_threads), kern.seg_w.lds, stream, d_mm_binned, reinterpret_cast<const uint4*>(d_seg_bin),
+                               (const uint32_t*)nullptr, 0u, reinterpret_cast<const uint4*>(d_seg_perm), reinterpret_cast<const uint2*>(d_seg_thr), seg_tile_off,
+                               seg_cnt_off, d_delta_lay, RunStep{}, al);
         } else {
-#define LAUNCH_EX_W(T_, U_, N_)                                                                                                                           \
-    hipLaunchKernelGGL((k_exchange_reduce<REAL, BDDMMA_EX_ACC, EX_ITER, T_, U_, N_, false, true>), dim3(n_bins), dim3(T_), exch_lds, stream, d_mm_binned,  \
-                       d_bin_ptr, d_bvar, (const uint32_t*)nullptr, 0u, vars_per_bin, (uint32_t)n_vars, (uint32_t)n_layers, d_nbdds, (REAL*)nullptr,      \
-                       d_delta_lay, RunStep{}, al)
-            if (exch_medium) LAUNCH_EX_W(EXM_THREADS, EXM_UNROLL, EXM_NPT);
-            else if (exch_small) LAUNCH_EX_W(EXS_THREADS, EXS_UNROLL, EXS_NPT);
-            else LAUNCH_EX_W(EX_THREADS, EX_UNROLL, EX_NPT);
-#undef LAUNCH_EX_W
+            hipLaunchKernelGGL(kern.ex_w.fn, dim3(n_bins), dim3(kern.ex_threads), kern.ex_w.lds, stream, d_mm_binned, d_bin_ptr, d_bvar, (const uint32_t*)nullptr,
+                               0u, vars_per_bin, (uint32_t)n_vars, (uint32_t)n_layers, d_nbdds, (REAL*)nullptr, d_delta_lay, RunStep{}, al);
         }
         delta_var_valid = false;
         prof_end(BDDMMA_K_FINISH_DELTA);
@@ -1304,7 +1266,7 @@ struct SolverT final : SolverBase {
             ++ran;
             if (cfi > 0 && (cfi >= num_itr - itr || converged)) {  // :211-254
                 HIPCHK(hipMemsetAsync(d_sol, 0, n_layers, stream));
-                if ((rc = launch_fwd<FWD_SOLUTION>(nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
+                if ((rc = launch_fwd(FWD_SOLUTION, nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
                 hipLaunchKernelGGL((k_char_to_real<REAL>), gl, blk, 0, stream, (const char*)d_sol, last_sol, (uint32_t)L);
                 hipLaunchKernelGGL((k_lb_per_bdd<REAL>), gb, blk, 0, stream, d_T, d_root_slot, lb_last, (uint32_t)B);
                 if (tracked == 0) {
@@ -1660,7 +1622,7 @@ struct SolverT final : SolverBase {
         HIPCHK(hipSetDevice(device));
         int rc;
         if ((rc = forward_run())) return rc;  // bdd_cuda_base.cu:720
-        if ((rc = launch_bwd<BWD_MARGINALS>(nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
+        if ((rc = launch_bwd(BWD_MARGINALS, nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
         bwd_valid = true;
         return marginals_out(sorted, var, mm0, mm1, on_device);
     }
@@ -1715,7 +1677,7 @@ struct SolverT final : SolverBase {
         HIPCHK(hipSetDevice(device));
         int rc;
         if ((rc = forward_run())) return rc;
-        if ((rc = launch_bwd<BWD_MARGINALS>(nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
+        if ((rc = launch_bwd(BWD_MARGINALS, nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
         bwd_valid = true;
         REAL* dst = on_device ? (REAL*)out : d_tmp0;  // in place over mm0 when the result goes to the host
         hipLaunchKernelGGL((k_diff<REAL, REAL>), dim3(cdiv(n_layers, 256)), dim3(256), 0, stream, dst, (const REAL*)d_tmp1, (const REAL*)d_tmp0, (uint32_t)n_layers);
@@ -1729,7 +1691,7 @@ struct SolverT final : SolverBase {
         int rc;
         if ((rc = backward_run())) return rc;
         HIPCHK(hipMemsetAsync(d_sol, 0, n_layers, stream));
-        if ((rc = launch_fwd<FWD_SOLUTION>(nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
+        if ((rc = launch_fwd(FWD_SOLUTION, nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
         // (fwd_valid stays what it was: the solution sweep recomputes the costs-from-root on the fly and does not store them)
         const hipMemcpyKind k = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
         if (!sorted) {
@@ -1754,7 +1716,7 @@ struct SolverT final : SolverBase {
         if (!prezeroed) HIPCHK(hipMemsetAsync(dev_out, 0, n_layers, stream));
         char* const own = d_sol;
         d_sol = dev_out;  // ptrs() hands d_sol to the sweep
-        rc = launch_fwd<FWD_SOLUTION>(nullptr, REAL(0), BDDMMA_K_OTHER);
+        rc = launch_fwd(FWD_SOLUTION, nullptr, REAL(0), BDDMMA_K_OTHER);
         d_sol = own;
         if (rc) return rc;
         return BDDMMA_OK;
@@ -1810,7 +1772,6 @@ struct SolverT final : SolverBase {
     REAL* d_proj_ent = nullptr;     // ... and in entry order
     bool proj_staged = false;       // the last projection_means took the staged path
     bool proj_pending = false;      // ... and its way back to layer order is still to be done (with the first step)
-    bool proj_attr_set = false;
     const void* proj_of = nullptr;  // the vector the last projection_means was called on
     bool use_staged_projection() const
     {
@@ -1818,16 +1779,18 @@ struct SolverT final : SolverBase {
         if (n_narrow_layers == 0) return false;
         return (opts_variant & 0x200u) != 0 || n_layers >= 500000;
     }
-    template <int TO_LAYERS>
-    void launch_stage_transpose(const REAL* in, REAL* out, REAL* lohi, REAL step)
+    void launch_stage_transpose(int to_layers, const REAL* in, REAL* out, REAL* lohi, REAL step)
     {
-        const PackDev pk = pdev(nb_, 0);
-        const uint32_t n_quads = (uint32_t)cdiv(nb_.n_packs, wpb);
-        const uint32_t lds = wpb * stage_cap * (uint32_t)sizeof(REAL);
-#define LAUNCH_T(W_) hipLaunchKernelGGL((k_stage_transpose<REAL, W_, TO_LAYERS>), dim3(n_quads), dim3(64 * W_), lds, stream, in, out, pk, (const uint32_t*)d_cs_entry, \
-                                        (const uint16_t*)d_cs_slot, n_narrow_layers, (uint32_t)n_layers, lohi, step)
-        switch (wpb) { case 1: LAUNCH_T(1); break; case 2: LAUNCH_T(2); break; case 4: LAUNCH_T(4); break; default: LAUNCH_T(8); break; }
-#undef LAUNCH_T
+        const Kern<TransFn>& k = kern.transpose[to_layers];
+        hipLaunchKernelGGL(k.fn, dim3(cdiv(nb_.n_packs, wpb)), dim3(64 * wpb), k.lds, stream, in, out, pdev(nb_, 0), (const uint32_t*)d_cs_entry,
+                           (const uint16_t*)d_cs_slot, n_narrow_layers, (uint32_t)n_layers, lohi, step);
+    }
+    // x_e -= mean over the entries of its variable (d_proj_ent, in place); the way back to layer order is then pending
+    void launch_project_entries()
+    {
+        hipLaunchKernelGGL(kern.project.fn, dim3(n_bins), dim3(kern.ex_threads), kern.project.lds, stream, d_proj_ent, d_bin_ptr, d_bvar, d_nbdds, vars_per_bin,
+                           (uint32_t)n_vars, (uint32_t)n_layers);
+        proj_pending = true;
     }
     int projection_means(const void* g) override
     {
@@ -1844,23 +1807,12 @@ struct SolverT final : SolverBase {
         }
         if (!d_proj_dir && (rc = dalloc(&d_proj_dir, n_layers))) return rc;
         if (!d_proj_ent && (rc = dalloc(&d_proj_ent, n_layers))) return rc;
-        const uint32_t plds = vars_per_bin * (uint32_t)sizeof(double);
-        if (!proj_attr_set) {
-            if (plds > 64 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_project_entries<REAL, EX_THREADS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
-            proj_attr_set = true;
-        }
         // layers -> entries 
-        launch_stage_transpose<0>((const REAL*)g, d_proj_ent, (REAL*)nullptr, REAL(0));
+        launch_stage_transpose(0, (const REAL*)g, d_proj_ent, (REAL*)nullptr, REAL(0));
         if (n_layers > n_narrow_layers)
             hipLaunchKernelGGL((k_layers_to_entries<REAL>), dim3(cdiv(n_layers - n_narrow_layers, 256)), dim3(256), 0, stream, (const REAL*)g + n_narrow_layers,
                                d_lpos + n_narrow_layers, d_proj_ent, (uint32_t)(n_layers - n_narrow_layers));
-        // x_e -= mean over the entries of its variable
-#define LAUNCH_P(T_) hipLaunchKernelGGL((k_project_entries<REAL, T_>), dim3(n_bins), dim3(T_), plds, stream, d_proj_ent, d_bin_ptr, d_bvar, d_nbdds, vars_per_bin, (uint32_t)n_vars, (uint32_t)n_layers)
-        if (exch_small) LAUNCH_P(EXS_THREADS);
-        else if (exch_medium) LAUNCH_P(EXM_THREADS);
-        else LAUNCH_P(EX_THREADS);
-#undef LAUNCH_P
-        proj_pending = true;
+        launch_project_entries();
         HIPCHK(hipGetLastError());
         return BDDMMA_OK;
     }
@@ -1878,28 +1830,10 @@ struct SolverT final : SolverBase {
         proj_of = tag;
         if (!d_proj_dir && (rc = dalloc(&d_proj_dir, n_layers))) return rc;
         if (!d_proj_ent && (rc = dalloc(&d_proj_ent, n_layers))) return rc;
-        const uint32_t plds = vars_per_bin * (uint32_t)sizeof(double);
-        if (!proj_attr_set) {
-            if (plds > 64 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_project_entries<REAL, EX_THREADS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
-            proj_attr_set = true;
-        }
-        {
-            const PackDev pk = pdev(nb_, 0);
-            const uint32_t n_quads = (uint32_t)cdiv(nb_.n_packs, wpb);
-            const uint32_t lds = wpb * stage_cap * (uint32_t)sizeof(REAL);
-#define LAUNCH_LC(W_, NS_) hipLaunchKernelGGL((k_stage_lincomb<REAL, W_, NS_>), dim3(n_quads), dim3(64 * W_), lds, stream, lc, d_proj_ent, pk, (const uint32_t*)d_cs_entry, \
-                                              (const uint16_t*)d_cs_slot, n_narrow_layers, (uint32_t)n_layers)
-#define LAUNCH_LCW(W_) do { if (lc.ns == 5) LAUNCH_LC(W_, 5); else LAUNCH_LC(W_, 0); } while (0)
-            switch (wpb) { case 1: LAUNCH_LCW(1); break; case 2: LAUNCH_LCW(2); break; case 4: LAUNCH_LCW(4); break; default: LAUNCH_LCW(8); break; }
-#undef LAUNCH_LCW
-#undef LAUNCH_LC
-        }
-#define LAUNCH_P(T_) hipLaunchKernelGGL((k_project_entries<REAL, T_>), dim3(n_bins), dim3(T_), plds, stream, d_proj_ent, d_bin_ptr, d_bvar, d_nbdds, vars_per_bin, (uint32_t)n_vars, (uint32_t)n_layers)
-        if (exch_small) LAUNCH_P(EXS_THREADS);
-        else if (exch_medium) LAUNCH_P(EXM_THREADS);
-        else LAUNCH_P(EX_THREADS);
-#undef LAUNCH_P
-        proj_pending = true;
+        const Kern<LincombFn>& k = kern.lincomb[lc.ns == 5];
+        hipLaunchKernelGGL(k.fn, dim3(cdiv(nb_.n_packs, wpb)), dim3(64 * wpb), k.lds, stream, lc, d_proj_ent, pdev(nb_, 0), (const uint32_t*)d_cs_entry,
+                           (const uint16_t*)d_cs_slot, n_narrow_layers, (uint32_t)n_layers);
+        launch_project_entries();
         HIPCHK(hipGetLastError());
         return BDDMMA_OK;
     }
@@ -1911,7 +1845,7 @@ struct SolverT final : SolverBase {
         if (proj_staged) {
             if (proj_pending) {
                 // entries -> layers, with this step applied on the way
-                launch_stage_transpose<1>((const REAL*)d_proj_ent, d_proj_dir, d_lohi, REAL(step));
+                launch_stage_transpose(1, (const REAL*)d_proj_ent, d_proj_dir, d_lohi, REAL(step));
                 if (n_layers > n_narrow_layers) {
                     const uint32_t nw = (uint32_t)(n_layers - n_narrow_layers);
                     hipLaunchKernelGGL((k_entries_to_layers<REAL>), dim3(cdiv(nw, 256)), dim3(256), 0, stream, (const REAL*)d_proj_ent, d_lpos + n_narrow_layers,
@@ -1948,7 +1882,7 @@ struct SolverT final : SolverBase {
         *applied = 0;
         if ((rc = distribute_delta())) return rc;                 // :265
         if ((rc = forward_run())) return rc;                      // min_marginals_cuda(), :266
-        if ((rc = launch_bwd<BWD_MARGINALS>(nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
+        if ((rc = launch_bwd(BWD_MARGINALS, nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
         bwd_valid = true;
         HIPCHK(hipMemsetAsync(d_counts, 0, 4 * sizeof(uint32_t), stream));
         REAL* c0 = d_delta_c;               // 2V scratch: [0,V) cost_delta_0, [V,2V) cost_delta_1
@@ -2003,10 +1937,10 @@ struct SolverT final : SolverBase {
         int rc = BDDMMA_OK;
         auto once = [&]() -> int {
             switch (kind) {
-                case 0: return launch_fwd<FWD_PLAIN>(nullptr, REAL(0), BDDMMA_K_OTHER);
-                case 1: return launch_bwd<BWD_PLAIN>(nullptr, REAL(0), BDDMMA_K_OTHER);
-                case 2: return launch_fwd<FWD_SOLVE>(d_delta_lay, REAL(0.5), BDDMMA_K_OTHER);
-                case 3: return launch_bwd<BWD_SOLVE>(d_delta_lay, REAL(0.5), BDDMMA_K_OTHER);
+                case 0: return launch_fwd(FWD_PLAIN, nullptr, REAL(0), BDDMMA_K_OTHER);
+                case 1: return launch_bwd(BWD_PLAIN, nullptr, REAL(0), BDDMMA_K_OTHER);
+                case 2: return launch_fwd(FWD_SOLVE, d_delta_lay, REAL(0.5), BDDMMA_K_OTHER);
+                case 3: return launch_bwd(BWD_SOLVE, d_delta_lay, REAL(0.5), BDDMMA_K_OTHER);
                 case 4: return exchange();
                 case 5: launch_bcast(d_delta_c, d_delta_lay_c); return BDDMMA_OK;
                 case 8: return sm_launch_fwd();

@@ -2,7 +2,5 @@
 #include "solver_ov.hpp"
 
 namespace bddmma {
-template int SolverT<float>::launch_fwd_ov(const float*, float);
-template int SolverT<float>::launch_bwd_ov(const float*, float);
 template int SolverT<float>::ov_prepare();
 }  // namespace bddmma

@@ -2,7 +2,5 @@
 #include "solver_ov.hpp"
 
 namespace bddmma {
-template int SolverT<double>::launch_fwd_ov(const double*, double);
-template int SolverT<double>::launch_bwd_ov(const double*, double);
 template int SolverT<double>::ov_prepare();
 }  // namespace bddmma

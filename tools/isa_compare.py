@@ -2,9 +2,10 @@
 A kernel of OLD is matched in NEW by its exact demangled name, or else by that name with one template argument `false` appended to its
 argument list (a kernel template that gained a defaulted flag: the instantiation with the flag at its default).  A name that occurs in
 several device code objects of a library (a template instantiated in more than one translation unit) must have the same instructions in
-each; otherwise it is reported as AMBIGUOUS.
+each, or the same sequence of differing copies in both libraries; otherwise it is reported as AMBIGUOUS.
 python tools/isa_compare.py OLD.so NEW.so [name-substring ...]   (default: k_fwd_narrow3 k_bwd_narrow3)
-Prints one line per kernel (identical / DIFFERENT / MISSING / AMBIGUOUS, instruction counts) and exits 1 unless all are identical."""
+Prints one line per kernel (identical / DIFFERENT / MISSING / AMBIGUOUS, instruction counts; NEW-ONLY for a kernel OLD has no match for)
+and exits 1 unless all are identical."""
 import os
 import re
 import shutil
@@ -36,7 +37,7 @@ def kernels(lib):
                 if cur is None or not ln.startswith("\t"):
                     continue
                 ins = ln.split("//")[0].strip()
-                if ins:
+                if ins and ins != "...":  # "...": objdump's mark for the zero padding between two functions, not an instruction
                     cur.append(ins)
     return out
 
@@ -57,6 +58,7 @@ def main():
     pats = sys.argv[3:] or ["k_fwd_narrow3", "k_bwd_narrow3"]
     ko, kn = kernels(old), kernels(new)
     bad = 0
+    matched = set()
     for d in sorted(ko):
         if not any(p in d for p in pats):
             continue
@@ -65,7 +67,11 @@ def main():
             print(f"MISSING    {d}")
             bad += 1
             continue
+        matched.add(n)
         a, b = unique(ko[d]), unique(kn[n])
+        if (a is None or b is None) and ko[d] == kn[n]:  # the copies differ from each other, but both libraries have the same ones
+            print(f"identical  {len(ko[d])} differing copies, the same in both  {d}")
+            continue
         if a is None or b is None:
             print(f"AMBIGUOUS  {d}: copies in several code objects differ")
             bad += 1
@@ -73,6 +79,10 @@ def main():
         same = a == b
         bad += not same
         print(f"{'identical' if same else 'DIFFERENT'}  {len(a):6d} / {len(b):6d} instructions  {d}  ->  {n}")
+    for n in sorted(kn):
+        if n not in matched and any(p in n for p in pats):
+            print(f"NEW-ONLY   {n}")
+            bad += 1
     return 1 if bad else 0
 
 
