@@ -98,6 +98,10 @@ SIGNATURES = {
     "bddmma_min_marginal_diff": (_I, [_V, _V, _I]),
     "bddmma_sum_marginals": (_I, [_V, _I, _I, _V, _V, _V, _I]),
     "bddmma_smooth_solution": (_I, [_V, _V, _I]),
+    "bddmma_grad_min_marginal_diff": (_I, [_V, _V, _V, _V, _I]),
+    "bddmma_grad_lower_bound_per_bdd": (_I, [_V, _V, _V, _V, _I, _I]),
+    "bddmma_grad_distribute_delta": (_I, [_V, _V, _V, _V, _I]),
+    "bddmma_grad_cost_perturbation": (_I, [_V, _V, _V, _V, _V, _I]),
     "bddmma_bdds_solution": (_I, [_V, _I, _V, _I]),
     "bddmma_net_solver_costs": (_I, [_V, _V, _I]),
     "bddmma_make_dual_feasible": (_I, [_V, _V, _I]),

@@ -322,6 +322,58 @@ class bdd_hip_parallel_mma {
         check(bddmma_smooth_solution(h_, out.data(), 0));
         return out;
     }
+    // ---- the single-shot backward operators of bdd_cuda_learned_mma<REAL> (bdd_cuda_learned_mma.h:82-110); device pointers of nr_layers()
+    // entries in the solver's layer order unless stated, owned by the caller; state contracts in include/bdd_mma.h (bddmma_grad_*)
+    // grad_mm_diff_all_hops(incoming_grad_mm, grad_lo_cost_out, grad_hi_cost_out) (bdd_cuda_learned_mma.cu:623-1023)
+    void grad_mm_diff_all_hops(const REAL* dev_grad_mm, REAL* dev_grad_lo_out, REAL* dev_grad_hi_out)
+    {
+        check(bddmma_grad_min_marginal_diff(h_, dev_grad_mm, dev_grad_lo_out, dev_grad_hi_out, 1));
+    }
+    // grad_lower_bound_per_bdd(grad_lb_per_bdd [nr_bdds()], grad_lo_cost_out, grad_hi_cost_out, account_for_constant) (:387-416); smooth: the
+    // gradient of the smooth lower bound (grad_smooth_lower_bound_per_bdd of the reference's Python module)
+    void grad_lower_bound_per_bdd(const REAL* dev_grad_lb_per_bdd, REAL* dev_grad_lo_out, REAL* dev_grad_hi_out, bool smooth = false)
+    {
+        check(bddmma_grad_lower_bound_per_bdd(h_, dev_grad_lb_per_bdd, dev_grad_lo_out, dev_grad_hi_out, smooth ? 1 : 0, 1));
+    }
+    // grad_distribute_delta(grad_lo_cost, grad_hi_cost, grad_deferred_mm_diff_out) (:1025-1065): refers to the last distribute_delta()
+    void grad_distribute_delta(const REAL* dev_grad_lo, const REAL* dev_grad_hi, REAL* dev_grad_deferred_mm_out)
+    {
+        check(bddmma_grad_distribute_delta(h_, dev_grad_lo, dev_grad_hi, dev_grad_deferred_mm_out, 1));
+    }
+    // grad_cost_perturbation(grad_lo_cost, grad_hi_cost, grad_lo_pert_out, grad_hi_pert_out) (:1067-1187): outputs of nr_variables() entries
+    void grad_cost_perturbation(const REAL* dev_grad_lo, const REAL* dev_grad_hi, REAL* dev_grad_lo_pert_out, REAL* dev_grad_hi_pert_out)
+    {
+        check(bddmma_grad_cost_perturbation(h_, dev_grad_lo, dev_grad_hi, dev_grad_lo_pert_out, dev_grad_hi_pert_out, 1));
+    }
+    // the same four on host vectors: {grad_lo, grad_hi} / grad_deferred_mm / {grad_lo_pert, grad_hi_pert}
+    std::pair<std::vector<REAL>, std::vector<REAL>> grad_mm_diff_all_hops(const std::vector<REAL>& grad_mm)
+    {
+        if (grad_mm.size() != nr_layers()) throw std::invalid_argument("grad_mm_diff_all_hops: grad_mm must have nr_layers() entries");
+        std::vector<REAL> lo(nr_layers()), hi(nr_layers());
+        check(bddmma_grad_min_marginal_diff(h_, grad_mm.data(), lo.data(), hi.data(), 0));
+        return {std::move(lo), std::move(hi)};
+    }
+    std::pair<std::vector<REAL>, std::vector<REAL>> grad_lower_bound_per_bdd(const std::vector<REAL>& grad_lb_per_bdd, bool smooth = false)
+    {
+        if (grad_lb_per_bdd.size() != nr_bdds()) throw std::invalid_argument("grad_lower_bound_per_bdd: grad_lb_per_bdd must have nr_bdds() entries");
+        std::vector<REAL> lo(nr_layers()), hi(nr_layers());
+        check(bddmma_grad_lower_bound_per_bdd(h_, grad_lb_per_bdd.data(), lo.data(), hi.data(), smooth ? 1 : 0, 0));
+        return {std::move(lo), std::move(hi)};
+    }
+    std::vector<REAL> grad_distribute_delta(const std::vector<REAL>& grad_lo, const std::vector<REAL>& grad_hi)
+    {
+        if (grad_lo.size() != nr_layers() || grad_hi.size() != nr_layers()) throw std::invalid_argument("grad_distribute_delta: nr_layers() entries each");
+        std::vector<REAL> out(nr_layers());
+        check(bddmma_grad_distribute_delta(h_, grad_lo.data(), grad_hi.data(), out.data(), 0));
+        return out;
+    }
+    std::pair<std::vector<REAL>, std::vector<REAL>> grad_cost_perturbation(const std::vector<REAL>& grad_lo, const std::vector<REAL>& grad_hi)
+    {
+        if (grad_lo.size() != nr_layers() || grad_hi.size() != nr_layers()) throw std::invalid_argument("grad_cost_perturbation: nr_layers() entries each");
+        std::vector<REAL> lo(nr_variables()), hi(nr_variables());
+        check(bddmma_grad_cost_perturbation(h_, grad_lo.data(), grad_hi.data(), lo.data(), hi.data(), 0));
+        return {std::move(lo), std::move(hi)};
+    }
     // two_dim_variable_array<REAL> bdds_solution() (bdd_cuda_base.cu:1204-1233): [variable][bdd] -> 0 / 1, the argmin path of every BDD,
     // BDDs of a variable in ascending order (primal_variable_sorting_order_, :379-391); nested vectors instead of two_dim_variable_array
     std::vector<std::vector<REAL>> bdds_solution()

@@ -281,6 +281,32 @@ int bddmma_smooth_solution(bddmma_solver* s, void* out, int on_device)
 {
     return guarded(s, [&](SolverBase* b) { return out ? b->smooth_solution(out, on_device) : BDDMMA_ERR_INVALID_ARGUMENT; });
 }
+int bddmma_grad_min_marginal_diff(bddmma_solver* s, const void* grad_mm, void* grad_lo_out, void* grad_hi_out, int on_device)
+{
+    return guarded(s, [&](SolverBase* b) {
+        return (grad_mm && grad_lo_out && grad_hi_out) ? b->grad_min_marginal_diff(grad_mm, grad_lo_out, grad_hi_out, on_device) : BDDMMA_ERR_INVALID_ARGUMENT;
+    });
+}
+int bddmma_grad_lower_bound_per_bdd(bddmma_solver* s, const void* grad_lb_per_bdd, void* grad_lo_out, void* grad_hi_out, int smooth, int on_device)
+{
+    return guarded(s, [&](SolverBase* b) {
+        return (grad_lb_per_bdd && grad_lo_out && grad_hi_out) ? b->grad_lower_bound_per_bdd(grad_lb_per_bdd, grad_lo_out, grad_hi_out, smooth, on_device)
+                                                               : BDDMMA_ERR_INVALID_ARGUMENT;
+    });
+}
+int bddmma_grad_distribute_delta(bddmma_solver* s, const void* grad_lo, const void* grad_hi, void* grad_deferred_mm_out, int on_device)
+{
+    return guarded(s, [&](SolverBase* b) {
+        return (grad_lo && grad_hi && grad_deferred_mm_out) ? b->grad_distribute_delta(grad_lo, grad_hi, grad_deferred_mm_out, on_device) : BDDMMA_ERR_INVALID_ARGUMENT;
+    });
+}
+int bddmma_grad_cost_perturbation(bddmma_solver* s, const void* grad_lo, const void* grad_hi, void* grad_lo_pert_out, void* grad_hi_pert_out, int on_device)
+{
+    return guarded(s, [&](SolverBase* b) {
+        return (grad_lo && grad_hi && grad_lo_pert_out && grad_hi_pert_out) ? b->grad_cost_perturbation(grad_lo, grad_hi, grad_lo_pert_out, grad_hi_pert_out, on_device)
+                                                                            : BDDMMA_ERR_INVALID_ARGUMENT;
+    });
+}
 int bddmma_bdds_solution(bddmma_solver* s, int sorted, char* sol, int on_device)
 {
     return guarded(s, [&](SolverBase* b) { return sol ? b->bdds_solution(sorted, sol, on_device) : BDDMMA_ERR_INVALID_ARGUMENT; });

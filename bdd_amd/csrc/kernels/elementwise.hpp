@@ -695,4 +695,50 @@ __global__ void k_smooth_solution(const REAL* __restrict__ sm_lo, const REAL* __
     out[i] = e_hi / (e_lo + e_hi);
 }
 
+// ---- the single-shot backward operators (SolverT::gr_*; bdd_cuda_learned_mma.cu:387-416, 1025-1187)
+// counts the values that are not finite (cnt[0]); the caller zeroes cnt
+template <typename REAL>
+__global__ void k_count_nonfinite(const REAL* __restrict__ v, uint32_t* __restrict__ cnt, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && !(v[i] > REAL(-__builtin_huge_val()) && v[i] < REAL(__builtin_huge_val()))) atomicAdd(cnt, 1u);   // NaN fails both tests
+}
+// grad_lower_bound_per_bdd (:387-416): the bound of a BDD is the cost of its solution x, so grad_hi = x * glb[bdd], grad_lo = (1 - x) * glb[bdd];
+// x is the arg-min path (char 0 / 1) or the smooth solution.  out_hi may be x itself (every thread reads its x first).
+template <typename REAL, typename XT>
+__global__ void k_grad_lb(const XT* x, const REAL* __restrict__ glb, const int32_t* __restrict__ layer_bdd, REAL* out_lo, REAL* out_hi, uint32_t n)
+{
+    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= n) return;
+    const REAL xl = REAL(x[l]), gb = glb[layer_bdd[l]];
+    out_hi[l] = xl * gb;
+    out_lo[l] = (REAL(1) - xl) * gb;
+}
+// grad_distribute_delta (:1025-1065): distribute_delta added the deferred difference m to hi where m > 0 and -m to lo otherwise
+template <typename REAL>
+__global__ void k_grad_distribute(const REAL* __restrict__ g_lo, const REAL* __restrict__ g_hi, const REAL* __restrict__ mm_binned,
+                                  const uint32_t* __restrict__ lpos, REAL* __restrict__ out, uint32_t n)
+{
+    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l < n) out[l] = mm_binned[lpos[l]] > REAL(0) ? g_hi[l] : -g_lo[l];
+}
+// grad_cost_perturbation (:1079-1102): update_costs gives every layer of variable v the share pert[v] / nr_bdds(v); one thread per variable
+// sums its layers in the order of the variable -> layer table
+template <typename REAL>
+__global__ void k_grad_perturb(const REAL* __restrict__ g_lo, const REAL* __restrict__ g_hi, const uint32_t* __restrict__ var_ptr,
+                               const uint32_t* __restrict__ var_layers, REAL* __restrict__ out_lo, REAL* __restrict__ out_hi, uint32_t n_vars)
+{
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_vars) return;
+    const uint32_t k0 = var_ptr[v], k1 = var_ptr[v + 1];
+    REAL s0 = 0, s1 = 0;
+    for (uint32_t k = k0; k < k1; ++k) {
+        s0 += g_lo[var_layers[k]];
+        s1 += g_hi[var_layers[k]];
+    }
+    const REAL nb = REAL(k1 > k0 ? k1 - k0 : 1u);
+    out_lo[v] = s0 / nb;
+    out_hi[v] = s1 / nb;
+}
+
 }  // namespace bddmma

@@ -96,6 +96,12 @@ struct SolverBase {
     // semiring; state contract in include/bdd_mma.h (bddmma_sum_marginals)
     virtual int sum_marginals(int sorted, int log_probs, int32_t* var, void* sm0, void* sm1, int on_device) = 0;
     virtual int smooth_solution(void* out, int on_device) = 0;
+    // the single-shot backward operators of bdd_cuda_learned_mma (bdd_cuda_learned_mma.h:82-110): transpose-Jacobian products with respect to
+    // the arc costs; arrays in layer order, state contracts in include/bdd_mma.h (bddmma_grad_*)
+    virtual int grad_min_marginal_diff(const void* grad_mm, void* grad_lo, void* grad_hi, int on_device) = 0;
+    virtual int grad_lower_bound_per_bdd(const void* grad_lb, void* grad_lo, void* grad_hi, int smooth, int on_device) = 0;
+    virtual int grad_distribute_delta(const void* grad_lo, const void* grad_hi, void* grad_deferred_mm, int on_device) = 0;
+    virtual int grad_cost_perturbation(const void* grad_lo, const void* grad_hi, void* grad_lo_pert, void* grad_hi_pert, int on_device) = 0;
     virtual int bdds_solution(int sorted, char* sol, int on_device) = 0;
     virtual int net_solver_costs(void* out, int on_device) = 0;
     virtual int make_dual_feasible(void* g, int on_device) = 0;

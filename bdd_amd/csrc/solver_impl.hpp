@@ -1479,6 +1479,11 @@ struct SolverT final : SolverBase {
     int distribute_delta() override
     {
         HIPCHK(hipSetDevice(device));
+        // what this call applies and clears is what bddmma_grad_distribute_delta reads afterwards: keep a copy
+        int rc;
+        if (!d_mm_consumed && (rc = dalloc(&d_mm_consumed, n_layers))) return rc;
+        HIPCHK(hipMemcpyAsync(d_mm_consumed, d_mm_binned, n_layers * sizeof(REAL), hipMemcpyDeviceToDevice, stream));
+        mm_consumed_valid = true;
         hipLaunchKernelGGL((k_distribute_delta<REAL>), dim3(cdiv(n_layers, 256)), dim3(256), 0, stream, d_lo, d_hi, d_mm_binned, d_lpos, (uint32_t)n_layers);
         x_layer_valid = false;
         HIPCHK(hipMemsetAsync(d_delta_var, 0, 2 * n_vars * sizeof(REAL), stream));  // bdd_cuda_base.cu:1428
@@ -1672,6 +1677,26 @@ struct SolverT final : SolverBase {
         return sm_sum_marginals(sorted, log_probs, var, sm0, sm1, on_device);
     }
     int smooth_solution(void* out, int on_device) override { return sm_smooth_solution(out, on_device); }
+    // Gradients (kernels/gradmm.hpp and three elementwise kernels).  Defined in solver_gr.hpp and instantiated in translation units of their
+    // own (solver_gr_f32.hip / solver_gr_f64.hip), as the sum-marginals are: only declared here.
+    int gr_prepare();       // first call: the parent tables (sm_prepare) and this operator's per-layer scratch
+    int gr_launch_down();   // root -> terminal: seeds, the gradient through T; one launch per pack family
+    int gr_launch_up();     // terminal -> root: the gradient through F
+    int gr_load(REAL* dst, const void* src, uint64_t n, int on_dev, const char* what);  // an incoming gradient -> the device, checked finite
+    int gr_min_marginal_diff(const void* grad_mm, void* grad_lo, void* grad_hi, int on_device);
+    int gr_lower_bound_per_bdd(const void* grad_lb, void* grad_lo, void* grad_hi, int smooth, int on_device);
+    int gr_distribute_delta(const void* grad_lo, const void* grad_hi, void* grad_deferred_mm, int on_device);
+    int gr_cost_perturbation(const void* grad_lo, const void* grad_hi, void* grad_lo_pert, void* grad_hi_pert, int on_device);
+    bool gr_ready = false;
+    REAL *d_gr_in0 = nullptr, *d_gr_in1 = nullptr;   // incoming gradients in layer order (L each; the per-BDD one fits as well: B <= L)
+    uint32_t* d_gr_arg = nullptr;                    // 2L: hop-local slot of the arg-min node of every layer's lo / hi arc (GR_NONE: no finite path)
+    unsigned char* d_gr_scratch = nullptr;           // huge packs: the gradient sweeps' per-pack arrays (gr_lds_bytes of the huge width each)
+    REAL* d_mm_consumed = nullptr;                   // L, binned entry order: the deferred differences the last distribute_delta() applied
+    bool mm_consumed_valid = false;
+    int grad_min_marginal_diff(const void* g, void* lo, void* hi, int on_device) override { return gr_min_marginal_diff(g, lo, hi, on_device); }
+    int grad_lower_bound_per_bdd(const void* g, void* lo, void* hi, int smooth, int on_device) override { return gr_lower_bound_per_bdd(g, lo, hi, smooth, on_device); }
+    int grad_distribute_delta(const void* lo, const void* hi, void* out, int on_device) override { return gr_distribute_delta(lo, hi, out, on_device); }
+    int grad_cost_perturbation(const void* lo, const void* hi, void* lo_p, void* hi_p, int on_device) override { return gr_cost_perturbation(lo, hi, lo_p, hi_p, on_device); }
     int min_marginal_diff(void* out, int on_device) override
     {
         HIPCHK(hipSetDevice(device));
@@ -1945,12 +1970,20 @@ struct SolverT final : SolverBase {
                 case 5: launch_bcast(d_delta_c, d_delta_lay_c); return BDDMMA_OK;
                 case 8: return sm_launch_fwd();
                 case 9: return sm_launch_bwd();
+                case 10: return gr_launch_down();
+                case 11: return gr_launch_up();
+                case 12: { const int r = gr_launch_down(); return r ? r : gr_launch_up(); }
                 default: err = "unknown kernel kind"; return BDDMMA_ERR_INVALID_ARGUMENT;
             }
         };
         if (kind == 6 || kind == 7) return time_stream(kind == 7, reps, ms);
         if ((kind == 8 || kind == 9) && (rc = sm_prepare())) return rc;
         if (kind == 9 && (rc = sm_launch_fwd())) return rc;  // the backward sum sweep reads the forward one's log-partition values
+        if (kind >= 10 && kind <= 12) {  // the gradient sweeps read the plain potentials, a gradient (zero here) and, upwards, the arg-min slots
+            if ((rc = gr_prepare()) || (rc = forward_run()) || (rc = backward_run())) return rc;
+            HIPCHK(hipMemsetAsync(d_gr_in0, 0, n_layers * sizeof(REAL), stream));
+            if (kind == 11 && (rc = gr_launch_down())) return rc;
+        }
         if ((rc = once())) return rc;  // warm-up
         HIPCHK(hipEventRecord(ev_t0, stream));
         for (uint64_t i = 0; i < reps; ++i)

@@ -366,6 +366,50 @@ class bdd_hip_parallel_mma:
         self._ck(self._L.bddmma_min_marginal_diff(self._h, _ptr(res), 0))
         return res
 
+    # ---- single-shot backward operators (bdd_cuda_learned_mma.h:82-110; state contracts: include/bdd_mma.h, bddmma_grad_*).  Inputs are NumPy
+    # arrays (results come back as NumPy arrays) or device buffers (then `out` must hold the device buffers the results go to).
+    def _grad_call(self, fn, ins, in_sizes, out, out_sizes, *flags):
+        if _is_dev(ins[0]):
+            assert out is not None and len(out) == len(out_sizes), "device inputs need device output buffers (out=...)"
+            args = [_dev_ptr(x, n, self.value_type) for x, n in zip(list(ins) + list(out), list(in_sizes) + list(out_sizes))]
+            self._ck(fn(self._h, *args, *flags, 1))
+            return out[0] if len(out) == 1 else tuple(out)
+        ins = [np.ascontiguousarray(x, dtype=self.value_type) for x in ins]
+        for x, n in zip(ins, in_sizes):
+            assert x.size == n, f"expected {n} values, got {x.size}"
+        res = [np.zeros(n, self.value_type) for n in out_sizes]
+        self._ck(fn(self._h, *(_ptr(x) for x in ins + res), *flags, 0))
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def grad_all_min_marginal_differences(self, grad_mm, out=None):
+        """(grad_lo, grad_hi): the transpose-Jacobian product of min_marginal_diff() with respect to the arc costs, per layer
+        (grad_mm_diff_all_hops, bdd_cuda_learned_mma.cu:623-1023); `out`: (grad_lo, grad_hi) device buffers"""
+        n = self.nr_layers()
+        return self._grad_call(self._L.bddmma_grad_min_marginal_diff, (grad_mm,), (n,), out, (n, n))
+
+    def grad_lower_bound_per_bdd(self, grad_lb_per_bdd, out=None):
+        """(grad_lo, grad_hi) of the per-BDD lower bounds weighted by grad_lb_per_bdd [nr_bdds] (bdd_cuda_learned_mma.cu:387-416)"""
+        n = self.nr_layers()
+        return self._grad_call(self._L.bddmma_grad_lower_bound_per_bdd, (grad_lb_per_bdd,), (self.nr_bdds(),), out, (n, n), 0)
+
+    def grad_smooth_lower_bound_per_bdd(self, grad_lb_per_bdd, out=None):
+        """the same for the smooth lower bound -log sum over paths of exp(-cost) per BDD: x is smooth_solution_per_bdd()"""
+        n = self.nr_layers()
+        return self._grad_call(self._L.bddmma_grad_lower_bound_per_bdd, (grad_lb_per_bdd,), (self.nr_bdds(),), out, (n, n), 1)
+
+    def grad_distribute_delta(self, grad_lo, grad_hi, out=None):
+        """gradient with respect to the deferred differences the last distribute_delta() applied (bdd_cuda_learned_mma.cu:1025-1065);
+        `out`: a device buffer (a 1-tuple of it is accepted too)"""
+        n = self.nr_layers()
+        if out is not None and not isinstance(out, (tuple, list)):
+            out = (out,)
+        return self._grad_call(self._L.bddmma_grad_distribute_delta, (grad_lo, grad_hi), (n, n), out, (n,))
+
+    def grad_cost_perturbation(self, grad_lo, grad_hi, out=None):
+        """(grad_lo_pert, grad_hi_pert) per variable: the backward of update_costs (bdd_cuda_learned_mma.cu:1067-1187)"""
+        n, v = self.nr_layers(), self.nr_variables()
+        return self._grad_call(self._L.bddmma_grad_cost_perturbation, (grad_lo, grad_hi), (n, n), out, (v, v))
+
     def bdds_solution_vec(self, out=None):
         if out is not None:   # device_vector<char> (bdd_cuda_base.cu:1138-1145)
             self._ck(self._L.bddmma_bdds_solution(self._h, 0, _dev_ptr(out, self.nr_layers(), np.int8), 1))

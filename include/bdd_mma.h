@@ -302,6 +302,47 @@ int bddmma_smooth_solution(bddmma_solver* s, void* out, int on_device);
  * layer order (sorted = 0) or (variable,bdd) order (sorted = 1, as bdds_solution(), :1204-1233). */
 int bddmma_bdds_solution(bddmma_solver* s, int sorted, char* sol, int on_device);
 
+/* ---- single-shot backward operators (bdd_cuda_learned_mma.h:82-110) ------ */
+/* Transpose-Jacobian products with respect to the arc costs.  Every layer-sized array is REAL[nr_layers] in the public layer order (that of
+ * bddmma_get_solver_costs, bddmma_min_marginal_diff and bddmma_bdds_solution(sorted = 0)), on the host or the device (on_device, one flag
+ * for all arrays of a call); inputs and outputs must not overlap.  A null pointer or a non-finite incoming gradient gives
+ * BDDMMA_ERR_INVALID_ARGUMENT and leaves the solver untouched.  No entry point changes arc costs, deferred differences or delta; all of
+ * them work with an L-BFGS wrapper attached.  Backpropagation through iterations (grad_iterations) is not provided. */
+/* grad_mm_diff_all_hops (bdd_cuda_learned_mma.cu:623-1023; grad_all_min_marginal_differences of the reference's Python module): the
+ * transpose-Jacobian product of bddmma_min_marginal_diff with respect to the current lo / hi arc costs, deferred differences NOT applied
+ * (as in the forward call).  With F the cost from the root, T the cost to the terminal and, per layer l and arc a,
+ * m_a[l] = min over the nodes u of l of F[u] + c_a[l] + T[child_a(u)], the result is
+ *   grad_lo / grad_hi = sum over l of grad_mm[l] * (chi(P_hi(l)) - chi(P_lo(l))),
+ * P_a(l) a minimum-cost root -> top path that takes arc a in layer l, chi its indicator over (layer, arc).  An arc no finite path takes
+ * contributes nothing.
+ * Tie rule: where a minimum is attained more than once the result is one valid subgradient, chosen by a fixed rule — lowest slot first
+ * among a layer's nodes (slot order is the node order of the BDD's layer in the layout), first in parent table order among the parents of
+ * a node (parents by slot, lo arc before hi arc), lo before hi between a node's two arcs.  The reference resolves ties by a race; agreement
+ * with it at ties is not a goal.  Every sum has a fixed order and nothing is accumulated atomically: two calls agree bit for bit.
+ * One launch per direction and pack family (csrc/kernels/gradmm.hpp).
+ * State contract: reads the stored costs from root and to terminal of the plain sweeps and recomputes whichever is invalid (also right
+ * after bddmma_sum_marginals, which overwrites both); both are valid on return.  Nothing else changes. */
+int bddmma_grad_min_marginal_diff(bddmma_solver* s, const void* grad_mm, void* grad_lo_out, void* grad_hi_out, int on_device);
+/* grad_lower_bound_per_bdd (bdd_cuda_learned_mma.cu:387-416; grad_lower_bound_per_bdd and grad_smooth_lower_bound_per_bdd of the Python
+ * module): grad_hi[l] = x[l] * grad_lb_per_bdd[bdd(l)], grad_lo[l] = (1 - x[l]) * grad_lb_per_bdd[bdd(l)]; grad_lb_per_bdd is
+ * REAL[nr_bdds] in the order of bddmma_lower_bound_per_bdd.  smooth = 0: x is bddmma_bdds_solution (0 / 1), the gradient of the per-BDD
+ * lower bound; state contract of bddmma_bdds_solution.  smooth != 0: x is bddmma_smooth_solution, the gradient of
+ * -log sum over paths of exp(-cost) per BDD; state contract of bddmma_sum_marginals. */
+int bddmma_grad_lower_bound_per_bdd(bddmma_solver* s, const void* grad_lb_per_bdd, void* grad_lo_out, void* grad_hi_out, int smooth, int on_device);
+/* grad_distribute_delta (bdd_cuda_learned_mma.cu:1025-1065): the backward of bddmma_distribute_delta with respect to the deferred
+ * differences it applied: out[l] = grad_hi[l] where that difference was > 0, else -grad_lo[l].  grad_lo / grad_hi pass through to the
+ * arc costs unchanged (identity Jacobian) and are not written.  The reference reads the deferred differences in place and so needs them
+ * preserved by the caller; here bddmma_distribute_delta clears them and keeps a copy of what it applied, which this call reads: it
+ * refers to the LAST bddmma_distribute_delta on this handle, whatever has run since, and returns BDDMMA_ERR_STATE when there was none
+ * (a handle restored from a checkpoint included).  Cost of that copy, paid by every caller of bddmma_distribute_delta: REAL[nr_layers] of
+ * device memory from the first such call on (counted by bddmma_device_bytes) and one device-to-device copy of it per call;
+ * bddmma_distribute_delta is not part of an iteration. */
+int bddmma_grad_distribute_delta(bddmma_solver* s, const void* grad_lo, const void* grad_hi, void* grad_deferred_mm_out, int on_device);
+/* grad_cost_perturbation (bdd_cuda_learned_mma.cu:1067-1187): the backward of bddmma_update_costs' isotropic distribution: outputs
+ * REAL[nr_variables], out[v] = (sum over the layers of v of grad[l]) / nr_bdds(v), summed in the order of the variable's layers by BDD.
+ * Reads no solver state besides the layout. */
+int bddmma_grad_cost_perturbation(bddmma_solver* s, const void* grad_lo, const void* grad_hi, void* grad_lo_pert_out, void* grad_hi_pert_out, int on_device);
+
 /* ---- L-BFGS support (lbfgs.h:22-27) --------------------------------------- */
 /* net_solver_costs() (bdd_cuda_parallel_mma.cu:432-463): hi - lo + deferred mm diff, REAL[nr_layers]. */
 int bddmma_net_solver_costs(const bddmma_solver* s, void* out, int on_device);
@@ -403,7 +444,7 @@ int bddmma_time_iterations(bddmma_solver* s, double omega, uint64_t n, double* m
 /* Time `reps` back-to-back launches of one kernel class with hipEvents on the handle's stream
  * (kernel-level benchmarking; leaves the sweep state invalid).  kind: 0 forward_run sweep, 1 backward_run
  * sweep, 2 forward_mm sweep, 3 backward_mm sweep, 4 exchange reduce, 5 exchange broadcast, 8 / 9 forward / backward sum-marginal
- * sweep (bddmma_sum_marginals), 6 STREAM triad
+ * sweep (bddmma_sum_marginals), 10 / 11 / 12 the root -> terminal / terminal -> root / both gradient sweeps (bddmma_grad_min_marginal_diff), 6 STREAM triad
  * a = b + s*c over three temporary arrays of BDDMMA_TRIAD_BYTES each (3 * BDDMMA_TRIAD_BYTES of HBM traffic
  * per launch), 7 STREAM copy a = b (2 * BDDMMA_TRIAD_BYTES per launch): the measured bandwidth ceilings of the
  * box the roofline is quoted next to. */
