@@ -1,10 +1,9 @@
 // solver_gr.hpp — the single-shot backward operators of the learned solver for SolverT<REAL> (bdd_cuda_learned_mma.h:82-110:
-// grad_mm_diff_all_hops, grad_lower_bound_per_bdd, grad_distribute_delta, grad_cost_perturbation): the launches of kernels/gradmm.hpp and
+// grad_mm_diff_all_hops, grad_lower_bound_per_bdd, grad_distribute_delta, grad_cost_perturbation): the two sweeps of kernels/gradmm.hpp and
 // the four entry points.  Included by solver_gr_f32.hip / solver_gr_f64.hip only, so that these kernels compile in translation units of
 // their own.  The parent tables are the sum-marginals' (SolverT::sm_prepare, defined in the solver_sm translation units).
 #pragma once
 #include "solver_impl.hpp"
-#include "kernels/summarg.hpp"
 #include "kernels/gradmm.hpp"
 
 namespace bddmma {
@@ -16,72 +15,43 @@ int SolverT<REAL>::gr_prepare()
     HIPCHK(hipSetDevice(device));
     int rc;
     if ((rc = sm_prepare())) return rc;
-    if (!d_gr_in0 && (rc = dalloc(&d_gr_in0, n_layers))) return rc;
+    if ((rc = gr_inputs(false))) return rc;
     if (!d_gr_arg && (rc = dalloc(&d_gr_arg, 2 * n_layers))) return rc;
     if (hb_.n_packs && !d_gr_scratch && (rc = dalloc(&d_gr_scratch, (uint64_t)hb_.n_packs * gr_lds_bytes(sizeof(REAL), huge_pack_width)))) return rc;
-    // dynamic LDS of the wide launches beyond the default limit
-    const uint32_t wl = (uint32_t)gr_lds_bytes(sizeof(REAL), wide_pack_width);
-    if (wb_.n_packs && wl > lds_cu) { err = "grad_min_marginal_diff: a wide pack does not fit the LDS"; return BDDMMA_ERR_UNSUPPORTED; }
-    if (wb_.n_packs && wl > 48 * 1024) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gr_down<REAL, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gr_up<REAL, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl));
-    }
+    if ((rc = pull_wide_lds("grad_min_marginal_diff", gr_down_sweep(), gr_up_sweep()))) return rc;
     gr_ready = true;
     return BDDMMA_OK;
 }
 
-// One kernel per pack family and direction, each a profiled group of its own (class BDDMMA_K_OTHER), as the sum-marginals' launches.
-// Both read d_gr_in0 (the incoming gradient) and write d_tmp0 / d_tmp1 (grad_lo / grad_hi); d_gr_arg goes from the first to the second.
 template <typename REAL>
-int SolverT<REAL>::gr_launch_down()
+int SolverT<REAL>::gr_inputs(bool second)
 {
-    const DevPtrs<REAL> d = ptrs(nullptr);
-    if (nb_.n_packs) {
-        prof_begin(BDDMMA_K_OTHER);
-        hipLaunchKernelGGL((k_gr_down<REAL, true, false>), dim3(nb_.n_packs), dim3(64), gr_lds_bytes(sizeof(REAL), pack_width), stream, d, pdev(nb_, 0), d_sm_nptr,
-                           d_sm_npar, pack_width, nullptr, (const REAL*)d_gr_in0, d_tmp0, d_tmp1, d_gr_arg);
-        prof_end(BDDMMA_K_OTHER);
-    }
-    if (wb_.n_packs) {
-        prof_begin(BDDMMA_K_OTHER);
-        hipLaunchKernelGGL((k_gr_down<REAL, false, false>), dim3(wb_.n_packs), dim3(WIDE_THREADS), gr_lds_bytes(sizeof(REAL), wide_pack_width), stream, d,
-                           pdev(wb_, nb_.n_packs), d_sm_wptr, d_sm_wpar, wide_pack_width, nullptr, (const REAL*)d_gr_in0, d_tmp0, d_tmp1, d_gr_arg);
-        prof_end(BDDMMA_K_OTHER);
-    }
-    if (hb_.n_packs) {
-        prof_begin(BDDMMA_K_OTHER);
-        hipLaunchKernelGGL((k_gr_down<REAL, false, true>), dim3(hb_.n_packs), dim3(WIDE_THREADS), 0, stream, d, pdev(hb_, nb_.n_packs + wb_.n_packs), d_sm_wptr,
-                           d_sm_wpar, huge_pack_width, d_gr_scratch, (const REAL*)d_gr_in0, d_tmp0, d_tmp1, d_gr_arg);
-        prof_end(BDDMMA_K_OTHER);
-    }
-    HIPCHK(hipGetLastError());
+    int rc;
+    if (!d_gr_in0 && (rc = dalloc(&d_gr_in0, n_layers))) return rc;
+    if (second && !d_gr_in1 && (rc = dalloc(&d_gr_in1, n_layers))) return rc;
     return BDDMMA_OK;
 }
 
+// Both sweeps read d_gr_in0 (the incoming gradient) and write d_tmp0 / d_tmp1 (grad_lo / grad_hi); d_gr_arg goes from the first to the second.
+template <typename REAL>
+PullSweep<REAL, const REAL*, REAL*, REAL*, uint32_t*> SolverT<REAL>::gr_down_sweep() const
+{
+    return {&k_gr_down<REAL, true, false>, &k_gr_down<REAL, false, false>, &k_gr_down<REAL, false, true>, &gr_lds_bytes, d_gr_scratch};
+}
+template <typename REAL>
+PullSweep<REAL, const REAL*, REAL*, REAL*, const uint32_t*> SolverT<REAL>::gr_up_sweep() const
+{
+    return {&k_gr_up<REAL, true, false>, &k_gr_up<REAL, false, false>, &k_gr_up<REAL, false, true>, &gr_lds_bytes, d_gr_scratch};
+}
+template <typename REAL>
+int SolverT<REAL>::gr_launch_down()
+{
+    return launch_pull(gr_down_sweep(), d_gr_in0, d_tmp0, d_tmp1, d_gr_arg);
+}
 template <typename REAL>
 int SolverT<REAL>::gr_launch_up()
 {
-    const DevPtrs<REAL> d = ptrs(nullptr);
-    if (nb_.n_packs) {
-        prof_begin(BDDMMA_K_OTHER);
-        hipLaunchKernelGGL((k_gr_up<REAL, true, false>), dim3(nb_.n_packs), dim3(64), gr_lds_bytes(sizeof(REAL), pack_width), stream, d, pdev(nb_, 0), d_sm_nptr,
-                           d_sm_npar, pack_width, nullptr, (const REAL*)d_gr_in0, d_tmp0, d_tmp1, (const uint32_t*)d_gr_arg);
-        prof_end(BDDMMA_K_OTHER);
-    }
-    if (wb_.n_packs) {
-        prof_begin(BDDMMA_K_OTHER);
-        hipLaunchKernelGGL((k_gr_up<REAL, false, false>), dim3(wb_.n_packs), dim3(WIDE_THREADS), gr_lds_bytes(sizeof(REAL), wide_pack_width), stream, d,
-                           pdev(wb_, nb_.n_packs), d_sm_wptr, d_sm_wpar, wide_pack_width, nullptr, (const REAL*)d_gr_in0, d_tmp0, d_tmp1, (const uint32_t*)d_gr_arg);
-        prof_end(BDDMMA_K_OTHER);
-    }
-    if (hb_.n_packs) {
-        prof_begin(BDDMMA_K_OTHER);
-        hipLaunchKernelGGL((k_gr_up<REAL, false, true>), dim3(hb_.n_packs), dim3(WIDE_THREADS), 0, stream, d, pdev(hb_, nb_.n_packs + wb_.n_packs), d_sm_wptr,
-                           d_sm_wpar, huge_pack_width, d_gr_scratch, (const REAL*)d_gr_in0, d_tmp0, d_tmp1, (const uint32_t*)d_gr_arg);
-        prof_end(BDDMMA_K_OTHER);
-    }
-    HIPCHK(hipGetLastError());
-    return BDDMMA_OK;
+    return launch_pull(gr_up_sweep(), d_gr_in0, d_tmp0, d_tmp1, d_gr_arg);
 }
 
 // An incoming gradient (n values) -> dst on the device; BDDMMA_ERR_INVALID_ARGUMENT when a value is not finite (host input: before anything
@@ -138,7 +108,7 @@ int SolverT<REAL>::gr_lower_bound_per_bdd(const void* grad_lb, void* grad_lo, vo
 {
     HIPCHK(hipSetDevice(device));
     int rc;
-    if (!d_gr_in0 && (rc = dalloc(&d_gr_in0, n_layers))) return rc;
+    if ((rc = gr_inputs(false))) return rc;
     // (the n_bdds values fit the layer-sized buffer: every BDD has at least one layer)
     if ((rc = gr_load(d_gr_in0, grad_lb, n_bdds, on_device, "grad_lower_bound_per_bdd: grad_lb_per_bdd"))) return rc;
     REAL* const lo = on_device ? (REAL*)grad_lo : d_tmp1;
@@ -174,8 +144,7 @@ int SolverT<REAL>::gr_distribute_delta(const void* grad_lo, const void* grad_hi,
         return BDDMMA_ERR_STATE;
     }
     int rc;
-    if (!d_gr_in0 && (rc = dalloc(&d_gr_in0, n_layers))) return rc;
-    if (!d_gr_in1 && (rc = dalloc(&d_gr_in1, n_layers))) return rc;
+    if ((rc = gr_inputs(true))) return rc;
     if ((rc = gr_load(d_gr_in0, grad_lo, n_layers, on_device, "grad_distribute_delta: grad_lo"))) return rc;
     if ((rc = gr_load(d_gr_in1, grad_hi, n_layers, on_device, "grad_distribute_delta: grad_hi"))) return rc;
     REAL* const dst = on_device ? (REAL*)grad_deferred_mm : d_tmp0;
@@ -192,8 +161,7 @@ int SolverT<REAL>::gr_cost_perturbation(const void* grad_lo, const void* grad_hi
 {
     HIPCHK(hipSetDevice(device));
     int rc;
-    if (!d_gr_in0 && (rc = dalloc(&d_gr_in0, n_layers))) return rc;
-    if (!d_gr_in1 && (rc = dalloc(&d_gr_in1, n_layers))) return rc;
+    if ((rc = gr_inputs(true))) return rc;
     if ((rc = gr_load(d_gr_in0, grad_lo, n_layers, on_device, "grad_cost_perturbation: grad_lo"))) return rc;
     if ((rc = gr_load(d_gr_in1, grad_hi, n_layers, on_device, "grad_cost_perturbation: grad_hi"))) return rc;
     REAL* const lo = on_device ? (REAL*)grad_lo_pert : d_delta_c;  // 2V scratch of the explicit forward_mm / backward_mm calls

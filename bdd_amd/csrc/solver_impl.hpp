@@ -58,6 +58,17 @@ decltype(auto) pick(uint32_t v, F&& f)
     else return v == (uint32_t)V0 ? f(std::integral_constant<int, V0>{}) : pick<Vs...>(v, static_cast<F&&>(f));
 }
 
+// A pull sweep (kernels/pull.hpp), described once: its kernel for the narrow, the wide and the huge packs (one function type: the leading
+// arguments of every pull kernel, then the sweep's own TAIL), the bytes of a pack's arrays by value size and pack width (the dynamic LDS
+// of the narrow and wide launches) and the huge packs' global scratch of that shape.  SolverT::launch_pull launches it.
+template <typename REAL, typename... TAIL>
+struct PullSweep {
+    using Fn = void (*)(DevPtrs<REAL>, PackDev, const uint32_t*, const uint32_t*, uint32_t, unsigned char*, TAIL...);
+    Fn narrow, wide, huge;
+    size_t (*bytes)(size_t, uint32_t);
+    unsigned char* scratch;
+};
+
 // ---------------------------------------------------------------------------------------------
 // accumulator type of the exchange kernel's LDS tile (kernels.hpp: k_exchange_reduce); experiments: -DBDDMMA_EX_ACC=REAL
 #ifndef BDDMMA_EX_ACC
@@ -1662,10 +1673,44 @@ struct SolverT final : SolverBase {
         HIPCHK(e);
         return BDDMMA_OK;
     }
+    // ---------------------------------------------------------------------------- the pull sweeps (kernels/pull.hpp)
+    // One launch per pack family, each a profiled group of its own (class BDDMMA_K_OTHER), so that the launch counts of bddmma_get_profile
+    // count these kernels.  The parent tables are the solver's (sm_prepare), the same for every sweep; `tail` = the sweep's own arguments.
+    template <typename... TAIL, typename... ARGS>
+    int launch_pull(const PullSweep<REAL, TAIL...>& s, ARGS... tail)
+    {
+        const DevPtrs<REAL> d = ptrs(nullptr);
+        auto family = [&](auto fn, const PackBufs& b, uint32_t lb_base, uint32_t threads, uint32_t ww, const uint32_t* ptr, const uint32_t* par, unsigned char* scratch) {
+            if (!b.n_packs) return;
+            prof_begin(BDDMMA_K_OTHER);
+            hipLaunchKernelGGL(fn, dim3(b.n_packs), dim3(threads), scratch ? 0 : s.bytes(sizeof(REAL), ww), stream, d, pdev(b, lb_base), ptr, par, ww, scratch, tail...);
+            prof_end(BDDMMA_K_OTHER);
+        };
+        family(s.narrow, nb_, 0, 64, pack_width, d_sm_nptr, d_sm_npar, nullptr);
+        family(s.wide, wb_, nb_.n_packs, WIDE_THREADS, wide_pack_width, d_sm_wptr, d_sm_wpar, nullptr);
+        family(s.huge, hb_, nb_.n_packs + wb_.n_packs, WIDE_THREADS, huge_pack_width, d_sm_wptr, d_sm_wpar, s.scratch);
+        HIPCHK(hipGetLastError());
+        return BDDMMA_OK;
+    }
+    // The wide launches of an operator's two sweeps (they share their bytes per pack): an error where a wide pack does not fit the LDS, the
+    // launch attribute where its dynamic LDS is beyond the default limit.  Not through raise_lds_limit(): that sets the attribute for every
+    // size but zero, and these kernels have always been launched without it up to 48 KiB.
+    template <typename... A, typename... B>
+    int pull_wide_lds(const char* what, const PullSweep<REAL, A...>& a, const PullSweep<REAL, B...>& b)
+    {
+        const uint32_t wl = (uint32_t)a.bytes(sizeof(REAL), wide_pack_width);
+        if (wb_.n_packs && wl > lds_cu) { err = std::string(what) + ": a wide pack does not fit the LDS"; return BDDMMA_ERR_UNSUPPORTED; }
+        if (wb_.n_packs && wl > 48 * 1024) {
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(a.wide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl));
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(b.wide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl));
+        }
+        return BDDMMA_OK;
+    }
     // Sum-marginals (kernels/summarg.hpp).  Defined in solver_sm.hpp and instantiated in translation units of their own (solver_sm_f32.hip /
     // solver_sm_f64.hip), as the OV sweeps are: only declared here.
+    PullSweep<REAL> sm_fwd_sweep() const, sm_bwd_sweep() const;
     int sm_prepare();       // first call: the parent tables of the forward pull, derived from the node words
-    int sm_launch_fwd();    // one launch per pack family
+    int sm_launch_fwd();    // launch_pull of the sweep, and what it does to the solver's state
     int sm_launch_bwd();
     int sm_sum_marginals(int sorted, int log_probs, int32_t* var, void* sm0, void* sm1, int on_device);
     int sm_smooth_solution(void* out, int on_device);
@@ -1679,8 +1724,11 @@ struct SolverT final : SolverBase {
     int smooth_solution(void* out, int on_device) override { return sm_smooth_solution(out, on_device); }
     // Gradients (kernels/gradmm.hpp and three elementwise kernels).  Defined in solver_gr.hpp and instantiated in translation units of their
     // own (solver_gr_f32.hip / solver_gr_f64.hip), as the sum-marginals are: only declared here.
+    PullSweep<REAL, const REAL*, REAL*, REAL*, uint32_t*> gr_down_sweep() const;
+    PullSweep<REAL, const REAL*, REAL*, REAL*, const uint32_t*> gr_up_sweep() const;
     int gr_prepare();       // first call: the parent tables (sm_prepare) and this operator's per-layer scratch
-    int gr_launch_down();   // root -> terminal: seeds, the gradient through T; one launch per pack family
+    int gr_inputs(bool second);  // d_gr_in0 and, for the operators that take two gradients, d_gr_in1: allocated on first use
+    int gr_launch_down();   // root -> terminal: seeds, the gradient through T
     int gr_launch_up();     // terminal -> root: the gradient through F
     int gr_load(REAL* dst, const void* src, uint64_t n, int on_dev, const char* what);  // an incoming gradient -> the device, checked finite
     int gr_min_marginal_diff(const void* grad_mm, void* grad_lo, void* grad_hi, int on_device);

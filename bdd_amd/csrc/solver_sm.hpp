@@ -1,5 +1,5 @@
 // solver_sm.hpp — sum-marginals and the smooth solution for SolverT<REAL> (bdd_cuda_base.cu:788-1064: sum_marginals_cuda,
-// smooth_solution_cuda): the parent tables of the forward pull, the launches of kernels/summarg.hpp and the two entry points.  Included
+// smooth_solution_cuda): the parent tables of the pull sweeps, the two sweeps of kernels/summarg.hpp and the two entry points.  Included
 // by solver_sm_f32.hip / solver_sm_f64.hip only, so that these kernels compile in translation units of their own.
 #pragma once
 #include "solver_impl.hpp"
@@ -7,7 +7,7 @@
 
 namespace bddmma {
 
-// Parents of every node, by word index (kernels/summarg.hpp: k_sm_fwd): the children of a node are slots of the next hop of its pack, so
+// Parents of every node, by word index (kernels/pull.hpp: pull_parents): the children of a node are slots of the next hop of its pack, so
 // the parents of slot c of hop q + 1 are the nodes of hop q that name c, in slot order, lo arc before hi arc.  `word_of(p)` = word index
 // of the first slot of pack p of a set; packs that share a word sequence (narrow packs of one structure) share their part of the table.
 // One table may cover several pack sets (wide and huge packs share wwords).
@@ -115,42 +115,26 @@ int SolverT<REAL>::sm_prepare()
         HIPCHK(hipStreamSynchronize(stream));
     }
     if (hb_.n_packs && (rc = dalloc(&d_sm_scratch, (uint64_t)hb_.n_packs * sm_lds_bytes(sizeof(REAL), huge_pack_width)))) return rc;
-    // dynamic LDS of the wide launches beyond the default limit
-    const uint32_t wl = (uint32_t)sm_lds_bytes(sizeof(REAL), wide_pack_width);
-    if (wb_.n_packs && wl > lds_cu) { err = "sum-marginals: a wide pack does not fit the LDS"; return BDDMMA_ERR_UNSUPPORTED; }
-    if (wb_.n_packs && wl > 48 * 1024) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sm_fwd<REAL, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sm_bwd<REAL, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl));
-    }
+    if ((rc = pull_wide_lds("sum-marginals", sm_fwd_sweep(), sm_bwd_sweep()))) return rc;
     sm_ready = true;
     return BDDMMA_OK;
 }
 
-// One kernel per pack family and direction.  Each launch is a profiled group of its own (class BDDMMA_K_OTHER), so that the launch counts of
-// bddmma_get_profile count these kernels.
+template <typename REAL>
+PullSweep<REAL> SolverT<REAL>::sm_fwd_sweep() const
+{
+    return {&k_sm_fwd<REAL, true, false>, &k_sm_fwd<REAL, false, false>, &k_sm_fwd<REAL, false, true>, &sm_lds_bytes, d_sm_scratch};
+}
+template <typename REAL>
+PullSweep<REAL> SolverT<REAL>::sm_bwd_sweep() const
+{
+    return {&k_sm_bwd<REAL, true, false>, &k_sm_bwd<REAL, false, false>, &k_sm_bwd<REAL, false, true>, &sm_lds_bytes, d_sm_scratch};
+}
+
 template <typename REAL>
 int SolverT<REAL>::sm_launch_fwd()
 {
-    const DevPtrs<REAL> d = ptrs(nullptr);
-    if (nb_.n_packs) {
-        prof_begin(BDDMMA_K_OTHER);
-        hipLaunchKernelGGL((k_sm_fwd<REAL, true, false>), dim3(nb_.n_packs), dim3(64), sm_lds_bytes(sizeof(REAL), pack_width), stream, d, pdev(nb_, 0), d_sm_nptr,
-                           d_sm_npar, pack_width, nullptr);
-        prof_end(BDDMMA_K_OTHER);
-    }
-    if (wb_.n_packs) {
-        prof_begin(BDDMMA_K_OTHER);
-        hipLaunchKernelGGL((k_sm_fwd<REAL, false, false>), dim3(wb_.n_packs), dim3(WIDE_THREADS), sm_lds_bytes(sizeof(REAL), wide_pack_width), stream, d,
-                           pdev(wb_, nb_.n_packs), d_sm_wptr, d_sm_wpar, wide_pack_width, nullptr);
-        prof_end(BDDMMA_K_OTHER);
-    }
-    if (hb_.n_packs) {
-        prof_begin(BDDMMA_K_OTHER);
-        hipLaunchKernelGGL((k_sm_fwd<REAL, false, true>), dim3(hb_.n_packs), dim3(WIDE_THREADS), 0, stream, d, pdev(hb_, nb_.n_packs + wb_.n_packs), d_sm_wptr,
-                           d_sm_wpar, huge_pack_width, d_sm_scratch);
-        prof_end(BDDMMA_K_OTHER);
-    }
-    HIPCHK(hipGetLastError());
+    if (int rc = launch_pull(sm_fwd_sweep())) return rc;
     fwd_valid = false;  // the stored costs from root are log-partition values now
     return BDDMMA_OK;
 }
@@ -161,27 +145,7 @@ int SolverT<REAL>::sm_launch_bwd()
     bwd_valid = false;  // ... and the costs from terminal; the cached bound goes with them (flush_backward_states, bdd_cuda_base.cu:1011)
     lb_cached = false;
     ++lb_gen;
-    const DevPtrs<REAL> d = ptrs(nullptr);
-    if (nb_.n_packs) {
-        prof_begin(BDDMMA_K_OTHER);
-        hipLaunchKernelGGL((k_sm_bwd<REAL, true, false>), dim3(nb_.n_packs), dim3(64), sm_lds_bytes(sizeof(REAL), pack_width), stream, d, pdev(nb_, 0), pack_width,
-                           nullptr);
-        prof_end(BDDMMA_K_OTHER);
-    }
-    if (wb_.n_packs) {
-        prof_begin(BDDMMA_K_OTHER);
-        hipLaunchKernelGGL((k_sm_bwd<REAL, false, false>), dim3(wb_.n_packs), dim3(WIDE_THREADS), sm_lds_bytes(sizeof(REAL), wide_pack_width), stream, d,
-                           pdev(wb_, nb_.n_packs), wide_pack_width, nullptr);
-        prof_end(BDDMMA_K_OTHER);
-    }
-    if (hb_.n_packs) {
-        prof_begin(BDDMMA_K_OTHER);
-        hipLaunchKernelGGL((k_sm_bwd<REAL, false, true>), dim3(hb_.n_packs), dim3(WIDE_THREADS), 0, stream, d, pdev(hb_, nb_.n_packs + wb_.n_packs), huge_pack_width,
-                           d_sm_scratch);
-        prof_end(BDDMMA_K_OTHER);
-    }
-    HIPCHK(hipGetLastError());
-    return BDDMMA_OK;
+    return launch_pull(sm_bwd_sweep());
 }
 
 template <typename REAL>

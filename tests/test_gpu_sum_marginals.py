@@ -36,6 +36,12 @@ def _split():
     return col, pad_costs(np.asarray(ilp.objective, np.float64), col.nr_variables())
 
 
+# What reaches the two levels of the layer folds (kernels/pull.hpp: pull_layer_fold, runs of 16 slots), from the layouts alone: a layer that
+# spans more than one run, so that its head folds several runs, and a run that starts at a multiple of 16 that is no layer head.
+#   narrow packs  knapsack_w64 only (2 packs, widest layer 29 slots, 14 such run starts; a layer has at most 2 runs) — every other
+#                 family's narrow packs hold covering / equality rows, whose layers have at most 2 nodes;
+#   wide packs    wide2 / mixed (6 packs, widest layer 152 slots, 185 such run starts, up to 10 runs a layer), huge (1 pack, 180 slots);
+#   huge packs    huge (1 pack, widest layer 7 843 slots, 2 191 such run starts, up to 491 runs a layer).
 FAMILIES = {
     "cover10_w64": (_cover10_small, dict(pack_width=64)),
     "cover10_w128": (_cover10_small, dict(pack_width=128)),
@@ -43,6 +49,7 @@ FAMILIES = {
     "wide2": (_wide, dict(pack_width=64, wide_pack_width=512, resident_sweeps=1, variant_flags=0x3)),
     "mixed": (_wide, dict(pack_width=64, wide_pack_width=512, resident_sweeps=1)),
     "huge": (_huge, dict()),
+    "knapsack_w64": (_knapsack_rows, dict(pack_width=64)),
     "assignment8": (_assignment8, dict()),
     "staggered_rows": (_mixed_rows, dict()),
     "split_bdds": (_split, dict()),

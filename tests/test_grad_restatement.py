@@ -15,8 +15,8 @@ from test_sum_marginals_restatement import INSTANCES
 
 # the seed of tie_free_state() per family of test_gpu_sum_marginals.FAMILIES: the first one for which tie_free() holds in both precisions
 # (decided by the restatement alone; test_gpu_fixtures_are_tie_free asserts it)
-SEEDS = {"assignment8": 1, "cover10_w64": 5, "cover10_w128": 5, "cover10_w256": 5, "huge": 1, "mixed": 2, "split_bdds": 1, "staggered_rows": 1,
-         "wide2": 2}
+SEEDS = {"assignment8": 1, "cover10_w64": 5, "cover10_w128": 5, "cover10_w256": 5, "huge": 1, "knapsack_w64": 1, "mixed": 2, "split_bdds": 1,
+         "staggered_rows": 1, "wide2": 2}
 
 
 def _model(name, seed=7):

@@ -1,6 +1,8 @@
 """Timing of the backward operator of the min-marginal differences (bddmma_grad_min_marginal_diff) next to sum-marginals, the closest
 existing pair of pull sweeps over the parent tables, on the benchmark's default instance (10.5 M nodes), both precisions.
-  python tools/grad_time.py [--out FILE]        on an MI355X
+  python tools/grad_time.py [--out FILE] [--label TEXT --append]        on an MI355X
+(--label names the run in its first line and --append adds it to FILE: the rounds of two builds of the library, chosen with BDDMMA_LIB, side
+by side in one file)
 Per precision, after 3 warm-up calls of each entry point: hipEvents around 20 repetitions (bddmma_time_kernel) of the two gradient
 launches (kinds 10 / 11, and 12 = both back to back) and of the two sum sweeps (kinds 8 / 9); the ratio is (gradient pair) / (sum pair).
 Whole calls into device buffers (host wall clock, synchronous: they include the plain sweeps a call recomputes, the copy and the finiteness
@@ -54,10 +56,13 @@ def run(precision, out):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grad_time.txt"))
+    ap.add_argument("--label", default="")
+    ap.add_argument("--append", action="store_true")
     a = ap.parse_args()
-    lines = ["bddmma_grad_min_marginal_diff against bddmma_sum_marginals on one MI355X — written by tools/grad_time.py (see its docstring).", ""]
+    lines = [f"{a.label + ': ' if a.label else ''}bddmma_grad_min_marginal_diff against bddmma_sum_marginals on one MI355X — written by tools/grad_time.py "
+             "(see its docstring).", ""]
     for p in ("float", "double"):
         run(p, lines)
-    with open(a.out, "w") as f:
+    with open(a.out, "a" if a.append else "w") as f:
         f.write("\n".join(lines) + "\n")
     print("\n".join(lines))
