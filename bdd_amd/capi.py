@@ -102,6 +102,7 @@ SIGNATURES = {
     "bddmma_grad_lower_bound_per_bdd": (_I, [_V, _V, _V, _V, _I, _I]),
     "bddmma_grad_distribute_delta": (_I, [_V, _V, _V, _V, _I]),
     "bddmma_grad_cost_perturbation": (_I, [_V, _V, _V, _V, _V, _I]),
+    "bddmma_grad_learned_iterations": (_I, [_V, _V, _I, _D, _V, _I, _V, _V, _V, _V, _V, _U64, _U64, _U64, _I]),
     "bddmma_bdds_solution": (_I, [_V, _I, _V, _I]),
     "bddmma_net_solver_costs": (_I, [_V, _V, _I]),
     "bddmma_make_dual_feasible": (_I, [_V, _V, _I]),

@@ -345,6 +345,18 @@ class bdd_hip_parallel_mma {
     {
         check(bddmma_grad_cost_perturbation(h_, dev_grad_lo, dev_grad_hi, dev_grad_lo_pert_out, dev_grad_hi_pert_out, 1));
     }
+    // grad_iterations(dist_weights, grad_lo_cost, grad_hi_cost, grad_mm, grad_dist_weights_out, grad_omega, omega_scalar, track_grad_after_itr,
+    // track_grad_for_num_itr, num_caches, omega_vec) (:308-385): device arrays; grad_lo / grad_hi / grad_mm in-out, grad_omega of one entry
+    // (nr_layers() with omega_vec).  Contract: bddmma_grad_learned_iterations.
+    void grad_iterations(const REAL* dev_dist_weights, REAL* dev_grad_lo, REAL* dev_grad_hi, REAL* dev_grad_mm, REAL* dev_grad_dist_weights_out,
+                         REAL* dev_grad_omega, REAL omega_scalar, int track_grad_after_itr, int track_grad_for_num_itr, int num_caches,
+                         const REAL* dev_omega_vec = nullptr)
+    {
+        if (track_grad_after_itr < 0 || track_grad_for_num_itr < 0 || num_caches < 0) throw std::invalid_argument("grad_iterations: negative count");
+        check(bddmma_grad_learned_iterations(h_, dev_dist_weights, 1, (double)omega_scalar, dev_omega_vec, 1, dev_grad_lo, dev_grad_hi, dev_grad_mm,
+                                             dev_grad_dist_weights_out, dev_grad_omega, (uint64_t)track_grad_after_itr, (uint64_t)track_grad_for_num_itr,
+                                             (uint64_t)num_caches, 1));
+    }
     // the same four on host vectors: {grad_lo, grad_hi} / grad_deferred_mm / {grad_lo_pert, grad_hi_pert}
     std::pair<std::vector<REAL>, std::vector<REAL>> grad_mm_diff_all_hops(const std::vector<REAL>& grad_mm)
     {

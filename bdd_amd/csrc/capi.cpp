@@ -300,6 +300,15 @@ int bddmma_grad_distribute_delta(bddmma_solver* s, const void* grad_lo, const vo
         return (grad_lo && grad_hi && grad_deferred_mm_out) ? b->grad_distribute_delta(grad_lo, grad_hi, grad_deferred_mm_out, on_device) : BDDMMA_ERR_INVALID_ARGUMENT;
     });
 }
+int bddmma_grad_learned_iterations(bddmma_solver* s, const void* dist_weights, int weights_on_device, double omega, const void* omega_vec,
+                                   int omega_vec_on_device, void* grad_lo, void* grad_hi, void* grad_mm, void* grad_dist_weights_out, void* grad_omega_out,
+                                   uint64_t track_grad_after_itr, uint64_t track_grad_for_num_itr, uint64_t num_caches, int on_device)
+{
+    return guarded(s, [&](SolverBase* b) {
+        return b->grad_learned_iterations(dist_weights, weights_on_device, omega, omega_vec, omega_vec_on_device, grad_lo, grad_hi, grad_mm,
+                                          grad_dist_weights_out, grad_omega_out, track_grad_after_itr, track_grad_for_num_itr, num_caches, on_device);
+    });
+}
 int bddmma_grad_cost_perturbation(bddmma_solver* s, const void* grad_lo, const void* grad_hi, void* grad_lo_pert_out, void* grad_hi_pert_out, int on_device)
 {
     return guarded(s, [&](SolverBase* b) {

@@ -209,6 +209,20 @@ PYBIND11_MODULE(bdd_solver_py, m)
         // bdd_cuda_parallel_mma_py.cu:56-72: hi - lo min-marginal of every layer into a caller-owned DEVICE buffer (REAL[nr_layers])
         .def("compute_and_set_min_marginal_diff",
              [](hip_solver& s, uint64_t mm_diff_out_ptr) { ck(bddmma_min_marginal_diff(s.h, reinterpret_cast<void*>(mm_diff_out_ptr), 1), s.h); })
+        // grad_iterations of the learned solver (bdd_cuda_learned_mma.cu:308-385) on caller-owned DEVICE buffers given as addresses: grad_lo /
+        // grad_hi / grad_mm REAL[nr_layers] in-out, grad_omega REAL[1] (REAL[nr_layers] with omega_vec); include/bdd_mma.h, bddmma_grad_learned_iterations
+        .def("grad_iterations",
+             [](hip_solver& s, uint64_t dist_weights_ptr, uint64_t grad_lo_ptr, uint64_t grad_hi_ptr, uint64_t grad_mm_ptr, uint64_t grad_dist_weights_out_ptr,
+                uint64_t grad_omega_ptr, double omega, uint64_t track_grad_after_itr, uint64_t track_grad_for_num_itr, uint64_t num_caches, uint64_t omega_vec_ptr) {
+                 ck(bddmma_grad_learned_iterations(s.h, reinterpret_cast<const void*>(dist_weights_ptr), 1, omega, reinterpret_cast<const void*>(omega_vec_ptr), 1,
+                                                   reinterpret_cast<void*>(grad_lo_ptr), reinterpret_cast<void*>(grad_hi_ptr), reinterpret_cast<void*>(grad_mm_ptr),
+                                                   reinterpret_cast<void*>(grad_dist_weights_out_ptr), reinterpret_cast<void*>(grad_omega_ptr),
+                                                   track_grad_after_itr, track_grad_for_num_itr, num_caches, 1),
+                    s.h);
+             },
+             py::arg("dist_weights_ptr"), py::arg("grad_lo_ptr"), py::arg("grad_hi_ptr"), py::arg("grad_mm_ptr"), py::arg("grad_dist_weights_out_ptr"),
+             py::arg("grad_omega_ptr"), py::arg("omega") = 0.5, py::arg("track_grad_after_itr") = 0, py::arg("track_grad_for_num_itr") = 1,
+             py::arg("num_caches") = 1, py::arg("omega_vec_ptr") = 0)
         // the same into a new host list (no counterpart in the reference; convenient without a device buffer)
         .def("min_marginal_diff", [](hip_solver& s) {
             const size_t L = bddmma_nr_layers(s.h);

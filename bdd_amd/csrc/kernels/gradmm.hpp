@@ -26,10 +26,54 @@
 namespace bddmma {
 
 constexpr uint32_t GR_NONE = 0xFFFFFFFFu;
+
 // LDS of a pack of width ww: down 6 arrays of values + 3 of indices, up 6 + 2.  In float that is 36 bytes per slot against the 32 of
 // sm_lds_bytes (double: 60 against 60), so a wide pack width that the sum-marginals just fit (above lds_cu / 36 slots, 4 551 at 160 KiB)
 // is refused here with BDDMMA_ERR_UNSUPPORTED (SolverT::gr_prepare); the default wide pack width is 2 048 slots.
 __host__ __device__ inline size_t gr_lds_bytes(size_t real_size, uint32_t ww) { return (6 * real_size + 12) * (size_t)ww; }
+
+// ---- the steps of a hop that every sweep carrying dT or dF shares (the two kernels here and those of kernels/graditer.hpp): the tie rules
+// of the routing are written here and nowhere else.
+// T of a child: 0 at the top sink, inf at the bottom sink
+template <typename REAL>
+__device__ __forceinline__ REAL gr_child_T(const REAL* __restrict__ T, uint32_t nbn, uint32_t c)
+{
+    return c == PULL_BOT ? inf_v<REAL>() : (c == PULL_TOP ? REAL(0) : T[nbn + c]);
+}
+// Down: slot j's dT = dt0 + what its parents sent (parent table order; `pull` false: a root, nobody sends), and it leaves along the arc of
+// the smaller of a (lo) and b (hi), lo before hi: Sc[arc][j] = dT, the other arc 0.
+template <typename REAL>
+__device__ __forceinline__ void gr_send_down(const uint32_t* par_ptr, const uint32_t* par, uint32_t wi, bool pull, const REAL* Sp, REAL* Sc, uint32_t ww,
+                                             uint32_t j, REAL dt0, REAL a, REAL b)
+{
+    REAL dt = dt0;
+    if (pull) pull_parents(par_ptr, par, wi, [&](uint32_t slot, uint32_t arc) { dt += Sp[(size_t)arc * ww + slot]; });
+    const bool lo_arc = a <= b;  // lo before hi
+    Sc[j] = lo_arc ? dt : REAL(0);
+    Sc[ww + j] = lo_arc ? REAL(0) : dt;
+}
+// Up: the nn children (word index w0 + c) publish their arg-min (parent, arc) over V0 / V1 = F + cost of the lo / hi arc per slot of this
+// hop: AP[c] = slot << 1 | arc; first in parent table order wins a tie; a root or an unreachable node names nobody (GR_NONE).
+template <typename REAL>
+__device__ __forceinline__ void gr_name_parents(const PullPack<REAL>& pc, const uint32_t* par_ptr, const uint32_t* par, uint32_t w0, uint32_t nn, const REAL* V0,
+                                                const REAL* V1, uint32_t* AP)
+{
+    for (uint32_t c = pc.tid; c < nn; c += pc.T) {
+        REAL m = inf_v<REAL>();
+        uint32_t best = GR_NONE;
+        pull_parents(par_ptr, par, w0 + c, [&](uint32_t slot, uint32_t arc) {
+            const REAL v = arc ? V1[slot] : V0[slot];
+            if (v < m) { m = v; best = (slot << 1) | arc; }
+        });
+        AP[c] = best;
+    }
+}
+// ... and slot j takes dF (Dn) of each child that names it: {over its lo arc, over its hi arc}
+template <typename REAL>
+__device__ __forceinline__ Pull2<REAL> gr_take_up(const PullNode& nd, uint32_t j, uint32_t nn, const uint32_t* AP, const REAL* Dn)
+{
+    return {(nd.lo < nn && AP[nd.lo] == (j << 1)) ? Dn[nd.lo] : REAL(0), (nd.hi < nn && AP[nd.hi] == ((j << 1) | 1u)) ? Dn[nd.hi] : REAL(0)};
+}
 
 template <typename REAL, bool NARROW, bool GLOBAL>
 __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gr_down(DevPtrs<REAL> d, PackDev pk, const uint32_t* par_ptr, const uint32_t* par, uint32_t ww,
@@ -54,17 +98,11 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gr_down(DevPtrs<
         const REAL* const Sp = S + (size_t)(cur ^ 1u) * 2 * ww;
         // ---- pull dT, path values, what goes down each arc
         pull_slots<REAL, NARROW, true>(d, pc, nb, n, lbase, Lid, [&](uint32_t j, uint32_t wi, const PullNode& nd) {
-            REAL dt = REAL(0);
-            if (!(q == pc.q0 || j == rt)) pull_parents(par_ptr, par, wi, [&](uint32_t slot, uint32_t arc) { dt += Sp[(size_t)arc * ww + slot]; });
-            const REAL tl = nd.lo == PULL_BOT ? INF : (nd.lo == PULL_TOP ? REAL(0) : d.T[nbn + nd.lo]);
-            const REAL th = nd.hi == PULL_BOT ? INF : (nd.hi == PULL_TOP ? REAL(0) : d.T[nbn + nd.hi]);
-            const REAL a = d.lohi[2 * (size_t)nd.layer] + tl, b = d.lohi[2 * (size_t)nd.layer + 1] + th;
+            const REAL a = d.lohi[2 * (size_t)nd.layer] + gr_child_T(d.T, nbn, nd.lo), b = d.lohi[2 * (size_t)nd.layer + 1] + gr_child_T(d.T, nbn, nd.hi);
             const REAL f = d.F[nb + j];
             P0[j] = f + a;
             P1[j] = f + b;
-            const bool lo_arc = a <= b;  // lo before hi
-            Sc[j] = lo_arc ? dt : REAL(0);
-            Sc[ww + j] = lo_arc ? REAL(0) : dt;
+            gr_send_down(par_ptr, par, wi, !(q == pc.q0 || j == rt), Sp, Sc, ww, j, REAL(0), a, b);
         });
         __syncthreads();
         // ---- arg-min per layer and arc (strictly smaller replaces, in the runs and among them: the lowest slot wins a tie)
@@ -105,7 +143,6 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gr_up(DevPtrs<RE
     REAL* const Q1 = pc.base + 5 * (size_t)ww;
     uint32_t* const AP = reinterpret_cast<uint32_t*>(pc.base + 6 * (size_t)ww);  // per slot of the hop below: its arg-min parent << 1 | arc, GR_NONE
     uint32_t* const Lid = AP + ww;
-    const REAL INF = inf_v<REAL>();
     uint32_t cur = 0;
     for (uint32_t q = pc.q1; q-- > pc.q0; cur ^= 1u) {
         const uint32_t nb = pk.hop_node_off[q], n = pk.hop_node_off[q + 1] - nb, lbase = pk.hop_layer_off[q];
@@ -120,20 +157,12 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gr_up(DevPtrs<RE
         });
         __syncthreads();
         // ---- the children's arg-min (parent, arc): first in parent table order wins a tie; a root or an unreachable node names nobody
-        for (uint32_t c = pc.tid; c < nn; c += pc.T) {
-            REAL m = INF;
-            uint32_t best = GR_NONE;
-            pull_parents(par_ptr, par, nb + n + c + pc.wdelta, [&](uint32_t slot, uint32_t arc) {
-                const REAL v = arc ? V1[slot] : V0[slot];
-                if (v < m) { m = v; best = (slot << 1) | arc; }
-            });
-            AP[c] = best;
-        }
+        gr_name_parents(pc, par_ptr, par, nb + n + pc.wdelta, nn, V0, V1, AP);
         __syncthreads();
         // ---- dF = seeds + dF of the children that name this node
         pull_slots<REAL, NARROW, false>(d, pc, nb, n, lbase, nullptr, [&](uint32_t j, uint32_t, const PullNode& nd) {
-            const REAL t0 = (nd.lo < nn && AP[nd.lo] == (j << 1)) ? Dn[nd.lo] : REAL(0);
-            const REAL t1 = (nd.hi < nn && AP[nd.hi] == ((j << 1) | 1u)) ? Dn[nd.hi] : REAL(0);
+            const Pull2<REAL> t = gr_take_up(nd, j, nn, AP, Dn);
+            const REAL t0 = t.lo, t1 = t.hi;
             REAL df = t0 + t1;
             const uint32_t a0 = arg[2 * (size_t)nd.layer], a1 = arg[2 * (size_t)nd.layer + 1];
             if (a0 == j || a1 == j) {

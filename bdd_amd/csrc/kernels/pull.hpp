@@ -21,6 +21,28 @@ struct PullNode {
 };
 // Node j of a hop: NARROW — the 64 lanes of the (one-wave) workgroup decode 64 consecutive slots together; `lgrp` is the first layer of
 // that lane group and is advanced by the group's layer count (load_layer, kernels/narrow.hpp).  Wide / huge: the word holds everything.
+// The children of a node word as slots of the next hop, PULL_TOP or PULL_BOT: the part of the decode that needs no ballot, so a single lane
+// may ask for the children of any slot (word index wi).  W: uint32_t (narrow) / uint64_t (wide).
+struct PullChildren {
+    uint32_t lo, hi;
+};
+template <bool NARROW, typename W>
+__device__ __forceinline__ PullChildren pull_children_of(W w, uint32_t ww)
+{
+    if constexpr (NARROW) {
+        const uint32_t lo = w & NW_CHILD_MASK, hi = (w >> NW_CHILD_BITS) & NW_CHILD_MASK;
+        return {lo < ww ? lo : (lo == nw_top(ww) ? PULL_TOP : PULL_BOT), hi < ww ? hi : (hi == nw_top(ww) ? PULL_TOP : PULL_BOT)};
+    } else {
+        const uint64_t lo = w & WW_CHILD_MASK, hi = (w >> WW_CHILD_BITS) & WW_CHILD_MASK;
+        return {lo < WW_TOP ? (uint32_t)lo : (lo == WW_TOP ? PULL_TOP : PULL_BOT), hi < WW_TOP ? (uint32_t)hi : (hi == WW_TOP ? PULL_TOP : PULL_BOT)};
+    }
+}
+template <typename REAL, bool NARROW>
+__device__ __forceinline__ PullChildren pull_children(const DevPtrs<REAL>& d, uint32_t wi, uint32_t ww)
+{
+    if constexpr (NARROW) return pull_children_of<true>(d.nwords[wi], ww);
+    else return pull_children_of<false>(d.wwords[wi], ww);
+}
 template <typename REAL, bool NARROW>
 __device__ __forceinline__ PullNode pull_decode(const DevPtrs<REAL>& d, uint32_t wi, bool in, uint32_t ww, uint32_t lbase, uint32_t& lgrp)
 {
@@ -28,17 +50,17 @@ __device__ __forceinline__ PullNode pull_decode(const DevPtrs<REAL>& d, uint32_t
     if constexpr (NARROW) {
         const uint32_t w = in ? d.nwords[wi] : nw_pad_word(0);
         nd.act = !(w & NW_PAD);
-        const uint32_t lo = w & NW_CHILD_MASK, hi = (w >> NW_CHILD_BITS) & NW_CHILD_MASK;
-        nd.lo = lo < ww ? lo : (lo == nw_top(ww) ? PULL_TOP : PULL_BOT);
-        nd.hi = hi < ww ? hi : (hi == nw_top(ww) ? PULL_TOP : PULL_BOT);
+        const PullChildren c = pull_children_of<true>(w, ww);
+        nd.lo = c.lo;
+        nd.hi = c.hi;
         nd.layer = lgrp + nw_lidx(w);
         lgrp += (uint32_t)__popcll(__ballot(nw_head(w)));
     } else {
         const uint64_t w = in ? d.wwords[wi] : WW_PAD_WORD;
         nd.act = in;
-        const uint64_t lo = w & WW_CHILD_MASK, hi = (w >> WW_CHILD_BITS) & WW_CHILD_MASK;
-        nd.lo = lo < WW_TOP ? (uint32_t)lo : (lo == WW_TOP ? PULL_TOP : PULL_BOT);
-        nd.hi = hi < WW_TOP ? (uint32_t)hi : (hi == WW_TOP ? PULL_TOP : PULL_BOT);
+        const PullChildren c = pull_children_of<false>(w, ww);
+        nd.lo = c.lo;
+        nd.hi = c.hi;
         nd.layer = lbase + ww_layer(w);
     }
     return nd;

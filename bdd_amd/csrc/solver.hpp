@@ -102,6 +102,11 @@ struct SolverBase {
     virtual int grad_lower_bound_per_bdd(const void* grad_lb, void* grad_lo, void* grad_hi, int smooth, int on_device) = 0;
     virtual int grad_distribute_delta(const void* grad_lo, const void* grad_hi, void* grad_deferred_mm, int on_device) = 0;
     virtual int grad_cost_perturbation(const void* grad_lo, const void* grad_hi, void* grad_lo_pert, void* grad_hi_pert, int on_device) = 0;
+    // grad_iterations (bdd_cuda_learned_mma.cu:308-385): the transpose-Jacobian product of `n` learned iterations run after `after` untracked
+    // ones; grad_lo / grad_hi / grad_mm in-out; contract in include/bdd_mma.h (bddmma_grad_learned_iterations)
+    virtual int grad_learned_iterations(const void* dist_weights, int weights_on_device, double omega, const void* omega_vec, int omega_vec_on_device,
+                                        void* grad_lo, void* grad_hi, void* grad_mm, void* grad_dist_weights_out, void* grad_omega_out, uint64_t after,
+                                        uint64_t n, uint64_t num_caches, int on_device) = 0;
     virtual int bdds_solution(int sorted, char* sol, int on_device) = 0;
     virtual int net_solver_costs(void* out, int on_device) = 0;
     virtual int make_dual_feasible(void* g, int on_device) = 0;

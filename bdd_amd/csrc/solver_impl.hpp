@@ -1745,6 +1745,22 @@ struct SolverT final : SolverBase {
     int grad_lower_bound_per_bdd(const void* g, void* lo, void* hi, int smooth, int on_device) override { return gr_lower_bound_per_bdd(g, lo, hi, smooth, on_device); }
     int grad_distribute_delta(const void* lo, const void* hi, void* out, int on_device) override { return gr_distribute_delta(lo, hi, out, on_device); }
     int grad_cost_perturbation(const void* lo, const void* hi, void* lo_p, void* hi_p, int on_device) override { return gr_cost_perturbation(lo, hi, lo_p, hi_p, on_device); }
+    // The backward of the learned iterations (kernels/graditer.hpp).  Defined in solver_gi.hpp and instantiated in translation units of its
+    // own (solver_gi_f32.hip / solver_gi_f64.hip), as the single-shot operators are: only declared here.
+    int gi_prepare(uint64_t n_caches);  // every buffer of a call with that many caches, before the solver is touched
+    int gi_grad_learned_iterations(const void* w, int w_dev, double omega, const void* omega_vec, int ov_dev, void* grad_lo, void* grad_hi, void* grad_mm,
+                                   void* grad_w_out, void* grad_omega_out, uint64_t after, uint64_t n, uint64_t num_caches, int on_device);
+    int gi_time_kernel(int kind, uint64_t reps, double* ms);  // bddmma_time_kernel kinds 13 - 17
+    struct { int kind = 0; uint64_t reps = 0; float ms = 0.f; } gi_timing;  // kind != 0: that launch group of the call is repeated and timed
+    bool gi_ready = false;
+    REAL* d_gi = nullptr;                  // the call's per-layer / per-slot / per-variable arrays, one block (solver_gi.hpp)
+    std::vector<REAL*> gi_caches;          // {lo, hi} per layer + deferred differences in binned entry order, 3 L each
+    unsigned char* d_gi_scratch = nullptr; // huge packs: the reverse sweeps' per-pack arrays (gi_lds_bytes of the huge width each)
+    int grad_learned_iterations(const void* w, int w_dev, double omega, const void* omega_vec, int ov_dev, void* grad_lo, void* grad_hi, void* grad_mm,
+                                void* grad_w_out, void* grad_omega_out, uint64_t after, uint64_t n, uint64_t num_caches, int on_device) override
+    {
+        return gi_grad_learned_iterations(w, w_dev, omega, omega_vec, ov_dev, grad_lo, grad_hi, grad_mm, grad_w_out, grad_omega_out, after, n, num_caches, on_device);
+    }
     int min_marginal_diff(void* out, int on_device) override
     {
         HIPCHK(hipSetDevice(device));
@@ -2007,6 +2023,7 @@ struct SolverT final : SolverBase {
     int time_kernel(int kind, uint64_t reps, double* ms) override
     {
         HIPCHK(hipSetDevice(device));
+        if (kind >= 13 && kind <= 17) return gi_time_kernel(kind, reps, ms);
         int rc = BDDMMA_OK;
         auto once = [&]() -> int {
             switch (kind) {

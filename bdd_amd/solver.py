@@ -410,6 +410,31 @@ class bdd_hip_parallel_mma:
         n, v = self.nr_layers(), self.nr_variables()
         return self._grad_call(self._L.bddmma_grad_cost_perturbation, (grad_lo, grad_hi), (n, n), out, (v, v))
 
+    def grad_iterations(self, dist_weights, grad_lo, grad_hi, grad_mm, omega=0.5, track_grad_after_itr=0, track_grad_for_num_itr=1, num_caches=1,
+                        omega_vec=None, out=None):
+        """The backward of learned_iterations (grad_iterations, bdd_cuda_learned_mma.cu:308-385): the loss gradient with respect to the arc
+        costs and deferred differences after track_grad_for_num_itr iterations (run after track_grad_after_itr untracked ones) -> the
+        gradient with respect to those before them, the distribution weights and omega.  Returns (grad_lo, grad_hi, grad_mm,
+        grad_dist_weights, grad_omega); grad_omega has one entry, nr_layers with omega_vec.  NumPy inputs give new NumPy arrays; with
+        device tensors grad_lo / grad_hi / grad_mm are updated in place and `out` = (grad_dist_weights, grad_omega) device buffers.
+        State contract and error codes: include/bdd_mma.h, bddmma_grad_learned_iterations."""
+        n = self.nr_layers()
+        n_om = n if omega_vec is not None else 1
+        w, w_dev = self._learned_buf(dist_weights, n, "dist_weights")
+        ov, ov_dev = self._learned_buf(omega_vec, n, "omega_vec") if omega_vec is not None else (None, 0)
+        tail = (int(track_grad_after_itr), int(track_grad_for_num_itr), int(num_caches))
+        if _is_dev(grad_lo):
+            assert out is not None and len(out) == 2, "device gradients need device output buffers: out=(grad_dist_weights, grad_omega)"
+            ptrs = [_dev_ptr(x, k, self.value_type) for x, k in zip((grad_lo, grad_hi, grad_mm, out[0], out[1]), (n, n, n, n, n_om))]
+            self._ck(self._L.bddmma_grad_learned_iterations(self._h, w, w_dev, float(omega), ov, ov_dev, *ptrs, *tail, 1))
+            return grad_lo, grad_hi, grad_mm, out[0], out[1]
+        g = [np.array(x, dtype=self.value_type, order="C") for x in (grad_lo, grad_hi, grad_mm)]
+        for x in g:
+            assert x.size == n, f"expected {n} values, got {x.size}"
+        res = [np.zeros(n, self.value_type), np.zeros(n_om, self.value_type)]
+        self._ck(self._L.bddmma_grad_learned_iterations(self._h, w, w_dev, float(omega), ov, ov_dev, *(_ptr(x) for x in g + res), *tail, 0))
+        return g[0], g[1], g[2], res[0], res[1]
+
     def bdds_solution_vec(self, out=None):
         if out is not None:   # device_vector<char> (bdd_cuda_base.cu:1138-1145)
             self._ck(self._L.bddmma_bdds_solution(self._h, 0, _dev_ptr(out, self.nr_layers(), np.int8), 1))

@@ -307,7 +307,7 @@ int bddmma_bdds_solution(bddmma_solver* s, int sorted, char* sol, int on_device)
  * bddmma_get_solver_costs, bddmma_min_marginal_diff and bddmma_bdds_solution(sorted = 0)), on the host or the device (on_device, one flag
  * for all arrays of a call); inputs and outputs must not overlap.  A null pointer or a non-finite incoming gradient gives
  * BDDMMA_ERR_INVALID_ARGUMENT and leaves the solver untouched.  No entry point changes arc costs, deferred differences or delta; all of
- * them work with an L-BFGS wrapper attached.  Backpropagation through iterations (grad_iterations) is not provided. */
+ * them work with an L-BFGS wrapper attached.  Backpropagation through the learned iterations: bddmma_grad_learned_iterations below. */
 /* grad_mm_diff_all_hops (bdd_cuda_learned_mma.cu:623-1023; grad_all_min_marginal_differences of the reference's Python module): the
  * transpose-Jacobian product of bddmma_min_marginal_diff with respect to the current lo / hi arc costs, deferred differences NOT applied
  * (as in the forward call).  With F the cost from the root, T the cost to the terminal and, per layer l and arc a,
@@ -342,6 +342,41 @@ int bddmma_grad_distribute_delta(bddmma_solver* s, const void* grad_lo, const vo
  * REAL[nr_variables], out[v] = (sum over the layers of v of grad[l]) / nr_bdds(v), summed in the order of the variable's layers by BDD.
  * Reads no solver state besides the layout. */
 int bddmma_grad_cost_perturbation(bddmma_solver* s, const void* grad_lo, const void* grad_hi, void* grad_lo_pert_out, void* grad_hi_pert_out, int on_device);
+
+/* grad_iterations (bdd_cuda_learned_mma.cu:308-385 with :418-621): the exact transpose-Jacobian product of track_grad_for_num_itr learned
+ * iterations (bddmma_learned_iterations / _omega_vec with improvement_slope = 0 and no history), run after track_grad_after_itr untracked
+ * ones, at the arg-mins those iterations took.  One iteration maps (lo, hi, d) — arc costs and deferred differences per layer — to new ones:
+ * T = cost to terminal of (lo, hi); a forward pass root -> terminal with, per layer l, m_a[l] = min over its nodes u of F[u] + c_a[l] +
+ * T[child_a(u)], mm[l] = omega_l (m_hi - m_lo) (0 unless both are finite), lo'[l] = lo[l] + min(mm, 0) + w[l] S_lo[v(l)],
+ * hi'[l] = hi[l] + min(-mm, 0) + w[l] S_hi[v(l)], S the per-variable sums of max(-d, 0) / max(d, 0), F grown from the new costs; then a
+ * backward pass terminal -> root, the same with that F, the forward pass's mm as d, and T rebuilt from the new costs as it rises.
+ *   dist_weights, omega, omega_vec   those of the forward call (omega_vec null: the scalar omega; otherwise REAL[nr_layers] and omega is ignored)
+ *   grad_lo, grad_hi, grad_mm        REAL[nr_layers], in-out: on entry the loss gradient with respect to the arc costs and deferred differences
+ *                                    AFTER the tracked iterations, on return with respect to those BEFORE the first tracked iteration (after
+ *                                    the untracked ones)
+ *   grad_dist_weights_out            REAL[nr_layers], overwritten
+ *   grad_omega_out                   REAL[1] (scalar omega: the per-layer values summed in double in a fixed order) or REAL[nr_layers]
+ *   num_caches                       up to max(num_caches, 1) inputs of tracked iterations are kept on the device at the reference's interval
+ *                                    rule (bdd_cuda_learned_mma.h:12-23); the others are replayed from the nearest one.  The caches (3 REAL per
+ *                                    layer each) and the call's other arrays are allocated on first use and counted by bddmma_device_bytes.
+ * Layer arrays are in the public layer order; on_device is one flag for the five gradient arrays.
+ * The reverse of a pass uses the potentials F and T the pass itself read (the reference replays the pass and takes its arg-mins against the
+ * potentials of the UPDATED costs, :542-545 and :592-595; agreement with it there is not a goal, agreement with finite differences of
+ * bddmma_learned_iterations is).  Tie rules as bddmma_grad_min_marginal_diff; the dual update's rule at mm = 0 is the reference's (>= 0: the hi
+ * side, :439-442), as is that of the consumed differences (:512-516).  One launch per pass and pack family (csrc/kernels/graditer.hpp), no
+ * atomics in the reverse sweeps.
+ * State contract: on entry the solver holds the state from which the forward call started.  On return the arc costs, the deferred
+ * differences and delta are the entry values bit for bit; both sweep states are invalid (recomputed by whoever needs them).  Refusals, each
+ * leaving the solver untouched: BDDMMA_ERR_STATE while an L-BFGS wrapper is attached or run_solver is queueing iterations;
+ * BDDMMA_ERR_INVALID_ARGUMENT for a null pointer (omega_vec excepted), a non-finite incoming gradient, a negative or non-finite weight or
+ * omega; BDDMMA_ERR_UNSUPPORTED where a wide pack's arrays (8 REAL + 12 bytes per slot) do not fit the LDS.
+ * track_grad_for_num_itr = 0: no iteration runs, the in-out arrays are unchanged, both outputs are zero-filled.
+ * The result does not depend on num_caches.  With the deterministic exchange (bddmma_options.deterministic) two calls, and calls with any two
+ * num_caches, agree bit for bit; with the default LDS-atomic exchange the replayed iterations may differ in the last bits of a variable's sum
+ * from call to call, and so may the result. */
+int bddmma_grad_learned_iterations(bddmma_solver* s, const void* dist_weights, int weights_on_device, double omega, const void* omega_vec,
+                                   int omega_vec_on_device, void* grad_lo, void* grad_hi, void* grad_mm, void* grad_dist_weights_out, void* grad_omega_out,
+                                   uint64_t track_grad_after_itr, uint64_t track_grad_for_num_itr, uint64_t num_caches, int on_device);
 
 /* ---- L-BFGS support (lbfgs.h:22-27) --------------------------------------- */
 /* net_solver_costs() (bdd_cuda_parallel_mma.cu:432-463): hi - lo + deferred mm diff, REAL[nr_layers]. */
@@ -444,7 +479,11 @@ int bddmma_time_iterations(bddmma_solver* s, double omega, uint64_t n, double* m
 /* Time `reps` back-to-back launches of one kernel class with hipEvents on the handle's stream
  * (kernel-level benchmarking; leaves the sweep state invalid).  kind: 0 forward_run sweep, 1 backward_run
  * sweep, 2 forward_mm sweep, 3 backward_mm sweep, 4 exchange reduce, 5 exchange broadcast, 8 / 9 forward / backward sum-marginal
- * sweep (bddmma_sum_marginals), 10 / 11 / 12 the root -> terminal / terminal -> root / both gradient sweeps (bddmma_grad_min_marginal_diff), 6 STREAM triad
+ * sweep (bddmma_sum_marginals), 10 / 11 / 12 the root -> terminal / terminal -> root / both gradient sweeps (bddmma_grad_min_marginal_diff),
+ * 13 - 17 the launch groups of one reversed learned iteration (bddmma_grad_learned_iterations with one tracked iteration, zero incoming
+ * gradients and isotropic weights; the state is the entry state on return): 13 the reverse of the backward pass, 14 the reverse of the
+ * forward pass, 15 the final sweep through T, 16 the copies and memsets that keep what the reverse reads, 17 its six elementwise launches;
+ * 6 STREAM triad
  * a = b + s*c over three temporary arrays of BDDMMA_TRIAD_BYTES each (3 * BDDMMA_TRIAD_BYTES of HBM traffic
  * per launch), 7 STREAM copy a = b (2 * BDDMMA_TRIAD_BYTES per launch): the measured bandwidth ceilings of the
  * box the roofline is quoted next to. */
