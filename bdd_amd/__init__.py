@@ -34,3 +34,4 @@ _share_hip_runtime_with_torch()
 
 from .bdd_collection import BddCollection, TOPSINK, BOTSINK  # noqa: F401
 from .ilp import ILP, parse_lp, to_bdd_collection  # noqa: F401
+from .solver import bdd_hip_batch, bdd_hip_parallel_mma  # noqa: F401

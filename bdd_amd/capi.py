@@ -116,6 +116,14 @@ SIGNATURES = {
     "bddmma_perturb_primal_costs": (_I, [_V, _V, _D, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), _V, _V, _V]),
     "bddmma_run_solver": (_I, [_V, _V, _U64, _D, _D, _D, _I, C.POINTER(RunResult)]),
     "bddmma_run_solver_host_loop": (_I, [_V, _V, _U64, _D, _D, _D, _I, C.POINTER(RunResult)]),
+    "bddmma_batch_create": (_I, [C.POINTER(_V), C.POINTER(_V), _U64]),
+    "bddmma_batch_destroy": (None, [_V]),
+    "bddmma_batch_last_error": (C.c_char_p, [_V]),
+    "bddmma_batch_size": (_U64, [_V]),
+    "bddmma_batch_iterations": (_I, [_V, _D, _U64]),
+    "bddmma_batch_time_iterations": (_I, [_V, _D, _U64, C.POINTER(_D)]),
+    "bddmma_batch_run_solver": (_I, [_V, _U64, _D, _D, _D, C.POINTER(RunResult)]),
+    "bddmma_batch_lower_bounds": (_I, [_V, C.POINTER(_D)]),
     "bddmma_incremental_mm_agreement_rounding": (_I, [_V, _V, _D, _D, _U64, _U64, C.c_uint32, _I, _V, C.POINTER(_I)]),
     "bddmma_save": (_I, [_V, C.c_char_p]),
     "bddmma_load": (_I, [C.POINTER(_V), _I, C.c_char_p]),

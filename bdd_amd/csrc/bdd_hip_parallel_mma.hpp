@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <array>
 #include <cstdint>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -447,6 +448,46 @@ class bdd_hip_parallel_mma {
         if (rc != BDDMMA_OK) throw std::runtime_error(std::string("bdd_hip_parallel_mma: ") + bddmma_last_error(h));
     }
     bddmma_solver* h_ = nullptr;
+};
+
+// Solvers whose instances fit one workgroup each (fused_small()), run together: one workgroup per member in one launch instead of one
+// launch per solver (include/bdd_mma.h: bddmma_batch_*).  The solvers are borrowed: they must outlive the batch and stay usable on their
+// own between its calls; a call behaves as if it had been made on each member in turn.
+template <typename REAL>
+class bdd_hip_batch {
+   public:
+    explicit bdd_hip_batch(const std::vector<std::reference_wrapper<bdd_hip_parallel_mma<REAL>>>& solvers)
+    {
+        std::vector<bddmma_solver*> h;
+        for (bdd_hip_parallel_mma<REAL>& s : solvers) h.push_back(s.handle());
+        if (bddmma_batch_create(&b_, h.data(), h.size()) != BDDMMA_OK) throw std::runtime_error(std::string("bdd_hip_batch: ") + bddmma_batch_last_error(nullptr));
+    }
+    ~bdd_hip_batch() { bddmma_batch_destroy(b_); }
+    bdd_hip_batch(const bdd_hip_batch&) = delete;
+    bdd_hip_batch& operator=(const bdd_hip_batch&) = delete;
+    size_t size() const { return bddmma_batch_size(b_); }
+    void iterations(const size_t n, const REAL omega = 0.5) { check(bddmma_batch_iterations(b_, omega, n)); }
+    std::vector<bddmma_run_result> run_solver(const size_t max_iter = 1000, const double tolerance = 1e-6, const double improvement_slope = 1e-9,
+                                              const double time_limit = 3600.0)
+    {
+        std::vector<bddmma_run_result> res(size());
+        check(bddmma_batch_run_solver(b_, max_iter, tolerance, improvement_slope, time_limit, res.data()));
+        return res;
+    }
+    std::vector<double> lower_bounds()
+    {
+        std::vector<double> lb(size());
+        check(bddmma_batch_lower_bounds(b_, lb.data()));
+        return lb;
+    }
+    bddmma_batch* handle() { return b_; }
+
+   private:
+    void check(int rc) const
+    {
+        if (rc != BDDMMA_OK) throw std::runtime_error(std::string("bdd_hip_batch: ") + bddmma_batch_last_error(b_));
+    }
+    bddmma_batch* b_ = nullptr;
 };
 
 // lbfgs<bdd_cuda_parallel_mma<REAL>, ...> (include/bdd_solver/lbfgs.h:35-111) over the HIP solver.

@@ -41,6 +41,18 @@ int guarded(bddmma_solver* s, F&& f)
 template <typename F>
 int guarded(const bddmma_solver* s, F&& f) { return guarded(const_cast<bddmma_solver*>(s), f); }
 
+template <typename F>
+int guarded_batch(bddmma_batch* b, F&& f)
+{
+    if (!b || !b->impl) return BDDMMA_ERR_INVALID_ARGUMENT;
+    try {
+        return f(b->impl);
+    } catch (const std::exception& e) {
+        b->impl->err = e.what();
+        return BDDMMA_ERR_DEVICE;
+    }
+}
+
 template <typename T>
 int copy_host(const std::vector<T>& v, T* out)
 {
@@ -388,6 +400,64 @@ int bddmma_run_solver_host_loop(bddmma_solver* s, bddmma_lbfgs* lbfgs, uint64_t 
                                 double time_limit, int verbose, bddmma_run_result* res)
 {
     return run_solver_impl(s, lbfgs, max_iter, tolerance, improvement_slope, time_limit, verbose, res, true);
+}
+
+// ---- batches of one-workgroup instances (solver.hpp: BatchBase)
+int bddmma_batch_create(bddmma_batch** out, bddmma_solver* const* members, uint64_t n)
+{
+    if (out) *out = nullptr;
+    if (!out || !members || n == 0) {
+        g_err = !out ? "batch: null output pointer" : !members ? "batch: null member array" : "batch: no members";
+        return BDDMMA_ERR_INVALID_ARGUMENT;
+    }
+    try {
+        std::vector<SolverBase*> impls(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            if (!members[i] || !members[i]->impl) {
+                g_err = "batch member " + std::to_string(i) + ": null handle";
+                return BDDMMA_ERR_INVALID_ARGUMENT;
+            }
+            impls[i] = members[i]->impl;
+        }
+        BatchBase* impl = nullptr;
+        const int rc = create_batch(&impl, impls.data(), n, g_err);
+        if (rc) return rc;
+        *out = new bddmma_batch{impl};
+        return BDDMMA_OK;
+    } catch (const std::exception& e) {
+        g_err = e.what();
+        return BDDMMA_ERR_DEVICE;
+    }
+}
+void bddmma_batch_destroy(bddmma_batch* b)
+{
+    if (!b) return;
+    delete b->impl;
+    delete b;
+}
+const char* bddmma_batch_last_error(const bddmma_batch* b) { return (b && b->impl) ? b->impl->err.c_str() : g_err.c_str(); }
+uint64_t bddmma_batch_size(const bddmma_batch* b) { return b && b->impl ? b->impl->size() : 0; }
+int bddmma_batch_iterations(bddmma_batch* b, double omega, uint64_t n)
+{
+    return guarded_batch(b, [&](BatchBase* i) { return i->iterations(omega, n); });
+}
+int bddmma_batch_time_iterations(bddmma_batch* b, double omega, uint64_t n, double* ms)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!ms) { i->err = "batch: null output pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        return i->time_iterations(omega, n, ms);
+    });
+}
+int bddmma_batch_run_solver(bddmma_batch* b, uint64_t max_iter, double tolerance, double improvement_slope, double time_limit, bddmma_run_result* res)
+{
+    return guarded_batch(b, [&](BatchBase* i) { return i->run_plain(max_iter, tolerance, improvement_slope, time_limit, res); });
+}
+int bddmma_batch_lower_bounds(bddmma_batch* b, double* out)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!out) { i->err = "batch: null output pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        return i->lower_bounds(out);
+    });
 }
 
 // perturb_primal_costs (incremental_mm_agreement_rounding_cuda.cu:262-331).  The cost update goes through the solver type the

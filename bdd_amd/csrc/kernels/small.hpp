@@ -1,4 +1,4 @@
-// kernels/small.hpp — instances that fit ONE workgroup: whole MMA iterations inside one launch (k_iterate_small).
+// kernels/small.hpp — instances that fit ONE workgroup: whole MMA iterations inside one launch (k_iterate_small, k_iterate_small_batch).
 // Part of kernels.hpp (include that, not this file: the parts build on each other in its order).
 #pragma once
 
@@ -71,9 +71,10 @@ inline uint32_t small_lds_bytes(uint32_t real_size, uint32_t n_packs, uint32_t n
     return o;
 }
 
+// The workgroup's work, shared by k_iterate_small (one instance per launch) and k_iterate_small_batch (one instance per workgroup).
 // NW waves, pack p on wave p (n_packs <= NW); RL: the packs' records live in LDS too (1 KiB per hop), else they stream from L2 eight hops ahead
 template <typename REAL, int NW, bool RL>
-__global__ void __launch_bounds__(64 * NW) k_iterate_small(SmallDev sm, DevPtrs<REAL> d, PackDev pk, REAL omega, uint32_t n_iters, RunStep run)
+__device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<REAL>& d, const PackDev& pk, REAL omega, uint32_t n_iters, const RunStep& run)
 {
     constexpr uint32_t S = sizeof(REAL);
     constexpr uint32_t NT = 64 * NW;
@@ -410,6 +411,47 @@ __global__ void __launch_bounds__(64 * NW) k_iterate_small(SmallDev sm, DevPtrs<
             }
         }
     }
+}
+
+template <typename REAL, int NW, bool RL>
+__global__ void __launch_bounds__(64 * NW) k_iterate_small(SmallDev sm, DevPtrs<REAL> d, PackDev pk, REAL omega, uint32_t n_iters, RunStep run)
+{
+    small_iterate<REAL, NW, RL>(sm, d, pk, omega, n_iters, run);
+}
+
+// A batch of such instances in one launch (solver_bt.hpp): workgroup b runs instance items[b], which holds what k_iterate_small takes by
+// value.  No workgroup talks to another.  The item's address is uniform and the array is read-only for the launch, so its fields arrive
+// by scalar loads as kernel arguments do.  Every member of a launch has the same NW and RL; the dynamic LDS is the largest member's.
+template <typename REAL>
+struct SmallItem {
+    SmallDev sm;
+    DevPtrs<REAL> d;
+    PackDev pk;
+    RunStep run;
+};
+template <typename REAL, int NW, bool RL>
+__global__ void __launch_bounds__(64 * NW) k_iterate_small_batch(const SmallItem<REAL>* __restrict__ items, REAL omega, uint32_t n_iters)
+{
+    const SmallItem<REAL>& item = items[blockIdx.x];
+    small_iterate<REAL, NW, RL>(item.sm, item.d, item.pk, omega, n_iters, item.run);
+}
+// What changes between the launches of a batch, written into the items on the device (in stream order, so no launch sees half an update):
+// the run_solver gate and control block of each item — `ctl` null: outside run_solver — and the index of the launch's first iteration.
+template <typename REAL>
+__global__ void k_small_items_refresh(SmallItem<REAL>* items, uint32_t n, RunCtl* ctl, RunHost* host, uint32_t run_iter)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    items[i].d.stop = ctl != nullptr ? &ctl[i].stop : nullptr;
+    items[i].d.run_iter = run_iter;
+    items[i].run.ctl = ctl != nullptr ? ctl + i : nullptr;
+    items[i].run.host = ctl != nullptr ? host + i : nullptr;
+}
+// k_run_begin for every control block of a batch: one clock for all of them
+static __global__ void k_run_begin_batch(RunCtl* ctl, uint32_t n, uint64_t host_ticks_so_far)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) ctl[i].t0 = __builtin_amdgcn_s_memrealtime() - host_ticks_so_far;
 }
 
 }  // namespace bddmma

@@ -146,13 +146,41 @@ struct SolverBase {
     int time_iterations(double omega, uint64_t n, double* ms);
 };
 
+// A batch of solvers whose instances fit one workgroup each (fused_small): its calls run every member's iterations concurrently, one
+// workgroup per member, one launch per kernel instantiation present (kernels/small.hpp: k_iterate_small_batch; solver_bt.hpp: BatchT).
+// The members are borrowed: they must outlive the batch, and they stay usable on their own between the batch's calls.
+//
+// Ordering: a call behaves as if the same call had been made on each member in turn.  The batch has a stream of its own; a call first
+// records an event on every member's stream and makes the batch stream wait for it (ordered after everything queued on the members),
+// launches, then records one event on the batch stream that every member's stream waits for (everything queued on a member afterwards
+// is ordered after the call).  No host synchronisation; two event calls per member and call on entry, one on exit.
+//
+// State refusals are made per call, before anything is launched: BDDMMA_ERR_STATE and every member untouched when a member has
+// profiling on, has (had) an L-BFGS wrapper attached or is inside run_solver.
+struct BatchBase {
+    std::string err;
+    virtual ~BatchBase() {}
+    virtual uint64_t size() const = 0;
+    virtual int iterations(double omega, uint64_t n) = 0;   // SolverBase::iterations(omega, n) of every member
+    // run_plain of every member (tests in its workgroup, its own control block; one clock and one time limit for the batch); res[size()]
+    virtual int run_plain(uint64_t max_iter, double tolerance, double slope, double time_limit, bddmma_run_result* res) = 0;
+    virtual int time_iterations(double omega, uint64_t n, double* ms) = 0;   // iterations() between hipEvents on the batch stream; waits
+    virtual int lower_bounds(double* out) = 0;              // SolverBase::lower_bound of every member, the reductions in flight together
+};
+// Refuses (before any device call): BDDMMA_ERR_INVALID_ARGUMENT for n == 0, a null member or a member listed twice; BDDMMA_ERR_UNSUPPORTED for
+// a member that is not fused_small or differs from member 0 in precision or device; BDDMMA_ERR_STATE for profiling / an L-BFGS wrapper.
+int create_batch(BatchBase** out, SolverBase* const* members, uint64_t n, std::string& err);
+
 int device_count();
 int query_chip(int device, ChipInfo* out, std::string& err);  // CU count and LDS per CU of `device` (hipDeviceProp)
 int create_solver(SolverBase** out, int precision, int device, const HostLayout& L, const bddmma_options* opts, std::string& err);
 
 }  // namespace bddmma
 
-// the opaque C handle
+// the opaque C handles
 struct bddmma_solver {
     bddmma::SolverBase* impl = nullptr;
+};
+struct bddmma_batch {
+    bddmma::BatchBase* impl = nullptr;
 };

@@ -2,6 +2,7 @@
 // create_solver, which picks the instantiation of SolverT<REAL> (solver_impl.hpp) built by solver_f32.hip / solver_f64.hip.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <memory>
@@ -25,6 +26,8 @@ namespace bddmma {
 
 SolverBase* make_solver_f32();  // solver_f32.hip
 SolverBase* make_solver_f64();  // solver_f64.hip
+int make_batch_f32(BatchBase** out, SolverBase* const* members, uint64_t n, std::string& err);  // solver_bt_f32.hip
+int make_batch_f64(BatchBase** out, SolverBase* const* members, uint64_t n, std::string& err);  // solver_bt_f64.hip
 
 // ---------------------------------------------------------------------------------------------
 int SolverBase::synchronize()
@@ -142,6 +145,55 @@ int create_solver(SolverBase** out, int precision, int device, const HostLayout&
     }
     *out = s.release();
     return BDDMMA_OK;
+}
+
+// Every refusal that needs no device comes first, so that a bad member list costs nothing and touches nothing.
+int create_batch(BatchBase** out, SolverBase* const* members, uint64_t n, std::string& err)
+{
+    if (!members || n == 0) {
+        err = "batch: no members";
+        return BDDMMA_ERR_INVALID_ARGUMENT;
+    }
+    if (n > 0xFFFFFFFFull / 4096) {
+        err = "batch: too many members";
+        return BDDMMA_ERR_INVALID_ARGUMENT;
+    }
+    for (uint64_t i = 0; i < n; ++i)
+        if (!members[i]) {
+            err = "batch member " + std::to_string(i) + ": null handle";
+            return BDDMMA_ERR_INVALID_ARGUMENT;
+        }
+    {
+        std::vector<const SolverBase*> sorted(members, members + n);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) {
+            uint64_t i = n;   // the second listing of the handle
+            while (i-- > 0 && members[i] != *dup) {}
+            err = "batch member " + std::to_string(i) + ": the handle is listed twice";
+            return BDDMMA_ERR_INVALID_ARGUMENT;
+        }
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        const SolverBase* s = members[i];
+        const char* why = !s->fused_small                      ? "the instance does not run as one workgroup (bddmma_fused_small is 0)"
+                          : s->precision != members[0]->precision ? "its precision differs from member 0's"
+                          : s->device != members[0]->device       ? "its device differs from member 0's"
+                                                                  : nullptr;
+        if (why) {
+            err = "batch member " + std::to_string(i) + ": " + why;
+            return BDDMMA_ERR_UNSUPPORTED;
+        }
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        const SolverBase* s = members[i];
+        const char* why = s->profiling ? "profiling is on" : *s->lbfgs_attached > 0 ? "an L-BFGS wrapper is attached" : nullptr;
+        if (why) {
+            err = "batch member " + std::to_string(i) + ": " + why;
+            return BDDMMA_ERR_STATE;
+        }
+    }
+    return members[0]->precision == BDDMMA_F32 ? make_batch_f32(out, members, n, err) : make_batch_f64(out, members, n, err);
 }
 
 }  // namespace bddmma

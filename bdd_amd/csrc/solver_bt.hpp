@@ -1,0 +1,316 @@
+// solver_bt.hpp — BatchT<REAL>: many one-workgroup instances in one launch (solver.hpp: BatchBase; kernels/small.hpp:
+// k_iterate_small_batch).  Included by solver_bt_f32.hip / solver_bt_f64.hip only, so that the batch kernels compile in translation units of
+// their own.
+#pragma once
+#include <algorithm>
+#include <mutex>
+
+#include "solver_impl.hpp"
+
+namespace bddmma {
+
+template <typename REAL>
+struct BatchT final : BatchBase {
+    using S = SolverT<REAL>;
+    using Fn = void (*)(const SmallItem<REAL>*, REAL, uint32_t);
+    // The members in the caller's order; item j of the device arrays (items, control blocks, published bounds) is member order[j]: the items
+    // are sorted by the instantiation the member's solver chose (small_nw x small_rl), so that each group is one contiguous launch.
+    std::vector<S*> m;
+    std::vector<uint32_t> order;
+    struct Group {
+        Fn fn;
+        uint32_t threads, lds, first, count;   // lds: the largest small_lds of the group
+    };
+    std::vector<Group> groups;
+    int device = -1;
+    hipStream_t stream = nullptr;
+    std::vector<hipEvent_t> ev_in;             // one per member: recorded on the member's stream on entry
+    hipEvent_t ev_out = nullptr, ev_chunk[2] = {nullptr, nullptr};
+    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;   // time_iterations (created on first use)
+    SmallItem<REAL>* d_items = nullptr;
+    RunCtl *d_ctl = nullptr, *h_ctl = nullptr;           // h_ctl: pinned staging of the control blocks' initial values
+    RunHost *h_run = nullptr, *d_run_host = nullptr;     // pinned + its device address: what the members' workgroups publish
+
+    ~BatchT() override
+    {
+        // (the members are not touched: they may be gone already — the caller's error, but not one to crash on)
+        if (device >= 0) (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (hipEvent_t e : ev_in) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1})
+            if (e) (void)hipEventDestroy(e);
+        if (d_items) (void)hipFree(d_items);
+        if (d_ctl) (void)hipFree(d_ctl);
+        if (h_ctl) (void)hipHostFree(h_ctl);
+        if (h_run) (void)hipHostFree(h_run);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+    uint64_t size() const override { return m.size(); }
+
+    static Fn batch_fn(int nw, bool rl)
+    {
+        return pick<1, 2, 4, 8, 16>((uint32_t)nw, [&](auto NW) -> Fn {
+            return rl ? &k_iterate_small_batch<REAL, NW.value, true> : &k_iterate_small_batch<REAL, NW.value, false>;
+        });
+    }
+    // The dynamic-LDS limit of a batch kernel is a property of the function, shared by every batch of the process: it is only ever raised
+    // (a limit is not a reservation), so that a later batch of smaller members does not take it away from an earlier one.
+    int raise_lds_limit(Fn fn, uint32_t lds)
+    {
+        static std::mutex mtx;
+        static std::vector<std::pair<Fn, uint32_t>> limits;
+        std::lock_guard<std::mutex> lock(mtx);
+        auto it = std::find_if(limits.begin(), limits.end(), [&](const std::pair<Fn, uint32_t>& e) { return e.first == fn; });
+        if (it != limits.end() && it->second >= lds) return BDDMMA_OK;
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (it != limits.end()) it->second = lds;
+        else limits.push_back({fn, lds});
+        return BDDMMA_OK;
+    }
+
+    int init(SolverBase* const* members, uint64_t n)
+    {
+        m.resize(n);
+        for (uint64_t i = 0; i < n; ++i) m[i] = static_cast<S*>(members[i]);
+        device = m[0]->device;
+        if (int rc = check_state()) return rc;
+        order.resize(n);
+        for (uint32_t i = 0; i < n; ++i) order[i] = i;
+        auto key = [&](uint32_t i) { return (uint32_t)m[i]->small_nw * 2u + (m[i]->small_rl ? 1u : 0u); };
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
+        std::vector<SmallItem<REAL>> items(n);
+        for (uint32_t j = 0; j < n; ++j) {
+            const S* s = m[order[j]];
+            items[j] = s->small_item();
+            if (groups.empty() || key(order[j]) != key(order[groups.back().first]))
+                groups.push_back(Group{batch_fn(s->small_nw, s->small_rl), 64u * (uint32_t)s->small_nw, 0u, j, 0u});
+            Group& g = groups.back();
+            g.lds = std::max(g.lds, s->small_lds);
+            ++g.count;
+        }
+        HIPCHK(hipSetDevice(device));
+        for (const Group& g : groups)
+            if (int rc = raise_lds_limit(g.fn, g.lds)) return rc;
+        HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        ev_in.assign(n, nullptr);
+        for (hipEvent_t& e : ev_in) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&ev_out, hipEventDisableTiming));
+        for (hipEvent_t& e : ev_chunk) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIPCHK(hipMalloc((void**)&d_items, n * sizeof(SmallItem<REAL>)));
+        HIPCHK(hipMalloc((void**)&d_ctl, n * sizeof(RunCtl)));
+        HIPCHK(hipHostMalloc((void**)&h_ctl, n * sizeof(RunCtl), hipHostMallocDefault));
+        HIPCHK(hipHostMalloc((void**)&h_run, n * sizeof(RunHost), hipHostMallocMapped | hipHostMallocCoherent));
+        HIPCHK(hipHostGetDevicePointer((void**)&d_run_host, h_run, 0));
+        HIPCHK(hipMemcpy(d_items, items.data(), n * sizeof(SmallItem<REAL>), hipMemcpyHostToDevice));
+        return BDDMMA_OK;
+    }
+
+    // per call, before anything is launched: what small_usable() asks of a solver, for every member
+    int check_state()
+    {
+        for (size_t i = 0; i < m.size(); ++i) {
+            const char* why = m[i]->profiling                                        ? "profiling is on"
+                              : (*m[i]->lbfgs_attached > 0 || m[i]->d_x_layer != nullptr) ? "an L-BFGS wrapper is or was attached (its backward sweeps write x per layer)"
+                              : m[i]->run_stop != nullptr                            ? "run_solver is in progress"
+                                                                                     : nullptr;
+            if (why) {
+                err = "batch member " + std::to_string(i) + ": " + why;
+                return BDDMMA_ERR_STATE;
+            }
+        }
+        return BDDMMA_OK;
+    }
+    // entry: members whose costs-to-terminal are stale get their own backward_run() first, as launch_small does; then the batch stream waits
+    // for everything queued on every member's stream
+    int join_in()
+    {
+        for (S* s : m)
+            if (int rc = s->backward_run()) { err = s->err; return rc; }
+        for (size_t i = 0; i < m.size(); ++i) {
+            HIPCHK(hipEventRecord(ev_in[i], m[i]->stream));
+            HIPCHK(hipStreamWaitEvent(stream, ev_in[i], 0));
+        }
+        return BDDMMA_OK;
+    }
+    // exit: every member's stream waits for what the batch stream holds now
+    int join_out()
+    {
+        HIPCHK(hipEventRecord(ev_out, stream));
+        for (S* s : m) HIPCHK(hipStreamWaitEvent(s->stream, ev_out, 0));
+        return BDDMMA_OK;
+    }
+    int refresh(bool run, uint32_t run_iter)
+    {
+        const uint32_t n = (uint32_t)m.size();
+        hipLaunchKernelGGL((k_small_items_refresh<REAL>), dim3(cdiv(n, 256)), dim3(256), 0, stream, d_items, n, run ? d_ctl : (RunCtl*)nullptr, d_run_host, run_iter);
+        HIPCHK(hipGetLastError());
+        return BDDMMA_OK;
+    }
+    // one launch per group: the group's member count as the grid, its largest small_lds as the dynamic LDS
+    int launch(REAL omega, uint32_t n_iters)
+    {
+        for (const Group& g : groups) {
+            hipLaunchKernelGGL(g.fn, dim3(g.count), dim3(g.threads), g.lds, stream, (const SmallItem<REAL>*)(d_items + g.first), omega, n_iters);
+            HIPCHK(hipGetLastError());
+        }
+        for (S* s : m) s->small_launched();
+        return BDDMMA_OK;
+    }
+
+    int iterations(double omega, uint64_t n) override { return iterations_timed(omega, n, nullptr); }
+    // ms non-null: hipEvents on the batch stream around the launches, from the first to the last (the joins are outside); waits for them
+    int iterations_timed(double omega, uint64_t n, double* ms)
+    {
+        int rc;
+        if ((rc = check_state())) return rc;
+        if (ms) *ms = 0.0;
+        if (n == 0) return BDDMMA_OK;
+        HIPCHK(hipSetDevice(device));
+        if (ms && !ev_t0) {
+            HIPCHK(hipEventCreate(&ev_t0));
+            HIPCHK(hipEventCreate(&ev_t1));
+        }
+        if ((rc = join_in())) return rc;
+        if (ms) HIPCHK(hipEventRecord(ev_t0, stream));
+        if ((rc = refresh(false, 0))) return rc;
+        while (n) {
+            const uint32_t chunk = (uint32_t)std::min<uint64_t>(n, 1u << 14);   // as SolverT::iterations
+            if ((rc = launch((REAL)omega, chunk))) break;
+            n -= chunk;
+        }
+        if (ms && !rc) HIPCHK(hipEventRecord(ev_t1, stream));
+        const int rc2 = join_out();   // also behind a failed launch: what was queued stays ordered
+        if (rc || rc2) return rc ? rc : rc2;
+        if (ms) {
+            float f = 0.f;
+            HIPCHK(hipEventSynchronize(ev_t1));
+            HIPCHK(hipEventElapsedTime(&f, ev_t0, ev_t1));
+            *ms = f;
+        }
+        return BDDMMA_OK;
+    }
+    int time_iterations(double omega, uint64_t n, double* ms) override { return iterations_timed(omega, n, ms); }
+
+    int lower_bounds(double* out) override
+    {
+        HIPCHK(hipSetDevice(device));
+        std::vector<char> pending(m.size(), 0);
+        for (size_t i = 0; i < m.size(); ++i) {
+            S* s = m[i];
+            int rc = s->backward_run();
+            if (!rc && !s->lb_cached) {
+                rc = s->launch_bound(0);
+                pending[i] = 1;
+            }
+            if (rc) { err = s->err; return rc; }
+        }
+        // the reductions run side by side on the members' streams; the host then collects them in order
+        for (size_t i = 0; i < m.size(); ++i) {
+            S* s = m[i];
+            if (pending[i]) {
+                if (int rc = s->wait_bound(0)) { err = s->err; return rc; }
+                s->lb_cache = ((volatile double*)s->h_lb)[0];
+                s->lb_cached = true;
+            }
+            out[i] = s->lb_cache;
+        }
+        return BDDMMA_OK;
+    }
+
+    // SolverT::run_plain for every member at once.  Chunks of SMALL_CHUNK iterations, the tests in each member's workgroup after every
+    // iteration against its own control block; a member that has stopped returns at once in later chunks (DevPtrs::stop).  At most two
+    // chunks are outstanding; the host waits for the older one and reads what the members have published.
+    int run_plain(uint64_t max_iter, double tolerance, double slope, double time_limit, bddmma_run_result* res) override
+    {
+        if (slope < 0.0 || slope >= 1.0 || time_limit < 0.0 || tolerance < 0.0) {
+            err = "run_solver: invalid termination criteria";
+            return BDDMMA_ERR_INVALID_ARGUMENT;
+        }
+        int rc;
+        if ((rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        const auto t0 = std::chrono::steady_clock::now();
+        auto elapsed = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
+        const uint32_t n = (uint32_t)m.size();
+        std::vector<double> lb_initial(n);
+        if ((rc = lower_bounds(lb_initial.data()))) return rc;
+        constexpr uint64_t MASK = (1ull << 56) - 1;
+        if (max_iter > 0) {
+            for (uint32_t j = 0; j < n; ++j) {
+                RunCtl c{};
+                c.stop = RUN_NOT_STOPPED;
+                c.lb_initial = lb_initial[order[j]];
+                c.lb_first = std::numeric_limits<double>::max();
+                c.lb_post = c.lb_initial;
+                c.tolerance = tolerance;
+                c.slope = slope;
+                c.time_limit = time_limit;
+                h_ctl[j] = c;
+            }
+            std::memset((void*)h_run, 0, n * sizeof(RunHost));
+            if ((rc = join_in())) return rc;
+            HIPCHK(hipMemcpyAsync(d_ctl, h_ctl, n * sizeof(RunCtl), hipMemcpyHostToDevice, stream));
+            hipLaunchKernelGGL(k_run_begin_batch, dim3(cdiv(n, 256)), dim3(256), 0, stream, d_ctl, n, (uint64_t)(elapsed() * RUN_TICKS_PER_SECOND));
+            HIPCHK(hipGetLastError());
+            constexpr uint64_t SMALL_CHUNK = 64;
+            static_assert(2 * SMALL_CHUNK < RUN_RING, "published bounds must not wrap before the host has read them");
+            for (uint32_t j = 0; j < n; ++j) m[order[j]]->run_stop = &d_ctl[j].stop;   // "run_solver in progress", as run_plain marks it
+            volatile RunHost* hr = h_run;
+            uint64_t queued = 0, chunks = 0, waited = 0;
+            while (!rc) {
+                while (!rc && queued < max_iter && chunks - waited < 2) {
+                    const uint64_t n_launch = std::min<uint64_t>(SMALL_CHUNK, max_iter - queued);
+                    if ((rc = refresh(true, (uint32_t)std::min<uint64_t>(queued, RUN_NOT_STOPPED - 1))) || (rc = launch(REAL(0.5), (uint32_t)n_launch))) break;
+                    const hipError_t e = hipEventRecord(ev_chunk[chunks & 1], stream);
+                    if (e != hipSuccess) { err = std::string("hipEventRecord: ") + hipGetErrorString(e); rc = BDDMMA_ERR_DEVICE; break; }
+                    queued += n_launch;
+                    ++chunks;
+                }
+                if (rc || waited == chunks) break;
+                const hipError_t e = hipEventSynchronize(ev_chunk[waited & 1]);
+                if (e != hipSuccess) { err = std::string("run_solver: ") + hipGetErrorString(e); rc = BDDMMA_ERR_DEVICE; break; }
+                ++waited;
+                bool all_done = true;
+                for (uint32_t j = 0; j < n && all_done; ++j) {
+                    const uint64_t st = hr[j].state;
+                    all_done = (st >> 56) != 0 || (st & MASK) >= max_iter;
+                }
+                if (all_done) break;
+            }
+            const hipError_t e = hipStreamSynchronize(stream);   // launches behind the last stop return at once
+            for (S* s : m) s->run_stop = nullptr;
+            if (!rc && e != hipSuccess) { err = std::string("run_solver: ") + hipGetErrorString(e); rc = BDDMMA_ERR_DEVICE; }
+            const int rc2 = join_out();
+            if (rc || rc2) return rc ? rc : rc2;
+            for (uint32_t j = 0; j < n; ++j) {
+                const uint64_t st = hr[j].state;
+                if ((st >> 56) == 0 && (st & MASK) < queued) {
+                    err = "run_solver: queued iterations of batch member " + std::to_string(order[j]) + " did not complete";
+                    return BDDMMA_ERR_DEVICE;
+                }
+            }
+        }
+        const double seconds = elapsed();
+        for (uint32_t j = 0; j < n; ++j) {
+            S* s = m[order[j]];
+            const uint64_t st = max_iter > 0 ? ((volatile RunHost*)h_run)[j].state : 0;
+            const uint64_t done = st & MASK;
+            const double lb_final = done ? ((volatile RunHost*)h_run)[j].lb[(done - 1) % RUN_RING] : lb_initial[order[j]];
+            if (done) {  // the device's bound of the last iteration that ran is lower_bound() of the state it left (same sum, same order)
+                s->lb_cache = lb_final;
+                s->lb_cached = true;
+            }
+            if (res) {
+                bddmma_run_result& r = res[order[j]];
+                r.iterations = done;
+                r.lb_initial = lb_initial[order[j]];
+                r.lb_final = lb_final;
+                r.seconds = seconds;
+                r.stop_reason = (int32_t)(st >> 56);
+            }
+        }
+        return BDDMMA_OK;
+    }
+};
+
+}  // namespace bddmma

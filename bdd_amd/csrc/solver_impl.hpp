@@ -1098,23 +1098,30 @@ struct SolverT final : SolverBase {
     // ---- instances that fit one workgroup: n iterations inside one launch (kernels/small.hpp).  Not while event pairs are wanted per launch
     // (profiling) or an L-BFGS wrapper wants x in layer order from the backward sweeps.
     bool small_usable() const { return small_ok && !profiling && d_x_layer == nullptr; }
-    int launch_small(REAL omega, uint32_t n, const RunStep& rstep)
+    // the host-side state after a launch of whole iterations: what the last iteration's four launches leave (mma_forward, exchange,
+    // mma_backward, exchange); the costs-to-terminal have changed, so the cached bound is stale
+    void small_launched()
     {
-        int rc;
-        if (!bwd_valid && (rc = backward_run())) return rc;  // bdd_cuda_parallel_mma.cu:211-212, as mma_forward
         lb_cached = false;
         ++lb_gen;
-        const DevPtrs<REAL> d = ptrs(d_delta_lay);
-        const PackDev pk = pdev(nb_, 0, 0);
-        hipLaunchKernelGGL(kern.small.fn, dim3(1), dim3(64 * small_nw), kern.small.lds, stream, small, d, pk, omega, n, rstep);
-        HIPCHK(hipGetLastError());
-        // the state the last iteration's four launches leave (mma_forward, exchange, mma_backward, exchange)
         x_layer_valid = false;
         fwd_valid = false;
         bwd_valid = true;
         delta_var_valid = false;
+    }
+    int launch_small(REAL omega, uint32_t n, const RunStep& rstep)
+    {
+        int rc;
+        if (!bwd_valid && (rc = backward_run())) return rc;  // bdd_cuda_parallel_mma.cu:211-212, as mma_forward
+        const DevPtrs<REAL> d = ptrs(d_delta_lay);
+        const PackDev pk = pdev(nb_, 0, 0);
+        hipLaunchKernelGGL(kern.small.fn, dim3(1), dim3(64 * small_nw), kern.small.lds, stream, small, d, pk, omega, n, rstep);
+        HIPCHK(hipGetLastError());
+        small_launched();
         return BDDMMA_OK;
     }
+    // the same launch as an item of a batch (solver_bt.hpp: one workgroup per member of BatchT); the run_solver fields are the batch's
+    SmallItem<REAL> small_item() const { return SmallItem<REAL>{small, ptrs(d_delta_lay), pdev(nb_, 0, 0), RunStep{d_lb_partial, nb_.n_packs + wb_.n_packs + hb_.n_packs, nullptr, nullptr}}; }
     int iterations(double omega, uint64_t n) override
     {
         HIPCHK(hipSetDevice(device));

@@ -566,6 +566,64 @@ class bdd_hip_lbfgs:
                    self.solver._h)
 
 
+class bdd_hip_batch:
+    """Solvers whose instances fit one workgroup each (fused_small()), run together: one workgroup per member in one launch instead of
+    one launch per solver (include/bdd_mma.h: bddmma_batch_*).  The solvers are borrowed — the batch keeps them alive, and they stay
+    usable on their own between its calls; a call behaves as if it had been made on each member in turn."""
+
+    def __init__(self, solvers):
+        self.solvers = list(solvers)
+        self._L = capi.lib()
+        n = len(self.solvers)
+        arr = (C.c_void_p * max(n, 1))(*[s._h for s in self.solvers])
+        h = C.c_void_p()
+        self._check(self._L.bddmma_batch_create(C.byref(h), arr if n else None, n), None)
+        self._h = h
+
+    def _check(self, rc, h):
+        if rc != capi.OK:
+            msg = self._L.bddmma_batch_last_error(h)
+            raise capi.BddMmaError(f"bdd_mma error {rc}: {msg.decode() if msg else ''}")
+
+    def close(self):
+        """release the batch (never its members); call before closing a member"""
+        if getattr(self, "_h", None):
+            self._L.bddmma_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return int(self._L.bddmma_batch_size(self._h))
+
+    def iterations(self, n, omega=0.5):
+        self._check(self._L.bddmma_batch_iterations(self._h, float(omega), int(n)), self._h)
+
+    def time_iterations(self, n, omega=0.5) -> float:
+        """iterations(n) between hipEvents on the batch's stream (first launch to last): elapsed device milliseconds"""
+        ms = C.c_double()
+        self._check(self._L.bddmma_batch_time_iterations(self._h, float(omega), int(n), C.byref(ms)), self._h)
+        return ms.value
+
+    def run_solver(self, max_iter=1000, tolerance=1e-6, improvement_slope=1e-9, time_limit=3600.0):
+        """run_solver() of every member, each stopping on its own criterion: a list of dicts shaped like run_solver()'s; `seconds` is
+        the batch's wall time, the time limit one clock for the whole batch"""
+        res = (capi.RunResult * len(self.solvers))()
+        self._check(self._L.bddmma_batch_run_solver(self._h, int(max_iter), float(tolerance), float(improvement_slope), float(time_limit), res),
+                    self._h)
+        return [dict(iterations=int(r.iterations), lb_initial=r.lb_initial, lb_final=r.lb_final, seconds=r.seconds,
+                     stop_reason=int(r.stop_reason)) for r in res]
+
+    def lower_bounds(self):
+        out = np.empty(len(self.solvers), dtype=np.float64)
+        self._check(self._L.bddmma_batch_lower_bounds(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
+        return out
+
+
 def run_solver(solver, max_iter=1000, tolerance=1e-6, improvement_slope=1e-9, time_limit=3600.0, verbose=False,
                lbfgs: bdd_hip_lbfgs = None, host_loop: bool = False):
     """run_solver<SOLVER>() of include/run_solver_util.h:10-77 (executed inside the library).  host_loop: the reference's literal loop

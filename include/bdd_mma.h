@@ -435,6 +435,42 @@ int bddmma_run_solver(bddmma_solver* s, bddmma_lbfgs* lbfgs_or_null, uint64_t ma
 int bddmma_run_solver_host_loop(bddmma_solver* s, bddmma_lbfgs* lbfgs_or_null, uint64_t max_iter, double tolerance,
                                 double improvement_slope, double time_limit, int verbose, bddmma_run_result* res);
 
+/* ---- batches of one-workgroup instances ------------------------------------
+ * Callers with instances that fit one workgroup (bddmma_fused_small == 1) usually have many of them.  A batch runs its members'
+ * iterations concurrently, one workgroup per member in one launch per kernel instantiation present, instead of one launch of one
+ * workgroup per handle.  The members are BORROWED: the batch never owns or destroys them, they stay usable on their own between the
+ * batch's calls, and every member must outlive the batch — destroying a member before its batch is the caller's error (only
+ * bddmma_batch_destroy and bddmma_batch_size may be called on such a batch).
+ * Ordering: a batch call behaves as if the same call had been made on each member in turn.  It is ordered after everything already
+ * queued on every member's stream, and everything queued on a member afterwards is ordered after it (events between the batch's
+ * stream and the members' streams; the host does not synchronise).  Results are bit-equal to the per-member calls.
+ * bddmma_batch_create: BDDMMA_ERR_INVALID_ARGUMENT for a null pointer, n == 0 or a handle listed twice; BDDMMA_ERR_UNSUPPORTED for a
+ * member that is not bddmma_fused_small or that differs from member 0 in precision or device; BDDMMA_ERR_STATE for a member with an
+ * L-BFGS wrapper attached or profiling on.  All of these are decided before any device call; bddmma_batch_last_error(NULL) names the
+ * member index and the reason.
+ * Every other call re-checks the members' state before it launches anything: when a member has since got an L-BFGS wrapper (attached
+ * now or earlier: its backward sweeps then write x per layer), has profiling on or is inside bddmma_run_solver, the call returns
+ * BDDMMA_ERR_STATE and every member is left untouched. */
+typedef struct bddmma_batch bddmma_batch;
+int bddmma_batch_create(bddmma_batch** out, bddmma_solver* const* members, uint64_t n);
+void bddmma_batch_destroy(bddmma_batch* b);
+/* error text of the last failed call on the batch; b == NULL: of the last failed bddmma_batch_create of this thread */
+const char* bddmma_batch_last_error(const bddmma_batch* b);
+uint64_t bddmma_batch_size(const bddmma_batch* b);
+/* bddmma_iterations(member, omega, n) for every member */
+int bddmma_batch_iterations(bddmma_batch* b, double omega, uint64_t n);
+/* bddmma_run_solver(member, NULL, max_iter, tolerance, improvement_slope, time_limit, 0, &res[i]) for every member i: each member's tests
+ * run inside its workgroup against its own control block and each stops on its own criterion; the host relaunches chunks of iterations
+ * until every member has stopped or reached max_iter.  res (bddmma_batch_size entries, may be NULL): member i's iterations, bounds and
+ * stop reason; `seconds` is the batch's wall time for all members.  The time limit is one clock for the whole batch. */
+int bddmma_batch_run_solver(bddmma_batch* b, uint64_t max_iter, double tolerance, double improvement_slope, double time_limit,
+                            bddmma_run_result* res);
+/* bddmma_batch_iterations bracketed by hipEvents on the batch's stream, from its first launch to its last; *ms = elapsed device time.
+ * Waits for the launches (the measurement counterpart of bddmma_time_iterations). */
+int bddmma_batch_time_iterations(bddmma_batch* b, double omega, uint64_t n, double* ms);
+/* out[i] = bddmma_lower_bound(member i); the members' reductions are in flight together and the host collects them once */
+int bddmma_batch_lower_bounds(bddmma_batch* b, double* out);
+
 /* ---- primal rounding (src/bdd_solver/incremental_mm_agreement_rounding_cuda.cu:333-372) ------------------
  * incremental_mm_agreement_rounding_cuda(s, init_delta, delta_growth_rate, num_itr_lb, verbose, num_rounds):
  * perturbs the costs towards the sign of the min-marginal differences until they agree in every BDD.
