@@ -27,6 +27,7 @@
 
 // The kernels by family (round 5: one 4 000-line header before); order matters — each part uses what the ones before it define.
 #include "kernels/common.hpp"
+#include "kernels/stream.hpp"
 #include "kernels/narrow.hpp"
 #include "kernels/resident.hpp"
 #include "kernels/narrow2.hpp"

@@ -693,22 +693,12 @@ __device__ __forceinline__ void bwd_narrow_body(const DevPtrs<REAL>& d, const Pa
             store_vals<R>(t, Tp, nb, o[0] - o[1], lane, pk.nt_potentials);
             wave_sync();
             cur ^= 1;
-#pragma unroll
-            for (int i = 0; i < 2 * D + 1; ++i) o[i] = o[i + 1];
-            o[2 * D + 1] = o_new;
+            // ---- rotate the pipeline registers
+            shift(o, o_new);
             lcur = l_next;
-#pragma unroll
-            for (int i = 0; i < 2 * D; ++i)
-#pragma unroll
-                for (int r = 0; r < R; ++r) wr[i][r] = wr[i + 1][r];
-#pragma unroll
-            for (int i = 0; i < D; ++i) Lr[i] = Lr[i + 1];
-            if (NEED_F) {
-#pragma unroll
-                for (int i = 0; i < D + 1; ++i)
-#pragma unroll
-                    for (int r = 0; r < R; ++r) fr[i][r] = fr[i + 1][r];
-            }
+            shift(wr);
+            shift(Lr);
+            if (NEED_F) shift(fr);
         };
         while (q >= qs + HOP_UNROLL) {
 #pragma unroll

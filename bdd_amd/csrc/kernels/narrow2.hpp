@@ -457,24 +457,12 @@ __device__ __forceinline__ void bwd_narrow2_body(const DevPtrs<REAL>& d, const P
             store_vals<R>(t, Tp, nb, o[0] - o[1], lane, pk.nt_potentials);
             wave_sync();
             cur ^= 1u;
-#pragma unroll
-            for (int i = 0; i < 2 * D + 1; ++i) o[i] = o[i + 1];
-            o[2 * D + 1] = o_new;
-#pragma unroll
-            for (int i = 0; i < D + 1; ++i) lb[i] = lb[i + 1];
-            lb[D + 1] = l_next;
-#pragma unroll
-            for (int i = 0; i < 2 * D; ++i)
-#pragma unroll
-                for (int r = 0; r < R; ++r) rc[i][r] = rc[i + 1][r];
-#pragma unroll
-            for (int i = 0; i < D; ++i)
-#pragma unroll
-                for (int r = 0; r < R; ++r) Lr[i][r] = Lr[i + 1][r];
-#pragma unroll
-            for (int i = 0; i < D + 1; ++i)
-#pragma unroll
-                for (int r = 0; r < R; ++r) fr[i][r] = fr[i + 1][r];
+            // ---- rotate the pipeline registers
+            shift(o, o_new);
+            shift(lb, l_next);
+            shift(rc);
+            shift(Lr);
+            shift(fr);
         };
         while (q >= qs + HOP_UNROLL) {
 #pragma unroll

@@ -258,23 +258,12 @@ __device__ __forceinline__ void fwd_narrow3_body(const DevPtrs<REAL>& d, const P
         wave_sync();
         cur ^= 1u;
         // ---- rotate the pipeline registers
-#pragma unroll
-        for (int i = 0; i < 2 * D + 2; ++i) o[i] = o[i + 1];
-        o[2 * D + 2] = o_new;
-#pragma unroll
-        for (int i = 0; i < D + 1; ++i) lb[i] = lb[i + 1];
-        lb[D + 1] = l_next;
-#pragma unroll
-        for (int i = 0; i < 2 * D; ++i) rc[i] = rc[i + 1];
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            Lr[i] = Lr[i + 1];
-            tr[i] = tr[i + 1];
-        }
-        if constexpr (OV) {
-#pragma unroll
-            for (int i = 0; i < D; ++i) Wr[i] = Wr[i + 1];
-        }
+        shift(o, o_new);
+        shift(lb, l_next);
+        shift(rc);
+        shift(Lr);
+        shift(tr);
+        shift(Wr);
         ++q;
     };
     while (q + HOP_UNROLL <= qe) {
@@ -467,23 +456,13 @@ __device__ __forceinline__ void bwd_narrow3_body(const DevPtrs<REAL>& d, const P
 #endif
         wave_sync();
         cur ^= 1u;
-#pragma unroll
-        for (int i = 0; i < 2 * D + 1; ++i) o[i] = o[i + 1];
-        o[2 * D + 1] = o_new;
-#pragma unroll
-        for (int i = 0; i < D + 1; ++i) lb[i] = lb[i + 1];
-        lb[D + 1] = l_next;
-#pragma unroll
-        for (int i = 0; i < 2 * D; ++i) rc[i] = rc[i + 1];
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            Lr[i] = Lr[i + 1];
-            fr[i] = fr[i + 1];
-        }
-        if constexpr (OV) {
-#pragma unroll
-            for (int i = 0; i < D; ++i) Wr[i] = Wr[i + 1];
-        }
+        // ---- rotate the pipeline registers
+        shift(o, o_new);
+        shift(lb, l_next);
+        shift(rc);
+        shift(Lr);
+        shift(fr);
+        shift(Wr);
     };
     while (q >= qs + HOP_UNROLL) {
 #pragma unroll
