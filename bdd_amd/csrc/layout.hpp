@@ -196,29 +196,59 @@ inline void set_layout_scalars(HostLayout& L, const LayoutScalars& s)
     L.ex.entry_by_var = s.entry_by_var != 0;
     L.res.ok = s.res_ok != 0; L.res.max_slots = s.res_max_slots; L.res.max_layers = s.res_max_layers;
 }
-// every array create_solver consumes, with a stable id (the checkpoint format); v(id, vector&)
+// every array create_solver consumes has a stable id: the checkpoint format, SolverT::dev_fields, and bddmma_layout_copy(l, 100 + id, ..)
+enum : int {
+    LAY_NARROW_WORDS = 1, LAY_NARROW_WORD_OFF = 2, LAY_WIDE_WORDS = 3,
+    LAY_LAYER_VAR = 4, LAY_LAYER_BDD = 5, LAY_NUM_BDDS_PER_VAR = 6, LAY_VAR_PTR = 7, LAY_VAR_LAYERS = 8, LAY_BDD_ROOT_SLOT = 9,
+    LAY_NARROW_PACK_HOP_PTR = 10, LAY_NARROW_HOP_NODE_OFF = 11, LAY_NARROW_HOP_LAYER_OFF = 12, LAY_NARROW_PACK_STEPS = 13,
+    LAY_WIDE_PACK_HOP_PTR = 14, LAY_WIDE_HOP_NODE_OFF = 15, LAY_WIDE_HOP_LAYER_OFF = 16, LAY_WIDE_PACK_STEPS = 17,
+    LAY_HUGE_PACK_HOP_PTR = 18, LAY_HUGE_HOP_NODE_OFF = 19, LAY_HUGE_HOP_LAYER_OFF = 20, LAY_HUGE_PACK_STEPS = 21,
+    LAY_EVAR = 22, LAY_BVAR = 23, LAY_LPOS = 24, LAY_VPOS = 25, LAY_BIN_PTR = 26,
+    LAY_PACK_GROUP_PTR = 27, LAY_GRP_LAYER_OFF = 28, LAY_GRP_HOP_END = 29,
+    LAY_QUAD_ROUND_PTR = 30, LAY_CS_PTR = 31, LAY_CS_ENTRY = 32, LAY_CS_SLOT = 33,
+    LAY_PACK_HDR = 34, LAY_QUAD_HDR = 35,
+    LAY_NODES_PER_HOP = 36, LAY_LAYERS_PER_HOP = 37,  // host-side statistics: never uploaded
+    LAY_NARROW_HOP_ROOT = 38, LAY_WIDE_HOP_ROOT = 39,
+    LAYOUT_ARRAY_IDS = 40
+};
+// a pack set's four arrays follow its pack_hop_ptr id (SolverT::upload_packs)
+enum : int { LAY_SET_HOP_NODE_OFF = 1, LAY_SET_HOP_LAYER_OFF = 2, LAY_SET_PACK_STEPS = 3 };
+static_assert(LAY_NARROW_HOP_NODE_OFF == LAY_NARROW_PACK_HOP_PTR + LAY_SET_HOP_NODE_OFF && LAY_WIDE_HOP_LAYER_OFF == LAY_WIDE_PACK_HOP_PTR + LAY_SET_HOP_LAYER_OFF &&
+              LAY_HUGE_PACK_STEPS == LAY_HUGE_PACK_HOP_PTR + LAY_SET_PACK_STEPS, "pack set ids");
+// v(id, vector&), in checkpoint order
 template <typename LAYOUT, typename V>
 void visit_layout_arrays(LAYOUT& L, V&& v)
 {
-    v(1, L.narrow_words_unique); v(2, L.narrow_word_off); v(3, L.wide_words);
-    v(4, L.layer_var); v(5, L.layer_bdd); v(6, L.num_bdds_per_var); v(7, L.var_ptr); v(8, L.var_layers); v(9, L.bdd_root_slot);
-    v(10, L.narrow.pack_hop_ptr); v(11, L.narrow.hop_node_off); v(12, L.narrow.hop_layer_off); v(13, L.narrow.pack_steps);
-    v(14, L.wide.pack_hop_ptr); v(15, L.wide.hop_node_off); v(16, L.wide.hop_layer_off); v(17, L.wide.pack_steps);
-    v(18, L.huge.pack_hop_ptr); v(19, L.huge.hop_node_off); v(20, L.huge.hop_layer_off); v(21, L.huge.pack_steps);
-    v(22, L.ex.evar); v(23, L.ex.bvar); v(24, L.ex.lpos); v(25, L.ex.vpos); v(26, L.ex.bin_ptr);
-    v(27, L.ex.pack_group_ptr); v(28, L.ex.grp_layer_off); v(29, L.ex.grp_hop_end);
-    v(30, L.ex.quad_round_ptr); v(31, L.ex.cs_ptr); v(32, L.ex.cs_entry); v(33, L.ex.cs_slot);
-    v(34, L.res.pack_hdr); v(35, L.res.quad_hdr);
-    v(36, L.nodes_per_hop); v(37, L.layers_per_hop);
-    v(38, L.narrow.hop_root); v(39, L.wide.hop_root);
+    v(LAY_NARROW_WORDS, L.narrow_words_unique); v(LAY_NARROW_WORD_OFF, L.narrow_word_off); v(LAY_WIDE_WORDS, L.wide_words);
+    v(LAY_LAYER_VAR, L.layer_var); v(LAY_LAYER_BDD, L.layer_bdd); v(LAY_NUM_BDDS_PER_VAR, L.num_bdds_per_var);
+    v(LAY_VAR_PTR, L.var_ptr); v(LAY_VAR_LAYERS, L.var_layers); v(LAY_BDD_ROOT_SLOT, L.bdd_root_slot);
+    v(LAY_NARROW_PACK_HOP_PTR, L.narrow.pack_hop_ptr); v(LAY_NARROW_HOP_NODE_OFF, L.narrow.hop_node_off);
+    v(LAY_NARROW_HOP_LAYER_OFF, L.narrow.hop_layer_off); v(LAY_NARROW_PACK_STEPS, L.narrow.pack_steps);
+    v(LAY_WIDE_PACK_HOP_PTR, L.wide.pack_hop_ptr); v(LAY_WIDE_HOP_NODE_OFF, L.wide.hop_node_off);
+    v(LAY_WIDE_HOP_LAYER_OFF, L.wide.hop_layer_off); v(LAY_WIDE_PACK_STEPS, L.wide.pack_steps);
+    v(LAY_HUGE_PACK_HOP_PTR, L.huge.pack_hop_ptr); v(LAY_HUGE_HOP_NODE_OFF, L.huge.hop_node_off);
+    v(LAY_HUGE_HOP_LAYER_OFF, L.huge.hop_layer_off); v(LAY_HUGE_PACK_STEPS, L.huge.pack_steps);
+    v(LAY_EVAR, L.ex.evar); v(LAY_BVAR, L.ex.bvar); v(LAY_LPOS, L.ex.lpos); v(LAY_VPOS, L.ex.vpos); v(LAY_BIN_PTR, L.ex.bin_ptr);
+    v(LAY_PACK_GROUP_PTR, L.ex.pack_group_ptr); v(LAY_GRP_LAYER_OFF, L.ex.grp_layer_off); v(LAY_GRP_HOP_END, L.ex.grp_hop_end);
+    v(LAY_QUAD_ROUND_PTR, L.ex.quad_round_ptr); v(LAY_CS_PTR, L.ex.cs_ptr); v(LAY_CS_ENTRY, L.ex.cs_entry); v(LAY_CS_SLOT, L.ex.cs_slot);
+    v(LAY_PACK_HDR, L.res.pack_hdr); v(LAY_QUAD_HDR, L.res.quad_hdr);
+    v(LAY_NODES_PER_HOP, L.nodes_per_hop); v(LAY_LAYERS_PER_HOP, L.layers_per_hop);
+    v(LAY_NARROW_HOP_ROOT, L.narrow.hop_root); v(LAY_WIDE_HOP_ROOT, L.wide.hop_root);
 }
-constexpr int LAYOUT_ARRAY_IDS = 40;
-// the ids above that code outside the checkpoint names (SolverT::sm_prepare fetches these arrays back from the device)
-enum : int {
-    LAY_NARROW_WORDS = 1, LAY_NARROW_WORD_OFF = 2, LAY_WIDE_WORDS = 3,
-    LAY_NARROW_PACK_HOP_PTR = 10, LAY_NARROW_HOP_NODE_OFF = 11, LAY_WIDE_PACK_HOP_PTR = 14, LAY_WIDE_HOP_NODE_OFF = 15,
-    LAY_HUGE_PACK_HOP_PTR = 18, LAY_HUGE_HOP_NODE_OFF = 19
+
+// Checksum of a checkpoint's layout section: four independent multiply-rotate lanes over 8-byte words, so that a 240 MB section costs
+// ~20 ms; byte order is the host's (little endian on every target of this library), a foreign-endian file fails the magic / header test.
+struct Checksum {
+    uint64_t lane[4] = {0x9E3779B97F4A7C15ull, 0xC2B2AE3D27D4EB4Full, 0x165667B19E3779F9ull, 0x27D4EB2F165667C5ull};
+    uint64_t n = 0;
+    void add(const void* p, size_t bytes);
+    uint64_t value() const;
 };
+// Headers of the resident sweeps (struct Resident): a function of the narrow pack set, the structure templates, the stage groups and the
+// cooperative staging tables, which must be complete.  The last phase of build_layout; layout_plausible recomputes them with it.
+void build_resident_headers(HostLayout& L);
+// Consistency of a layout read from a file: false and the reason in `why` (layout.cpp)
+bool layout_plausible(const HostLayout& L, std::string& why);
 
 // Host threads of the layout build: 0 = automatic (BDDMMA_THREADS, else min(cores, 32)).  Processes that build several layouts at once
 // (one per device slot: bddmma_host::solve_batch / bench_set_cover) share the cores through this.

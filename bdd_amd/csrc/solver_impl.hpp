@@ -268,8 +268,8 @@ struct SolverT final : SolverBase {
         hipError_t e = hipSuccess;
         visit_layout_arrays(H, [&](int id, auto& vec) {
             using T = typename std::remove_reference_t<decltype(vec)>::value_type;
-            if (id == 36) { vec.assign(nodes_per_hop.begin(), nodes_per_hop.end()); return; }
-            if (id == 37) { vec.assign(layers_per_hop.begin(), layers_per_hop.end()); return; }
+            if (id == LAY_NODES_PER_HOP) { vec.assign(nodes_per_hop.begin(), nodes_per_hop.end()); return; }
+            if (id == LAY_LAYERS_PER_HOP) { vec.assign(layers_per_hop.begin(), layers_per_hop.end()); return; }
             const DevField& f = dev_fields[id];
             vec.resize(f.count);
             if (f.count && e == hipSuccess) e = hipMemcpyAsync(vec.data(), f.ptr, f.count * sizeof(T), hipMemcpyDeviceToHost, stream);
@@ -283,9 +283,9 @@ struct SolverT final : SolverBase {
         b.n_packs = ps.n_packs();
         int rc;
         if ((rc = upload(&b.pack_hop_ptr, ps.pack_hop_ptr, id0))) return rc;
-        if ((rc = upload(&b.hop_node_off, ps.hop_node_off, id0 + 1))) return rc;
-        if ((rc = upload(&b.hop_layer_off, ps.hop_layer_off, id0 + 2))) return rc;
-        if ((rc = upload(&b.pack_steps, ps.pack_steps, id0 + 3))) return rc;
+        if ((rc = upload(&b.hop_node_off, ps.hop_node_off, id0 + LAY_SET_HOP_NODE_OFF))) return rc;
+        if ((rc = upload(&b.hop_layer_off, ps.hop_layer_off, id0 + LAY_SET_HOP_LAYER_OFF))) return rc;
+        if ((rc = upload(&b.pack_steps, ps.pack_steps, id0 + LAY_SET_PACK_STEPS))) return rc;
         return BDDMMA_OK;
     }
 
@@ -350,29 +350,29 @@ struct SolverT final : SolverBase {
             }
         }
         int rc;
-        if ((rc = upload(&d_nwords, L.narrow_words_unique, 1))) return rc;
+        if ((rc = upload(&d_nwords, L.narrow_words_unique, LAY_NARROW_WORDS))) return rc;
         n_nwords = (uint32_t)L.narrow_words_unique.size();
-        if ((rc = upload(&d_pack_word_off, L.narrow_word_off, 2))) return rc;
-        if ((rc = upload(&d_wwords, L.wide_words, 3))) return rc;
-        if ((rc = upload(&d_var, L.layer_var, 4))) return rc;
-        if ((rc = upload(&d_bdd, L.layer_bdd, 5))) return rc;
-        if ((rc = upload(&d_nbdds, L.num_bdds_per_var, 6))) return rc;
-        if ((rc = upload(&d_var_ptr, L.var_ptr, 7))) return rc;
-        if ((rc = upload(&d_var_layers, L.var_layers, 8))) return rc;
-        if ((rc = upload(&d_root_slot, L.bdd_root_slot, 9))) return rc;
-        if ((rc = upload_packs(nb_, L.narrow, 10))) return rc;
+        if ((rc = upload(&d_pack_word_off, L.narrow_word_off, LAY_NARROW_WORD_OFF))) return rc;
+        if ((rc = upload(&d_wwords, L.wide_words, LAY_WIDE_WORDS))) return rc;
+        if ((rc = upload(&d_var, L.layer_var, LAY_LAYER_VAR))) return rc;
+        if ((rc = upload(&d_bdd, L.layer_bdd, LAY_LAYER_BDD))) return rc;
+        if ((rc = upload(&d_nbdds, L.num_bdds_per_var, LAY_NUM_BDDS_PER_VAR))) return rc;
+        if ((rc = upload(&d_var_ptr, L.var_ptr, LAY_VAR_PTR))) return rc;
+        if ((rc = upload(&d_var_layers, L.var_layers, LAY_VAR_LAYERS))) return rc;
+        if ((rc = upload(&d_root_slot, L.bdd_root_slot, LAY_BDD_ROOT_SLOT))) return rc;
+        if ((rc = upload_packs(nb_, L.narrow, LAY_NARROW_PACK_HOP_PTR))) return rc;
         if (L.narrow.hop_root.size() + 1 != L.narrow.hop_node_off.size() && !L.narrow.hop_node_off.empty()) {
             err = "narrow hop_root table does not match the hop records";
             return BDDMMA_ERR_INVALID_ARGUMENT;
         }
-        if ((rc = upload(&nb_.hop_root, L.narrow.hop_root, 38))) return rc;
-        if ((rc = upload_packs(wb_, L.wide, 14))) return rc;
+        if ((rc = upload(&nb_.hop_root, L.narrow.hop_root, LAY_NARROW_HOP_ROOT))) return rc;
+        if ((rc = upload_packs(wb_, L.wide, LAY_WIDE_PACK_HOP_PTR))) return rc;
         if (L.wide.hop_root.size() + 1 != L.wide.hop_node_off.size() && !L.wide.hop_node_off.empty()) {
             err = "wide hop_root table does not match the hop records";
             return BDDMMA_ERR_INVALID_ARGUMENT;
         }
-        if ((rc = upload(&wb_.hop_root, L.wide.hop_root, 39))) return rc;
-        if ((rc = upload_packs(hb_, L.huge, 18))) return rc;
+        if ((rc = upload(&wb_.hop_root, L.wide.hop_root, LAY_WIDE_HOP_ROOT))) return rc;
+        if ((rc = upload_packs(hb_, L.huge, LAY_HUGE_PACK_HOP_PTR))) return rc;
         huge_pack_width = L.huge_pack_width;
         if (hb_.n_packs && (rc = dalloc(&d_huge_scratch, (size_t)hb_.n_packs * wide_lds_bytes(sizeof(REAL), huge_pack_width, true)))) return rc;
         wide_slot_base = L.narrow_slots;
@@ -384,18 +384,18 @@ struct SolverT final : SolverBase {
         if ((rc = dalloc(&d_mm_binned, n_layers))) return rc;
         if ((rc = dalloc(&d_delta_lay, 2 * n_layers))) return rc;
         if ((rc = dalloc(&d_delta_lay_c, 2 * n_layers))) return rc;
-        if ((rc = upload(&d_evar, L.ex.evar, 22))) return rc;
-        if ((rc = upload(&d_bvar, L.ex.bvar, 23))) return rc;
-        if ((rc = upload(&d_lpos, L.ex.lpos, 24))) return rc;
-        if ((rc = upload(&d_vpos, L.ex.vpos, 25))) return rc;
-        if ((rc = upload(&d_bin_ptr, L.ex.bin_ptr, 26))) return rc;
-        if ((rc = upload(&d_pack_group_ptr, L.ex.pack_group_ptr, 27))) return rc;
-        if ((rc = upload(&d_grp_layer_off, L.ex.grp_layer_off, 28))) return rc;
-        if ((rc = upload(&d_grp_hop_end, L.ex.grp_hop_end, 29))) return rc;
-        if ((rc = upload(&d_quad_round_ptr, L.ex.quad_round_ptr, 30))) return rc;
-        if ((rc = upload(&d_cs_ptr, L.ex.cs_ptr, 31))) return rc;
-        if ((rc = upload(&d_cs_entry, L.ex.cs_entry, 32))) return rc;
-        if ((rc = upload(&d_cs_slot, L.ex.cs_slot, 33))) return rc;
+        if ((rc = upload(&d_evar, L.ex.evar, LAY_EVAR))) return rc;
+        if ((rc = upload(&d_bvar, L.ex.bvar, LAY_BVAR))) return rc;
+        if ((rc = upload(&d_lpos, L.ex.lpos, LAY_LPOS))) return rc;
+        if ((rc = upload(&d_vpos, L.ex.vpos, LAY_VPOS))) return rc;
+        if ((rc = upload(&d_bin_ptr, L.ex.bin_ptr, LAY_BIN_PTR))) return rc;
+        if ((rc = upload(&d_pack_group_ptr, L.ex.pack_group_ptr, LAY_PACK_GROUP_PTR))) return rc;
+        if ((rc = upload(&d_grp_layer_off, L.ex.grp_layer_off, LAY_GRP_LAYER_OFF))) return rc;
+        if ((rc = upload(&d_grp_hop_end, L.ex.grp_hop_end, LAY_GRP_HOP_END))) return rc;
+        if ((rc = upload(&d_quad_round_ptr, L.ex.quad_round_ptr, LAY_QUAD_ROUND_PTR))) return rc;
+        if ((rc = upload(&d_cs_ptr, L.ex.cs_ptr, LAY_CS_PTR))) return rc;
+        if ((rc = upload(&d_cs_entry, L.ex.cs_entry, LAY_CS_ENTRY))) return rc;
+        if ((rc = upload(&d_cs_slot, L.ex.cs_slot, LAY_CS_SLOT))) return rc;
         wpb = L.ex.waves_per_block;
         entry_by_var = L.ex.entry_by_var;
         {   // balance of the narrow packs' hop counts over contiguous eighths of the pack sequence (see xcd_chunk)
@@ -476,8 +476,8 @@ struct SolverT final : SolverBase {
         }
         // resident sweeps: chosen when every narrow pack fits its wave's LDS slice and the instance is small enough that the streaming
         // kernels are latency-bound (few waves per SIMD); resident_sweeps = 1 turns them off, = 2 forces them on
-        if ((rc = upload(&d_pack_hdr, L.res.pack_hdr, 34))) return rc;
-        if ((rc = upload(&d_quad_hdr, L.res.quad_hdr, 35))) return rc;
+        if ((rc = upload(&d_pack_hdr, L.res.pack_hdr, LAY_PACK_HDR))) return rc;
+        if ((rc = upload(&d_quad_hdr, L.res.quad_hdr, LAY_QUAD_HDR))) return rc;
         res_hdr_ok = L.res.ok && nb_.n_packs > 0;
         if (nb_.n_packs && L.res.ok) {
             res_ns = (L.res.max_slots + 255) / 256 * 256;

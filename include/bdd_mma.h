@@ -540,6 +540,9 @@ int bddmma_layout_create(bddmma_layout** out, const bddmma_instruction* instr, c
 int bddmma_layout_create_for_chip(bddmma_layout** out, const bddmma_instruction* instr, const uint64_t* bdd_delims,
                                   uint64_t n_bdds, const bddmma_options* opts, int real_size, uint32_t n_cus, uint32_t lds_bytes_per_cu);
 void bddmma_layout_destroy(bddmma_layout* l);
+/* what / which: the codes listed in csrc/capi.cpp.  From 100 on they address the arrays of the checkpoint format by their id (csrc/layout.hpp:
+ * LAY_*, ids 1-39): bddmma_layout_size(l, 100 + id) is the array's element count and bddmma_layout_copy(l, 100 + id, out) copies it
+ * (element sizes as the format stores them: 8 bytes for ids 3, 36, 37; 1 for 13, 17, 21; 2 for 23, 33, 38, 39; 4 for the rest). */
 uint64_t bddmma_layout_size(const bddmma_layout* l, int what);
 int bddmma_layout_copy(const bddmma_layout* l, int which, void* out);
 /* The per-lane records of the second-generation resident sweeps (derived data, csrc/layout.hpp: Res2Records) for values of real_size
