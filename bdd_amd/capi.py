@@ -128,6 +128,8 @@ SIGNATURES = {
     "bddmma_save": (_I, [_V, C.c_char_p]),
     "bddmma_load": (_I, [C.POINTER(_V), _I, C.c_char_p]),
     "bddmma_synchronize": (_I, [_V]),
+    "bddmma_stream_wait": (_I, [_V, _V]),
+    "bddmma_stream_signal": (_I, [_V, _V]),
     "bddmma_set_profiling": (_I, [_V, _I]),
     "bddmma_get_profile": (_I, [_V, C.POINTER(Profile)]),
     "bddmma_time_iterations": (_I, [_V, _D, _U64, C.POINTER(_D)]),

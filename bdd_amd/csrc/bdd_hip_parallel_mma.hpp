@@ -433,6 +433,11 @@ class bdd_hip_parallel_mma {
         s.h_ = h;
         return s;
     }
+    // Ordering against another stream of the solver's device (a hipStream_t as void*; nullptr: the default stream), without the host waiting:
+    // stream_wait — the solver's later work starts after everything queued on `hip_stream` so far; stream_signal — the reverse
+    // (bddmma_stream_wait / bddmma_stream_signal).  For device vectors that another stream writes, reads or frees.
+    void stream_wait(void* hip_stream) { check(bddmma_stream_wait(h_, hip_stream)); }
+    void stream_signal(void* hip_stream) { check(bddmma_stream_signal(h_, hip_stream)); }
     bddmma_solver* handle() { return h_; }
 
    private:

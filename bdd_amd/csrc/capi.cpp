@@ -658,6 +658,8 @@ int bddmma_load(bddmma_solver** out, int device, const char* path)
 }
 
 int bddmma_synchronize(bddmma_solver* s) { return guarded(s, [&](SolverBase* b) { return b->synchronize(); }); }
+int bddmma_stream_wait(bddmma_solver* s, void* hip_stream) { return guarded(s, [&](SolverBase* b) { return b->stream_wait((hipStream_t)hip_stream); }); }
+int bddmma_stream_signal(bddmma_solver* s, void* hip_stream) { return guarded(s, [&](SolverBase* b) { return b->stream_signal((hipStream_t)hip_stream); }); }
 int bddmma_set_profiling(bddmma_solver* s, int on) { return guarded(s, [&](SolverBase* b) { return b->set_profiling(on); }); }
 int bddmma_get_profile(bddmma_solver* s, bddmma_profile* out)
 {

@@ -703,6 +703,47 @@ __global__ void k_count_nonfinite(const REAL* __restrict__ v, uint32_t* __restri
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && !(v[i] > REAL(-__builtin_huge_val()) && v[i] < REAL(__builtin_huge_val()))) atomicAdd(cnt, 1u);   // NaN fails both tests
 }
+// The device arguments of one call (SolverT::gr_load_device: grad_learned_iterations' weights, omega_vec and three incoming gradients) in one
+// launch: array k is copied src[k] -> dst[k] (n values each) and cnt[k] receives the number of its values that are not finite or, where
+// bit k of `nonneg` is set (weights, omega), not in [0, inf); the caller zeroes cnt.  Grid-stride; 16-byte loads and stores for an array
+// whose two pointers are 16-byte aligned (the rest of it, and unaligned arrays, value by value); the counts are summed over the wave
+// first: one atomic per wave and array, and none where the wave found nothing.
+constexpr int LOAD_MAX_ARRAYS = 5;
+template <typename REAL>
+struct LoadArrays {
+    const REAL* src[LOAD_MAX_ARRAYS];
+    REAL* dst[LOAD_MAX_ARRAYS];
+    uint32_t n, count, nonneg;
+};
+template <typename REAL>
+__global__ void __launch_bounds__(256) k_load_checked(LoadArrays<REAL> a, uint32_t* __restrict__ cnt)
+{
+    constexpr uint32_t W = 16 / sizeof(REAL);
+    typedef REAL vec_t __attribute__((ext_vector_type(W)));
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    const REAL inf = REAL(__builtin_huge_val());
+    for (uint32_t k = 0; k < a.count; ++k) {
+        const REAL* src = a.src[k];
+        REAL* dst = a.dst[k];
+        const bool nonneg = (a.nonneg >> k) & 1u;
+        auto offends = [&](REAL v) -> uint32_t { return nonneg ? !(v >= REAL(0) && v < inf) : !(v > -inf && v < inf); };   // NaN fails both tests
+        uint32_t bad = 0;
+        const uint32_t nv = (((uintptr_t)src | (uintptr_t)dst) & 15u) == 0 ? a.n / W : 0u;
+        for (uint64_t i = tid; i < nv; i += stride) {   // (64-bit: i + stride may pass 2^32 before it passes n)
+            const vec_t x = reinterpret_cast<const vec_t*>(src)[i];
+            reinterpret_cast<vec_t*>(dst)[i] = x;
+#pragma unroll
+            for (uint32_t j = 0; j < W; ++j) bad += offends(x[j]);
+        }
+        for (uint64_t i = (uint64_t)nv * W + tid; i < a.n; i += stride) {
+            const REAL x = src[i];
+            dst[i] = x;
+            bad += offends(x);
+        }
+        for (int off = 32; off > 0; off >>= 1) bad += __shfl_down(bad, off);
+        if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&cnt[k], bad);
+    }
+}
 // grad_lower_bound_per_bdd (:387-416): the bound of a BDD is the cost of its solution x, so grad_hi = x * glb[bdd], grad_lo = (1 - x) * glb[bdd];
 // x is the arg-min path (char 0 / 1) or the smooth solution.  out_hi may be x itself (every thread reads its x first).
 template <typename REAL, typename XT>

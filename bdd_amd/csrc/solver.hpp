@@ -45,6 +45,7 @@ struct SolverBase {
     std::vector<int> ev_class;
     size_t ev_used = 0;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
+    hipEvent_t ev_order = nullptr;  // bddmma_stream_wait / _signal: timing disabled, created on first use
 
     virtual ~SolverBase() {}
     virtual int forward_run() = 0;
@@ -139,6 +140,10 @@ struct SolverBase {
     virtual int rounding_scratch(void** c0_dev, void** c1_dev) = 0;  // device vectors holding the last perturbation (REAL[n_vars] each)
 
     int synchronize();
+    // bddmma_stream_wait / bddmma_stream_signal: `stream` behind everything queued on `other` so far / the reverse, by an event; the host
+    // does not wait (the batch object orders its stream against its members' the same way, solver_bt.hpp)
+    int stream_wait(hipStream_t other);
+    int stream_signal(hipStream_t other);
     void prof_begin(int kclass);
     void prof_end(int kclass);
     int set_profiling(int on);

@@ -37,6 +37,23 @@ int SolverBase::synchronize()
     return BDDMMA_OK;
 }
 
+int SolverBase::stream_wait(hipStream_t other)
+{
+    HIPCHK(hipSetDevice(device));
+    if (!ev_order) HIPCHK(hipEventCreateWithFlags(&ev_order, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ev_order, other));
+    HIPCHK(hipStreamWaitEvent(stream, ev_order, 0));
+    return BDDMMA_OK;
+}
+int SolverBase::stream_signal(hipStream_t other)
+{
+    HIPCHK(hipSetDevice(device));
+    if (!ev_order) HIPCHK(hipEventCreateWithFlags(&ev_order, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ev_order, stream));
+    HIPCHK(hipStreamWaitEvent(other, ev_order, 0));
+    return BDDMMA_OK;
+}
+
 void SolverBase::prof_begin(int kclass)
 {
     if (!profiling || !prof_active) return;

@@ -66,11 +66,23 @@ int SolverT<REAL>::gi_grad_learned_iterations(const void* w, int w_dev, double o
     REAL *alpha = take(L), *g_lo = take(L), *g_hi = take(L), *g_mm = take(L), *g_alpha = take(L), *g_omega = take(L), *g_omega1 = take(1);
     // ---- the arguments: nothing below this block fails on them, nothing in it writes the solver's state
     // (load_layer_values names its caller "learned_iterations: ...")
-    if (ov && (rc = load_layer_values(d_omega_lay, omega_vec, ov_dev, "omega_vec"))) { err = "grad_" + err; return rc; }
-    if ((rc = load_layer_values(alpha, w, w_dev, "dist_weights"))) { err = "grad_" + err; return rc; }
-    if ((rc = gr_load(g_lo, grad_lo, L, on_device, "grad_learned_iterations: grad_lo"))) return rc;
-    if ((rc = gr_load(g_hi, grad_hi, L, on_device, "grad_learned_iterations: grad_hi"))) return rc;
-    if ((rc = gr_load(g_mm, grad_mm, L, on_device, "grad_learned_iterations: grad_mm"))) return rc;
+    if (w_dev && on_device && (!ov || ov_dev)) {
+        // all on the device: one launch copies and checks them, one read of the counts (same order, same first offender, same words)
+        LoadSpec in[LOAD_MAX_ARRAYS];
+        int k = 0;
+        if (ov) in[k++] = {d_omega_lay, omega_vec, "omega_vec", true};
+        in[k++] = {alpha, w, "dist_weights", true};
+        in[k++] = {g_lo, grad_lo, "grad_lo", false};
+        in[k++] = {g_hi, grad_hi, "grad_hi", false};
+        in[k++] = {g_mm, grad_mm, "grad_mm", false};
+        if ((rc = gr_load_device(in, k, L, me))) return rc;
+    } else {
+        if (ov && (rc = load_layer_values(d_omega_lay, omega_vec, ov_dev, "omega_vec"))) { err = "grad_" + err; return rc; }
+        if ((rc = load_layer_values(alpha, w, w_dev, "dist_weights"))) { err = "grad_" + err; return rc; }
+        if ((rc = gr_load(g_lo, grad_lo, L, on_device, "grad_learned_iterations: grad_lo"))) return rc;
+        if ((rc = gr_load(g_hi, grad_hi, L, on_device, "grad_learned_iterations: grad_hi"))) return rc;
+        if ((rc = gr_load(g_mm, grad_mm, L, on_device, "grad_learned_iterations: grad_mm"))) return rc;
+    }
     const hipMemcpyKind out_kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     const uint64_t n_omega = ov ? L : 1;
     HIPCHK(hipMemsetAsync(g_alpha, 0, L * sizeof(REAL), stream));

@@ -85,6 +85,35 @@ int SolverT<REAL>::gr_load(REAL* dst, const void* src, uint64_t n, int on_dev, c
 }
 
 template <typename REAL>
+int SolverT<REAL>::gr_load_device(const LoadSpec* specs, int count, uint64_t n, const char* me)
+{
+    if (count <= 0 || n == 0) return BDDMMA_OK;
+    LoadArrays<REAL> a{};
+    a.n = (uint32_t)n;
+    a.count = (uint32_t)count;
+    for (int k = 0; k < count; ++k) {
+        a.src[k] = (const REAL*)specs[k].src;
+        a.dst[k] = specs[k].dst;
+        if (specs[k].weights) a.nonneg |= 1u << k;
+    }
+    uint32_t bad[LOAD_MAX_ARRAYS] = {};
+    HIPCHK(hipMemsetAsync(d_counts, 0, sizeof(bad), stream));
+    // a 16-byte vector per thread and trip, at most 2048 workgroups: the rest by the grid-stride loop
+    const uint64_t vecs = cdiv(n, 16 / sizeof(REAL));
+    hipLaunchKernelGGL((k_load_checked<REAL>), dim3((uint32_t)std::min<uint64_t>(cdiv(vecs, 256), 2048)), dim3(256), 0, stream, a, d_counts);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(bad, d_counts, sizeof(bad), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    for (int k = 0; k < count; ++k) {
+        if (!bad[k]) continue;
+        err = specs[k].weights ? std::string(me) + ": " + std::to_string(bad[k]) + " of the " + specs[k].what + " are negative or not finite"
+                               : std::to_string(bad[k]) + " values of " + me + ": " + specs[k].what + " are not finite";
+        return BDDMMA_ERR_INVALID_ARGUMENT;
+    }
+    return BDDMMA_OK;
+}
+
+template <typename REAL>
 int SolverT<REAL>::gr_min_marginal_diff(const void* grad_mm, void* grad_lo, void* grad_hi, int on_device)
 {
     HIPCHK(hipSetDevice(device));
@@ -145,8 +174,13 @@ int SolverT<REAL>::gr_distribute_delta(const void* grad_lo, const void* grad_hi,
     }
     int rc;
     if ((rc = gr_inputs(true))) return rc;
-    if ((rc = gr_load(d_gr_in0, grad_lo, n_layers, on_device, "grad_distribute_delta: grad_lo"))) return rc;
-    if ((rc = gr_load(d_gr_in1, grad_hi, n_layers, on_device, "grad_distribute_delta: grad_hi"))) return rc;
+    if (on_device) {
+        const LoadSpec in[2] = {{d_gr_in0, grad_lo, "grad_lo", false}, {d_gr_in1, grad_hi, "grad_hi", false}};
+        if ((rc = gr_load_device(in, 2, n_layers, "grad_distribute_delta"))) return rc;
+    } else {
+        if ((rc = gr_load(d_gr_in0, grad_lo, n_layers, 0, "grad_distribute_delta: grad_lo"))) return rc;
+        if ((rc = gr_load(d_gr_in1, grad_hi, n_layers, 0, "grad_distribute_delta: grad_hi"))) return rc;
+    }
     REAL* const dst = on_device ? (REAL*)grad_deferred_mm : d_tmp0;
     hipLaunchKernelGGL((k_grad_distribute<REAL>), dim3(cdiv(n_layers, 256)), dim3(256), 0, stream, (const REAL*)d_gr_in0, (const REAL*)d_gr_in1,
                        (const REAL*)d_mm_consumed, d_lpos, dst, (uint32_t)n_layers);
@@ -162,8 +196,13 @@ int SolverT<REAL>::gr_cost_perturbation(const void* grad_lo, const void* grad_hi
     HIPCHK(hipSetDevice(device));
     int rc;
     if ((rc = gr_inputs(true))) return rc;
-    if ((rc = gr_load(d_gr_in0, grad_lo, n_layers, on_device, "grad_cost_perturbation: grad_lo"))) return rc;
-    if ((rc = gr_load(d_gr_in1, grad_hi, n_layers, on_device, "grad_cost_perturbation: grad_hi"))) return rc;
+    if (on_device) {
+        const LoadSpec in[2] = {{d_gr_in0, grad_lo, "grad_lo", false}, {d_gr_in1, grad_hi, "grad_hi", false}};
+        if ((rc = gr_load_device(in, 2, n_layers, "grad_cost_perturbation"))) return rc;
+    } else {
+        if ((rc = gr_load(d_gr_in0, grad_lo, n_layers, 0, "grad_cost_perturbation: grad_lo"))) return rc;
+        if ((rc = gr_load(d_gr_in1, grad_hi, n_layers, 0, "grad_cost_perturbation: grad_hi"))) return rc;
+    }
     REAL* const lo = on_device ? (REAL*)grad_lo_pert : d_delta_c;  // 2V scratch of the explicit forward_mm / backward_mm calls
     REAL* const hi = on_device ? (REAL*)grad_hi_pert : d_delta_c + n_vars;
     hipLaunchKernelGGL((k_grad_perturb<REAL>), dim3(cdiv(n_vars, 256)), dim3(256), 0, stream, (const REAL*)d_gr_in0, (const REAL*)d_gr_in1, d_var_ptr, d_var_layers,

@@ -6,6 +6,7 @@ template int SolverT<double>::gr_prepare();
 template int SolverT<double>::gr_launch_down();
 template int SolverT<double>::gr_launch_up();
 template int SolverT<double>::gr_load(double*, const void*, uint64_t, int, const char*);
+template int SolverT<double>::gr_load_device(const SolverT<double>::LoadSpec*, int, uint64_t, const char*);
 template int SolverT<double>::gr_min_marginal_diff(const void*, void*, void*, int);
 template int SolverT<double>::gr_lower_bound_per_bdd(const void*, void*, void*, int, int);
 template int SolverT<double>::gr_distribute_delta(const void*, const void*, void*, int);

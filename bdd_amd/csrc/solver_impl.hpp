@@ -214,6 +214,7 @@ struct SolverT final : SolverBase {
         }
         if (ev_t0) (void)hipEventDestroy(ev_t0);
         if (ev_t1) (void)hipEventDestroy(ev_t1);
+        if (ev_order) (void)hipEventDestroy(ev_order);
         if (stream) (void)hipStreamDestroy(stream);
     }
 
@@ -438,7 +439,7 @@ struct SolverT final : SolverBase {
         HIPCHK(hipHostMalloc((void**)&h_lb_seq, 3 * sizeof(uint64_t), hipHostMallocMapped | hipHostMallocCoherent));
         HIPCHK(hipHostGetDevicePointer((void**)&d_lb_seq, h_lb_seq, 0));
         std::memset((void*)h_lb_seq, 0, 3 * sizeof(uint64_t));
-        if ((rc = dalloc(&d_counts, 4))) return rc;
+        if ((rc = dalloc(&d_counts, 8))) return rc;   // 4: rounding_round; LOAD_MAX_ARRAYS: gr_load_device
         HIPCHK(hipMemsetAsync(d_F, 0, n_slots * sizeof(REAL), stream));
         HIPCHK(hipMemsetAsync(d_T, 0, n_slots * sizeof(REAL), stream));
         HIPCHK(hipMemsetAsync(d_lohi, 0, 2 * n_layers * sizeof(REAL), stream));
@@ -1738,6 +1739,11 @@ struct SolverT final : SolverBase {
     int gr_launch_down();   // root -> terminal: seeds, the gradient through T
     int gr_launch_up();     // terminal -> root: the gradient through F
     int gr_load(REAL* dst, const void* src, uint64_t n, int on_dev, const char* what);  // an incoming gradient -> the device, checked finite
+    // The same for up to LOAD_MAX_ARRAYS device arrays of n values at once (k_load_checked: one launch, one read of the counts, one
+    // synchronisation): checked in the order given, the first offending one reported in the words gr_load / load_layer_values use.
+    // weights: the array must also be >= 0 and is reported as load_layer_values does, `what` prefixed by `me`.
+    struct LoadSpec { REAL* dst; const void* src; const char* what; bool weights; };
+    int gr_load_device(const LoadSpec* specs, int count, uint64_t n, const char* me);
     int gr_min_marginal_diff(const void* grad_mm, void* grad_lo, void* grad_hi, int on_device);
     int gr_lower_bound_per_bdd(const void* grad_lb, void* grad_lo, void* grad_hi, int smooth, int on_device);
     int gr_distribute_delta(const void* grad_lo, const void* grad_hi, void* grad_deferred_mm, int on_device);

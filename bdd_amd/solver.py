@@ -94,6 +94,9 @@ class bdd_hip_parallel_mma:
     def nontemporal_loads(self) -> bool:
         """the solve sweeps run in the instantiation that loads potentials and staging tables non-temporally (footprint beyond the caches' reach)"""
         return bool(self._L.bddmma_nontemporal_loads(self._h))
+    def device(self) -> int:
+        """index of the GPU the solver lives on"""
+        return int(self._L.bddmma_device(self._h))
     def device_bytes(self): return int(self._L.bddmma_device_bytes(self._h))
     def device_allocated_bytes(self): return int(self._L.bddmma_device_allocated_bytes(self._h))
 
@@ -485,6 +488,16 @@ class bdd_hip_parallel_mma:
                                                      int(seed), counts, _ptr(sol), _ptr(c0), _ptr(c1)))
         return dict(counts=tuple(int(c) for c in counts), sol=sol, cost_delta_0=c0, cost_delta_1=c1)
 
+    def primal_rounding_incremental(self, init_delta, delta_growth_rate, num_itr_lb, verbose=False, num_rounds=500, seed=0):
+        """incremental_mm_agreement_rounding_cuda on this solver (primal_rounding_incremental of the reference's Python module,
+        bdd_cuda_learned_mma_py.cu:433-440): the solution as a list of 0.0 / 1.0 per variable, empty when none was found.  The costs
+        stay perturbed."""
+        sol = np.zeros(self.nr_variables(), np.int8)
+        found = C.c_int(0)
+        self._ck(self._L.bddmma_incremental_mm_agreement_rounding(self._h, None, float(init_delta), float(delta_growth_rate), int(num_itr_lb),
+                                                                  int(num_rounds), int(seed), 1 if verbose else 0, _ptr(sol), C.byref(found)))
+        return [float(x) for x in sol] if found.value else []
+
     # ---- checkpoint (bdd_cuda_base.cu:1486-1550; pickle in bdd_cuda_parallel_mma_py.cu:15-38)
     def save(self, path: str):
         self._ck(self._L.bddmma_save(self._h, path.encode()))
@@ -496,6 +509,16 @@ class bdd_hip_parallel_mma:
         capi.check(L.bddmma_load(C.byref(h), device, path.encode()), None)
         prec = "double" if L.bddmma_precision(h) == capi.F64 else "float"
         return cls(None, precision=prec, _handle=h)
+
+    # ---- ordering against other streams (include/bdd_mma.h: bddmma_stream_wait / bddmma_stream_signal)
+    def stream_wait(self, hip_stream=0):
+        """what is queued on the solver's stream from now on starts after everything queued so far on `hip_stream` (a raw hipStream_t as an
+        integer, e.g. torch.cuda.current_stream().cuda_stream; 0 / None: the default stream).  The host does not wait."""
+        self._ck(self._L.bddmma_stream_wait(self._h, C.c_void_p(int(hip_stream or 0))))
+
+    def stream_signal(self, hip_stream=0):
+        """the reverse: what is queued on `hip_stream` from now on starts after everything queued so far on the solver's stream"""
+        self._ck(self._L.bddmma_stream_signal(self._h, C.c_void_p(int(hip_stream or 0))))
 
     # ---- measurement
     def synchronize(self): self._ck(self._L.bddmma_synchronize(self._h))

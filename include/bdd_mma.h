@@ -20,7 +20,10 @@
  *    (the reference's thrust::device_vector overloads); 0 means host memory.
  *  - One handle per problem; handles are independent (own stream, own buffers)
  *    so one host thread/process per GPU is safe (reference: single stream,
- *    device 0 hard-coded, include/cuda_utils.h:111-114).
+ *    device 0 hard-coded, include/cuda_utils.h:111-114).  A device buffer written or read by another stream (a tensor of a
+ *    framework that runs on a stream of its own) is not ordered against the handle's stream by itself: bddmma_stream_wait before the
+ *    calls that read it and bddmma_stream_signal after the calls that read or write it order the two streams without the host
+ *    waiting for either (or synchronise the device, as callers had to before these existed).
  *  - Layers: one layer per (BDD, variable) pair = one dual variable.  Terminal
  *    layers carry no information and are not exposed: nr_layers() equals the
  *    reference CPU solver's nr_layers() (bdd_parallel_mma_base.cpp:1398-1402),
@@ -493,6 +496,16 @@ int bddmma_perturb_primal_costs(bddmma_solver* s, bddmma_lbfgs* lbfgs_or_null, d
 /* ---- checkpoint (bdd_cuda_base.cu:1486-1550) ------------------------------ */
 int bddmma_save(const bddmma_solver* s, const char* path);
 int bddmma_load(bddmma_solver** out, int device, const char* path);
+
+/* ---- ordering against other streams ---------------------------------------
+ * bddmma_stream_wait: whatever is queued on the handle's stream after this call starts after everything queued on `hip_stream` (a
+ * hipStream_t of the handle's device; NULL: the default stream) so far.  bddmma_stream_signal: the reverse — whatever is queued on
+ * `hip_stream` after the call starts after everything queued on the handle's stream so far.  Both are an event record followed by a
+ * stream wait on an event the handle owns (timing disabled, created on first use): neither waits on the host, and neither changes how
+ * streams or queues are set up.  Call wait before handing the handle device buffers that `hip_stream` still writes, and signal before
+ * `hip_stream` reads what the handle wrote or reuses memory the handle read.  A HIP failure returns BDDMMA_ERR_DEVICE. */
+int bddmma_stream_wait(bddmma_solver* s, void* hip_stream);
+int bddmma_stream_signal(bddmma_solver* s, void* hip_stream);
 
 /* ---- measurement ---------------------------------------------------------- */
 int bddmma_synchronize(bddmma_solver* s);

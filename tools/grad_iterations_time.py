@@ -8,7 +8,8 @@ memsets that keep what the reverse reads), 17 (its six elementwise launches) —
 and of the single-shot gradient pair (kinds 10 - 12).  From these: reversed iteration = 13 + 14 + 16 + 17 + replay (1 + 2 + 3 + 2 x 4), and
 the ratio to (replay + gradient pair).  Whole calls on device buffers by host wall clock with a synchronisation behind each (after 3
 warm-up calls, 20 repetitions, median / min / max) are listed beside them; a whole grad_iterations call also pays the finiteness checks of
-its inputs, the cache and state copies and the restore."""
+its inputs, the cache and state copies and the restore; the lines "whole call, ..." split it: no tracked iteration against one, the scalar omega
+(whose gradient is summed over the layers by one workgroup, k_gi_omega_sum) against omega_vec."""
 import argparse
 import os
 import statistics
@@ -57,6 +58,23 @@ def run(precision, out):
             xs.append((time.perf_counter() - t0) * 1e6)
         med[name] = statistics.median(xs)
         out.append(f"  {name:44s} median {med[name]:9.1f} us (min {min(xs):.1f}, max {max(xs):.1f}; host wall clock, synchronous)")
+    # what a whole call consists of: no tracked iteration (argument loads, memsets, two output copies, one synchronisation) and one, for the
+    # scalar omega and for omega_vec — the scalar's extra is k_gi_omega_sum, its fixed-order sum over the layers
+    ov = torch.full((L,), 0.5, dtype=tdt, device="cuda")
+    for vec in (False, True):
+        o = (outs[0], torch.zeros(L, dtype=tdt, device="cuda") if vec else outs[1])
+        for n in (0, 1):
+            xs = []
+            for i in range(3 + REPS):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                s.grad_iterations(w, g[0], g[1], g[2], 0.5, 0, n, 1, omega_vec=ov if vec else None, out=o)
+                xs.append((time.perf_counter() - t0) * 1e6)
+                for x in g:
+                    x.clamp_(-1, 1)
+            xs = xs[3:]
+            name = f"whole call, {'omega_vec' if vec else 'scalar omega'}, {n} tracked"
+            out.append(f"  {name:44s} median {statistics.median(xs):9.1f} us (min {min(xs):.1f}, max {max(xs):.1f}; host wall clock, synchronous)")
     for _ in range(3):
         s.grad_all_min_marginal_differences(g[0], out=bufs)
     t = {}
