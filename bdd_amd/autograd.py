@@ -5,7 +5,8 @@ semantics are those of the reference's torch layer (src/bdd_cuda_torch/bdd_cuda_
 mirrors); the differences are the ones include/bdd_mma.h has from the reference's solver classes and are listed here.
 
 Conventions of every function
-  solvers     a list of bdd_hip_parallel_mma of one precision on one device.
+  solvers     a list of bdd_hip_parallel_mma of one precision on one device, or a bdd_hip_batch: its members in order.  (Only
+              DualIterations.forward does anything else with a batch than with the list of its members.)
   tensors     1-D, contiguous, on the solvers' device, of the solvers' precision (torch.float32 / torch.float64 — the reference asks for
               torch's default dtype instead).  A batch tensor is the concatenation over the solvers, in list order, of each solver's array:
                 per layer     nr_layers() values in the public layer order (get_solver_costs, get_primal_variable_index) — there are
@@ -36,6 +37,8 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
+from .solver import bdd_hip_batch
+
 __all__ = ["batch_index", "BatchIndex", "DualIterations", "DistributeDeferredDelta", "ComputeAllMinMarginalsDiff", "PerturbPrimalCosts",
            "ComputeLowerBoundperBDD", "ComputePerBDDSolutionsIdentityBackward", "ComputePerBDDSolutions", "GetSumMarginals",
            "GetMarginalProbability", "ComputePrimalSolution"]
@@ -50,7 +53,8 @@ class _Sizes:
     """what a list of solvers asks of the batch tensors; raises ValueError for a list no batch can be formed from"""
 
     def __init__(self, solvers):
-        self.solvers = list(solvers)
+        self.batch = solvers if isinstance(solvers, bdd_hip_batch) else None
+        self.solvers = list(solvers.solvers if self.batch is not None else solvers)
         if not self.solvers:
             raise ValueError("solvers: the list is empty")
         types = {np.dtype(s.value_type) for s in self.solvers}
@@ -100,7 +104,7 @@ def _offsets(counts):
 def batch_index(solvers, device=None):
     """The offsets of a batch of solvers and what a GNN indexes with (BatchIndex).  The index tensors are built on the host and moved
     to `device` when one is given."""
-    solvers = list(solvers)
+    solvers = list(solvers.solvers if isinstance(solvers, bdd_hip_batch) else solvers)
     layers = _offsets(s.nr_layers() for s in solvers)
     bdds = _offsets(s.nr_bdds() for s in solvers)
     variables = _offsets(s.nr_variables() for s in solvers)
@@ -201,7 +205,10 @@ class DualIterations(torch.autograd.Function):
     grad_dual_itr_max_itr, improvement_slope, num_caches, compute_history_for_itrs, history_avg_beta) ->
     (lo, hi, def_mm, sol_avg, lb_first_diff_avg, lb_second_diff_avg).
 
-    forward   learned_iterations on every solver, from the given costs and deferred differences.  omega is a tensor: one value (the scalar
+    forward   learned_iterations on every solver, from the given costs and deferred differences — for a bdd_hip_batch whose members are all
+              fused_small_learned(), with improvement_slope <= 0 and no history, ONE batch.learned_iterations between the members'
+              set_solver_costs and get_solver_costs (the same results: bit-equal in float, and in double wherever no variable sits in
+              more than two BDDs).  omega is a tensor: one value (the scalar
               call) or one per layer (learned_iterations' omega_vec).  With improvement_slope > 0 the solvers may stop at different
               counts; each count is remembered.  The last three outputs are None unless compute_history_for_itrs > 0 (they start as
               zeros: an entry the history does not reach keeps that) and are not differentiable.
@@ -233,6 +240,16 @@ class DualIterations(torch.autograd.Function):
             ctx.mark_non_differentiable(sol_avg, lb1, lb2)
         omega_scalar = None if per_layer_omega else float(omega.reshape(-1)[0].item())
         done = []
+        if z.batch is not None and not float(improvement_slope) > 0 and history == 0 and all(s.fused_small_learned() for s in z.solvers):
+            with _Ordered(z.solvers):
+                for s, l in zip(z.solvers, z.slices(z.layers)):
+                    s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], def_mm_batch[l])
+                z.batch.learned_iterations(dist_weights_batch, int(num_iterations), omega=0.5 if per_layer_omega else omega_scalar,
+                                           omega_vec=omega if per_layer_omega else None)
+                for s, l in zip(z.solvers, z.slices(z.layers)):
+                    s.get_solver_costs(out=(lo[l], hi[l], mm[l]))
+            ctx.iterations_done, ctx.omega_scalar = [int(num_iterations)] * len(z.solvers), omega_scalar
+            return lo, hi, mm, sol_avg, lb1, lb2
         with _Ordered(z.solvers):
             for s, l, b in zip(z.solvers, z.slices(z.layers), z.slices(z.bdds)):
                 s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], def_mm_batch[l])

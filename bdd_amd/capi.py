@@ -66,6 +66,7 @@ SIGNATURES = {
     "bddmma_nr_packs": (_U64, [_V]),
     "bddmma_solve_sweep_kind": (_I, [_V]),
     "bddmma_fused_small": (_I, [_V]),
+    "bddmma_fused_small_learned": (_I, [_V]),
     "bddmma_nontemporal_loads": (_I, [_V]),
     "bddmma_precision": (_I, [_V]),
     "bddmma_device": (_I, [_V]),
@@ -121,6 +122,7 @@ SIGNATURES = {
     "bddmma_batch_last_error": (C.c_char_p, [_V]),
     "bddmma_batch_size": (_U64, [_V]),
     "bddmma_batch_iterations": (_I, [_V, _D, _U64]),
+    "bddmma_learned_iterations_batch": (_I, [_V, _V, _V, _D, _U64, _I]),
     "bddmma_batch_time_iterations": (_I, [_V, _D, _U64, C.POINTER(_D)]),
     "bddmma_batch_run_solver": (_I, [_V, _U64, _D, _D, _D, C.POINTER(RunResult)]),
     "bddmma_batch_lower_bounds": (_I, [_V, C.POINTER(_D)]),

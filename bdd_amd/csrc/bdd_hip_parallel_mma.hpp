@@ -472,6 +472,17 @@ class bdd_hip_batch {
     bdd_hip_batch& operator=(const bdd_hip_batch&) = delete;
     size_t size() const { return bddmma_batch_size(b_); }
     void iterations(const size_t n, const REAL omega = 0.5) { check(bddmma_batch_iterations(b_, omega, n)); }
+    // learned_iterations(w_i, num_itr, omega, improvement_slope = 0) of every member i, or with omega_vec non-null its omega_vec form: the
+    // members' REAL[nr_layers] one behind the other in the members' order, host vectors or (the _dev form) device pointers.  Every member
+    // must be fused_small_learned() (include/bdd_mma.h: bddmma_learned_iterations_batch).
+    void learned_iterations(const std::vector<REAL>& dist_weights, const size_t num_itr, const REAL omega = 0.5, const std::vector<REAL>* omega_vec = nullptr)
+    {
+        check(bddmma_learned_iterations_batch(b_, dist_weights.data(), omega_vec ? omega_vec->data() : nullptr, omega, num_itr, 0));
+    }
+    void learned_iterations_dev(const REAL* dev_dist_weights, const size_t num_itr, const REAL omega = 0.5, const REAL* dev_omega_vec = nullptr)
+    {
+        check(bddmma_learned_iterations_batch(b_, dev_dist_weights, dev_omega_vec, omega, num_itr, 1));
+    }
     std::vector<bddmma_run_result> run_solver(const size_t max_iter = 1000, const double tolerance = 1e-6, const double improvement_slope = 1e-9,
                                               const double time_limit = 3600.0)
     {

@@ -155,6 +155,7 @@ uint64_t bddmma_nr_hops(const bddmma_solver* s) { return s && s->impl ? s->impl-
 uint64_t bddmma_nr_packs(const bddmma_solver* s) { return s && s->impl ? s->impl->n_packs_narrow + s->impl->n_packs_wide : 0; }
 int bddmma_solve_sweep_kind(const bddmma_solver* s) { return s && s->impl ? s->impl->solve_sweep_kind : -1; }
 int bddmma_fused_small(const bddmma_solver* s) { return s && s->impl ? (s->impl->fused_small ? 1 : 0) : -1; }
+int bddmma_fused_small_learned(const bddmma_solver* s) { return s && s->impl ? (s->impl->fused_small_learned ? 1 : 0) : -1; }
 int bddmma_nontemporal_loads(const bddmma_solver* s) { return s && s->impl ? (s->impl->nt_loads ? 1 : 0) : -1; }
 int bddmma_precision(const bddmma_solver* s) { return s && s->impl ? s->impl->precision : -1; }
 int bddmma_device(const bddmma_solver* s) { return s && s->impl ? s->impl->device : -1; }
@@ -440,6 +441,10 @@ uint64_t bddmma_batch_size(const bddmma_batch* b) { return b && b->impl ? b->imp
 int bddmma_batch_iterations(bddmma_batch* b, double omega, uint64_t n)
 {
     return guarded_batch(b, [&](BatchBase* i) { return i->iterations(omega, n); });
+}
+int bddmma_learned_iterations_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec, double omega, uint64_t num_itr, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) { return i->learned_iterations(dist_weights, omega_vec, omega, num_itr, on_device); });
 }
 int bddmma_batch_time_iterations(bddmma_batch* b, double omega, uint64_t n, double* ms)
 {

@@ -1,4 +1,5 @@
-// kernels/small.hpp — instances that fit ONE workgroup: whole MMA iterations inside one launch (k_iterate_small, k_iterate_small_batch).
+// kernels/small.hpp — instances that fit ONE workgroup: whole MMA iterations inside one launch (k_iterate_small, k_iterate_small_batch),
+// and whole learned iterations (k_learned_small, k_learned_small_batch).
 // Part of kernels.hpp (include that, not this file: the parts build on each other in its order).
 #pragma once
 
@@ -71,10 +72,44 @@ inline uint32_t small_lds_bytes(uint32_t real_size, uint32_t n_packs, uint32_t n
     return o;
 }
 
+// What the LEARNED form (learned iterations: SolverT::learned_iterations, bdd_cuda_learned_mma.cu:9-262) takes beyond SmallDev — a struct of
+// its own, so that SmallDev and the plain kernels' argument layout stay as they are.  In LDS:
+//   the distribution weights by (variable, bdd) entry — alpha_ent (binned entry order) gathered through var_ent — live in the off_mm area:
+//           that area receives the last backward sweep's differences in the exit exchange, which runs behind the last weighted one, so the
+//           weights are dead when it is written (every launch loads them again);
+//   off_om  (behind the plain areas) omega per layer of each pack, om_stride = the longest pack's layers per pack: omega_lay (layer order,
+//           the order of lohi) or, where that is null, the scalar omega in every slot — ONE instantiation serves bddmma_learned_iterations
+//           and _omega_vec, so an omega_vec that holds omega everywhere gives the scalar call's bits.  Padding lanes read the slot their
+//           {lo, hi} offset names: slot 0, or (records rewritten in LDS) slot nl — of the next packs' values or, behind the last pack, the
+//           nl + 1 - om_stride spare slots the area ends with; whatever they read is not used (their minima are +inf: the difference is 0).
+// The two shapes that decided this layout: the 10-pack float and the 7-pack double set covers of tests/test_gpu_small_learned.py fit the
+// CU's LDS with it and not with a weight area of their own and nl + 1 omega slots per pack.
+template <typename REAL>
+struct SmallLearn {
+    const REAL* alpha_ent;
+    const REAL* omega_lay;
+    uint32_t off_om, om_stride;
+};
+inline uint32_t small_learn_lds_bytes(uint32_t real_size, uint32_t n_packs, uint32_t nl, uint32_t max_layers, uint32_t plain_bytes, uint32_t& off_om)
+{
+    const uint32_t o = (plain_bytes + 15u) & ~15u;
+    off_om = o;
+    return o + ((n_packs - 1u) * max_layers + small_stage_stride(nl)) * real_size;
+}
+
 // The workgroup's work, shared by k_iterate_small (one instance per launch) and k_iterate_small_batch (one instance per workgroup).
 // NW waves, pack p on wave p (n_packs <= NW); RL: the packs' records live in LDS too (1 KiB per hop), else they stream from L2 eight hops ahead
-template <typename REAL, int NW, bool RL>
-__device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<REAL>& d, const PackDev& pk, REAL omega, uint32_t n_iters, const RunStep& run)
+// LEARNED (k_learned_small, k_learned_small_batch): n learned iterations,
+//     weighted exchange | forward solve sweep | weighted exchange | backward solve sweep
+// n times and then the plain exchange once.  On entry the layer slots' .x hold the solver's deferred differences (a pending isotropic delta is
+// ignored: the state contract of bddmma_learned_iterations); the weighted exchange gives entry k {alpha[k] * Slo, alpha[k] * Shi} of its
+// variable's sums — no division by the BDD count, one product each in REAL: exchange_reduce_body<.., WEIGHTED>'s arithmetic; the hop takes
+// omega from its layer's slot.  The plain exchange behind the last backward sweep and the plain epilogue leave what the four-launch path
+// leaves: the last backward pass's differences deferred, delta their isotropic exchange, the bound's partial sums.  No run_solver (run.ctl
+// is null there), so no early return at all.
+template <typename REAL, int NW, bool RL, bool LEARNED = false>
+__device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<REAL>& d, const PackDev& pk, REAL omega, uint32_t n_iters, const RunStep& run,
+                                              const SmallLearn<REAL>* ln = nullptr)
 {
     constexpr uint32_t S = sizeof(REAL);
     constexpr uint32_t NT = 64 * NW;
@@ -84,7 +119,8 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
     const int wave = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
     const int lane = tid & 63;
     // run_solver: launches queued behind the iteration that met a criterion do nothing (DevPtrs::stop / run_iter = this launch's first iteration)
-    if (d.stop != nullptr && *d.stop <= d.run_iter) return;
+    if constexpr (!LEARNED)
+        if (d.stop != nullptr && *d.stop <= d.run_iter) return;
     const REAL INF = inf_v<REAL>();
     const uint32_t region = small_region_bytes(S, sm.ns, sm.nl), dstride = small_stage_stride(sm.nl);
     const uint32_t ll_dummy = sm.nl * 2u * S;   // the dummy pair of a pack's {lo, hi} array and of its staging area
@@ -95,6 +131,7 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
     const rsrc_t rr = make_rsrc(sm.rec, sm.rec_words);
 
     REAL* const mmE = reinterpret_cast<REAL*>(dyn_lds + sm.off_mm);
+    REAL* const alE = mmE;   // LEARNED: the weights by (variable, bdd) entry, until the exit exchange writes the differences there
     // ---- this wave's pack: everything the sweeps need from the headers, once
     const uint32_t p = (uint32_t)wave;
     const bool has_pack = p < sm.n_packs;
@@ -106,6 +143,7 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
     const uint32_t wb = sm.off_regions + p * region, wbF = wb + res2_f_off(S, sm.ns), wbC = wb + res2_c_off(S, sm.ns);
     const uint32_t rl = sm.off_rec + p * sm.rec_cap, rlane = rl + (uint32_t)lane * 16u;
     const uint32_t nhm1 = nh ? nh - 1u : 0u;
+    const uint32_t ob = LEARNED ? ln->off_om + p * ln->om_stride * S : 0u;   // LEARNED: this pack's omega slots (layer j at ob + j S = ob + ll / 2)
     // ---- prologue: the state -> LDS
     if (has_pack) {
         wave_copy_to_lds(d.T + slot0, dyn_lds + wb, nslots * S, lane);
@@ -130,7 +168,17 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
     }
     for (uint32_t i = tid; i <= sm.n_vars; i += NT) vp[i] = sm.var_ptr[i];
     for (uint32_t i = tid; i < sm.n_entries; i += NT) vl[i] = sm.var_lds[i];
-    {   // the staged delta pairs of every quad: entry -> its layer's slot of the staging area (quad-relative slots, as the sweeps' own staging)
+    if constexpr (LEARNED) {
+        // the deferred differences -> the .x of the entries' layer slots; the weights -> (variable, bdd) order; omega -> this pack's slots
+        for (uint32_t k = tid; k < sm.n_entries; k += NT) {
+            const uint32_t e = sm.var_ent[k];
+            lds_st<REAL>(dyn_lds, sm.var_lds[k], d.mm_binned[e]);
+            alE[k] = ln->alpha_ent[e];
+        }
+        if (has_pack)
+            for (uint32_t j = (uint32_t)lane; j < nlayers; j += 64u)
+                lds_st<REAL>(dyn_lds, ob + j * S, ln->omega_lay != nullptr ? ln->omega_lay[layer0 + j] : omega);
+    } else {   // the staged delta pairs of every quad: entry -> its layer's slot of the staging area (quad-relative slots, as the sweeps' own staging)
         P2* const sD = reinterpret_cast<P2*>(dyn_lds);
         for (uint32_t q = 0; q < sm.n_quads; ++q) {
             const uint32_t c0 = sm.quad_hdr[4 * (size_t)q], cnt = sm.quad_hdr[4 * (size_t)q + 1];
@@ -143,7 +191,8 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the direct-to-LDS copies have landed
     if (has_pack && lane < 2) lds_st<REAL>(dyn_lds, wb + (sm.ns + (uint32_t)lane) * S, lane == 0 ? REAL(0) : INF);  // sinks: cost to terminal 0 (top) / +inf (bot)
     RunCtl c{};
-    if (run.ctl != nullptr && tid == 0) c = *run.ctl;
+    if constexpr (!LEARNED)
+        if (run.ctl != nullptr && tid == 0) c = *run.ctl;
     __syncthreads();
 
     // The exchange (compute_delta + normalize_delta + the broadcast to the variable's layers, bdd_cuda_parallel_mma.cu:358-430,191-197): a
@@ -170,13 +219,21 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
     };
     const uint32_t v_own = tid;
     uint32_t own_k0 = 0, own_n = 0, own_a[4] = {0u, 0u, 0u, 0u};
+    REAL own_w[4] = {REAL(0), REAL(0), REAL(0), REAL(0)};   // LEARNED: the weights of those entries (they do not change within a launch)
     if (v_own < sm.n_vars) {
         own_k0 = vp[v_own];
         own_n = vp[v_own + 1] - own_k0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) own_a[j] = vl[own_k0 + ((uint32_t)j < own_n ? j : 0)];   // past the last entry: the first again (see the exchange)
+        if constexpr (LEARNED)
+            if (own_n != 0) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) own_w[j] = alE[own_k0 + ((uint32_t)j < own_n ? j : 0)];
+            }
     }
-    auto exchange = [&](bool save_mm) {
+    // `weighted` (a compile-time tag; LEARNED only): the learned iterations' exchange — the same sums, entry k receives alpha[k] * them
+    auto exchange = [&](bool save_mm, auto weighted) {
+        constexpr bool W = decltype(weighted)::value;
         auto generic = [&](uint32_t v) {
             const uint32_t k0 = vp[v], k1 = vp[v + 1];
             if (k1 == k0) return;
@@ -196,6 +253,27 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
                         if (save_mm) mmE[kb + u] = m[u];
                     }
                 }
+            }
+            if constexpr (W) {
+                const REAL slo = REAL(lo), shi = REAL(hi);
+                for (uint32_t kb = k0; kb < k1; kb += 8) {
+                    uint32_t a[8];
+                    REAL w[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        a[u] = kb + u < k1 ? vl[kb + u] : 0u;
+                        w[u] = kb + u < k1 ? alE[kb + u] : REAL(0);
+                    }
+#pragma unroll
+                    for (int u = 0; u < 8; ++u)
+                        if (kb + u < k1) {
+                            P2 pr;
+                            pr.x = w[u] * slo;
+                            pr.y = w[u] * shi;
+                            lds_st<P2>(dyn_lds, a[u], pr);
+                        }
+                }
+                return;
             }
             const P2 pr = mean_pair(lo, hi, k1 - k0);
             for (uint32_t kb = k0; kb < k1; kb += 8) {
@@ -221,17 +299,34 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
                 else { hi += __builtin_fmax(x, 0.0); lo += __builtin_fmax(-x, 0.0); }
                 if (save_mm && (uint32_t)j < own_n) mmE[own_k0 + j] = m[j];
             }
+            if constexpr (W) {   // (an entry past the last: the first entry's slot and weight again — the same pair once more)
+                const REAL slo = REAL(lo), shi = REAL(hi);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    P2 pr;
+                    pr.x = own_w[j] * slo;
+                    pr.y = own_w[j] * shi;
+                    lds_st<P2>(dyn_lds, own_a[j], pr);
+                }
+            } else {
             const P2 pr = mean_pair(lo, hi, own_n);
 #pragma unroll
             for (int j = 0; j < 4; ++j) lds_st<P2>(dyn_lds, own_a[j], pr);
+            }
         } else if (own_n > 4) {
             generic(v_own);
         }
         for (uint32_t v = tid + NT; v < sm.n_vars; v += NT) generic(v);
     };
 
+    constexpr std::integral_constant<bool, false> PLAIN_EX{};
+    constexpr std::integral_constant<bool, LEARNED> ITER_EX{};
     uint32_t it = 0;
     for (; it < n_iters; ++it) {
+        if constexpr (LEARNED) {   // forward_iteration_learned_mm_dist: the weighted exchange of the deferred differences in front of the sweep
+            exchange(false, ITER_EX);
+            __syncthreads();
+        }
         // ---------------------------------------------------------------- forward solve sweep (k_fwd_res2's hop, state in LDS)
 #ifdef BDDMMA_EXP_SMALL_SKIP   // timing experiments only (wrong results): bit 0 forward sweep, 1 first exchange, 2 backward sweep, 3 second exchange, 4 bound
         if (has_pack && !(BDDMMA_EXP_SMALL_SKIP & 1)) {
@@ -248,7 +343,7 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
                 const P2 dd = lds_ld<P2>(dyn_lds, db + ll);
                 REAL m0 = (f + cc.x) + tl, m1 = (f + cc.y) + th;  // padding lanes: +inf
                 pair_min_aligned(m0, m1, RL ? (int32_t)r[3] < 0 : (r[3] & 0x10000u) != 0);
-                const REAL mm = mm_diff1(m0, m1, omega);
+                const REAL mm = mm_diff1(m0, m1, LEARNED ? lds_ld<REAL>(dyn_lds, ob + (ll >> 1)) : omega);
                 P2 nc;
                 nc.x = (cc.x + min0(mm)) + dd.x;
                 nc.y = (cc.y + min0_neg(mm)) + dd.y;
@@ -298,7 +393,7 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
 #ifdef BDDMMA_EXP_SMALL_SKIP
         if (!(BDDMMA_EXP_SMALL_SKIP & 2))
 #endif
-        exchange(false);
+        exchange(false, ITER_EX);
         __syncthreads();
         // ---------------------------------------------------------------- backward solve sweep (k_bwd_res2's hop)
 #ifdef BDDMMA_EXP_SMALL_SKIP
@@ -314,7 +409,7 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
                 const P2 dd = lds_ld<P2>(dyn_lds, db + ll);
                 REAL m0 = (f + cc.x) + tl, m1 = (f + cc.y) + th;
                 pair_min_aligned(m0, m1, RL ? (int32_t)r[3] < 0 : (r[3] & 0x10000u) != 0);
-                const REAL mm = mm_diff1(m0, m1, omega);
+                const REAL mm = mm_diff1(m0, m1, LEARNED ? lds_ld<REAL>(dyn_lds, ob + (ll >> 1)) : omega);
                 P2 nc;
                 nc.x = (cc.x + min0(mm)) + dd.x;
                 nc.y = (cc.y + min0_neg(mm)) + dd.y;
@@ -359,7 +454,7 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
             }
 #undef SMALL_HOP
             // lower bound contribution of this pack: sum of root costs-from-terminal (bdd_cuda_base.cu:1243-1251); every node of the first hop is a root
-            if (run.ctl != nullptr || it + 1 == n_iters) {   // (uniform) the bound: run_solver's tests, or the state the launch leaves
+            if ((!LEARNED && run.ctl != nullptr) || it + 1 == n_iters) {   // (uniform) the bound: run_solver's tests, or the state the launch leaves
             const u4v rroot = RL ? lds_ld<u4v>(dyn_lds, rl + (uint32_t)lane * 16u) : __builtin_amdgcn_raw_buffer_load_b128(rr, (uint32_t)lane * 16u, rbase * 16u, 0);
             double lb = (RL ? (rroot[2] & 0xFFFFu) != ll_dummy : rroot[3] != RES2_PAD) ? (double)lds_ld<REAL>(dyn_lds, wb + (rroot[2] >> 16)) : 0.0;
             for (int off2 = 32; off2 > 0; off2 >>= 1) lb += __shfl_down(lb, off2);
@@ -367,10 +462,11 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
             }
         }
         __syncthreads();
+        if constexpr (!LEARNED) {
 #ifdef BDDMMA_EXP_SMALL_SKIP
         if (!(BDDMMA_EXP_SMALL_SKIP & 8))
 #endif
-        exchange(true);
+        exchange(true, PLAIN_EX);
         if (run.ctl != nullptr && wave == 0) {
             // the bound of the iteration in the shape of k_lb_reduce / run_ctl_step (<= 64 partial sums: lane i holds pack i's, an in-wave tree,
             // the other fifteen partial results are 0) and run_solver's tests
@@ -388,8 +484,13 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
         }
         __syncthreads();
         if (run.ctl != nullptr && flag[0] != 0) { ++it; break; }  // uniform: the iteration that met a criterion is complete
+        }
     }
     (void)it;
+    if constexpr (LEARNED) {   // the exit state: the last backward pass's differences deferred, delta their isotropic exchange
+        exchange(true, PLAIN_EX);
+        __syncthreads();
+    }
     // ---- epilogue: the state -> global memory, as the last iteration's four launches would have left it
     if (has_pack) {
         for (uint32_t j = (uint32_t)lane; j < nslots; j += 64) {
@@ -434,6 +535,57 @@ __global__ void __launch_bounds__(64 * NW) k_iterate_small_batch(const SmallItem
 {
     const SmallItem<REAL>& item = items[blockIdx.x];
     small_iterate<REAL, NW, RL>(item.sm, item.d, item.pk, omega, n_iters, item.run);
+}
+// The learned form of both (SolverT::launch_small_learned, BatchT::learned_iterations); instantiated in solver_sl_f32.hip / _f64.hip only.
+template <typename REAL, int NW, bool RL>
+__global__ void __launch_bounds__(64 * NW) k_learned_small(SmallDev sm, DevPtrs<REAL> d, PackDev pk, SmallLearn<REAL> ln, REAL omega, uint32_t n_iters)
+{
+    small_iterate<REAL, NW, RL, true>(sm, d, pk, omega, n_iters, RunStep{}, &ln);
+}
+template <typename REAL>
+struct SmallLearnItem {
+    SmallDev sm;
+    DevPtrs<REAL> d;
+    PackDev pk;
+    SmallLearn<REAL> ln;
+};
+// use_ov = 0: the scalar omega for every member (the items keep the address of each member's omega_lay)
+template <typename REAL, int NW, bool RL>
+__global__ void __launch_bounds__(64 * NW) k_learned_small_batch(const SmallLearnItem<REAL>* __restrict__ items, REAL omega, uint32_t n_iters, uint32_t use_ov)
+{
+    const SmallLearnItem<REAL>& item = items[blockIdx.x];
+    SmallLearn<REAL> ln = item.ln;
+    if (!use_ov) ln.omega_lay = nullptr;
+    small_iterate<REAL, NW, RL, true>(item.sm, item.d, item.pk, omega, n_iters, RunStep{}, &ln);
+}
+// The arguments of one batch call in one launch: workgroup b checks member b's dist_weights (and omega_vec) and moves them where its
+// workgroup of k_learned_small_batch reads them — the weights layer -> binned entry order through lpos (k_layers_to_entries), omega_vec as
+// it is (layer order).  bad[0] / bad[1]: the smallest member index with a weight / an omega that is negative or not finite (the caller
+// presets both to 0xFFFFFFFF).
+template <typename REAL>
+struct LearnLoad {
+    const uint32_t* lpos;
+    REAL* alpha_ent;
+    REAL* omega_lay;
+    uint32_t src, n;   // first value of the member in the concatenated inputs, values
+};
+template <typename REAL>
+__global__ void k_batch_learn_load(const LearnLoad<REAL>* __restrict__ tab, const REAL* __restrict__ w, const REAL* __restrict__ ov, uint32_t* __restrict__ bad)
+{
+    const LearnLoad<REAL> t = tab[blockIdx.x];
+    bool bw = false, bo = false;
+    for (uint32_t l = threadIdx.x; l < t.n; l += blockDim.x) {
+        const REAL a = w[t.src + l];
+        bw |= !(a >= REAL(0) && a < REAL(__builtin_huge_val()));   // NaN fails both tests
+        t.alpha_ent[t.lpos[l]] = a;
+        if (ov != nullptr) {
+            const REAL o = ov[t.src + l];
+            bo |= !(o >= REAL(0) && o < REAL(__builtin_huge_val()));
+            t.omega_lay[l] = o;
+        }
+    }
+    if (bw) atomicMin(bad, blockIdx.x);
+    if (bo) atomicMin(bad + 1, blockIdx.x);
 }
 // What changes between the launches of a batch, written into the items on the device (in stream order, so no launch sees half an update):
 // the run_solver gate and control block of each item — `ctl` null: outside run_solver — and the index of the launch's first iteration.

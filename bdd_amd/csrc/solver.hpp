@@ -77,6 +77,7 @@ struct SolverBase {
     // solver does not touch freed memory
     std::shared_ptr<int> lbfgs_attached = std::make_shared<int>(0);
     bool fused_small = false;   // whole iterations in one launch (diagnostics: bddmma_fused_small)
+    bool fused_small_learned = false;   // ... and whole learned iterations (bddmma_fused_small_learned)
     bool nt_loads = false;      // the solve sweeps' non-temporal instantiation (diagnostics: bddmma_nontemporal_loads)
     // run_solver (include/run_solver_util.h:10-77) around iteration(): termination tests on the device, see solver_impl.hpp
     virtual int run_plain(uint64_t max_iter, double tolerance, double slope, double time_limit, int verbose, bddmma_run_result* res) = 0;
@@ -171,6 +172,9 @@ struct BatchBase {
     virtual int run_plain(uint64_t max_iter, double tolerance, double slope, double time_limit, bddmma_run_result* res) = 0;
     virtual int time_iterations(double omega, uint64_t n, double* ms) = 0;   // iterations() between hipEvents on the batch stream; waits
     virtual int lower_bounds(double* out) = 0;              // SolverBase::lower_bound of every member, the reductions in flight together
+    // SolverBase::learned_iterations(w_i, num_itr, omega, slope 0, no history) of every member, or its omega_vec form; dist_weights /
+    // omega_vec: the members' REAL[nr_layers] one behind the other in the caller's order (include/bdd_mma.h: bddmma_learned_iterations_batch)
+    virtual int learned_iterations(const void* dist_weights, const void* omega_vec, double omega, uint64_t num_itr, int on_device) = 0;
 };
 // Refuses (before any device call): BDDMMA_ERR_INVALID_ARGUMENT for n == 0, a null member or a member listed twice; BDDMMA_ERR_UNSUPPORTED for
 // a member that is not fused_small or differs from member 0 in precision or device; BDDMMA_ERR_STATE for profiling / an L-BFGS wrapper.

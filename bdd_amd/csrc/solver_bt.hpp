@@ -40,6 +40,8 @@ struct BatchT final : BatchBase {
         for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1})
             if (e) (void)hipEventDestroy(e);
         if (d_items) (void)hipFree(d_items);
+        for (void* q : {(void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad})
+            if (q) (void)hipFree(q);
         if (d_ctl) (void)hipFree(d_ctl);
         if (h_ctl) (void)hipHostFree(h_ctl);
         if (h_run) (void)hipHostFree(h_run);
@@ -55,14 +57,14 @@ struct BatchT final : BatchBase {
     }
     // The dynamic-LDS limit of a batch kernel is a property of the function, shared by every batch of the process: it is only ever raised
     // (a limit is not a reservation), so that a later batch of smaller members does not take it away from an earlier one.
-    int raise_lds_limit(Fn fn, uint32_t lds)
+    int raise_lds_limit(const void* fn, uint32_t lds)
     {
         static std::mutex mtx;
-        static std::vector<std::pair<Fn, uint32_t>> limits;
+        static std::vector<std::pair<const void*, uint32_t>> limits;
         std::lock_guard<std::mutex> lock(mtx);
-        auto it = std::find_if(limits.begin(), limits.end(), [&](const std::pair<Fn, uint32_t>& e) { return e.first == fn; });
+        auto it = std::find_if(limits.begin(), limits.end(), [&](const std::pair<const void*, uint32_t>& e) { return e.first == fn; });
         if (it != limits.end() && it->second >= lds) return BDDMMA_OK;
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         if (it != limits.end()) it->second = lds;
         else limits.push_back({fn, lds});
         return BDDMMA_OK;
@@ -90,7 +92,7 @@ struct BatchT final : BatchBase {
         }
         HIPCHK(hipSetDevice(device));
         for (const Group& g : groups)
-            if (int rc = raise_lds_limit(g.fn, g.lds)) return rc;
+            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(g.fn), g.lds)) return rc;
         HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         ev_in.assign(n, nullptr);
         for (hipEvent_t& e : ev_in) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -190,6 +192,177 @@ struct BatchT final : BatchBase {
         return BDDMMA_OK;
     }
     int time_iterations(double omega, uint64_t n, double* ms) override { return iterations_timed(omega, n, ms); }
+
+    // ---- learned iterations (kernels/small.hpp: k_learned_small_batch; the kernels themselves compile in solver_sl_f32.hip / _f64.hip)
+    // Items and groups of their own: a member's learned form chooses records-in-LDS on its own budget, so the groups may differ from the
+    // plain ones.  Built by the first call (the members' weight and omega buffers are allocated then).  ln_tab[i] is member i's row of
+    // k_batch_learn_load, in the caller's order, as the concatenated inputs are.
+    using LnFn = typename S::SmallLnBatchFn;
+    struct LnGroup {
+        LnFn fn;
+        uint32_t threads, lds, first, count;
+    };
+    std::vector<LnGroup> ln_groups;
+    SmallLearnItem<REAL>* d_ln_items = nullptr;
+    LearnLoad<REAL>* d_ln_tab = nullptr;
+    REAL* d_ln_in = nullptr;       // host inputs on the device: weights | omega_vec, ln_total values each
+    uint32_t* d_ln_bad = nullptr;  // k_batch_learn_load's two words
+    std::vector<uint64_t> ln_src;  // first value of member i in the inputs
+    uint64_t ln_total = 0;
+    bool ln_ready = false;
+
+    int ln_prepare()
+    {
+        const uint32_t n = (uint32_t)m.size();
+        std::vector<uint32_t> ord(n);
+        for (uint32_t i = 0; i < n; ++i) ord[i] = i;
+        auto key = [&](uint32_t i) { return (uint32_t)m[i]->small_nw * 2u + (m[i]->small_ln_rl ? 1u : 0u); };
+        std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
+        for (S* s : m) {
+            int rc = BDDMMA_OK;
+            if (!s->d_alpha_ent) rc = s->dalloc(&s->d_alpha_ent, s->n_layers);
+            if (!rc && !s->d_omega_lay) rc = s->dalloc(&s->d_omega_lay, s->n_layers);
+            if (rc) { err = s->err; return rc; }
+        }
+        std::vector<SmallLearnItem<REAL>> items(n);
+        std::vector<LnGroup> groups_;
+        for (uint32_t j = 0; j < n; ++j) {
+            const S* s = m[ord[j]];
+            items[j] = s->small_learn_item();
+            if (groups_.empty() || key(ord[j]) != key(ord[groups_.back().first]))
+                groups_.push_back(LnGroup{S::sl_batch_fn(s->small_nw, s->small_ln_rl), 64u * (uint32_t)s->small_nw, 0u, j, 0u});
+            LnGroup& g = groups_.back();
+            g.lds = std::max(g.lds, s->small_ln_lds);
+            ++g.count;
+        }
+        for (const LnGroup& g : groups_)
+            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(g.fn), g.lds)) return rc;
+        std::vector<LearnLoad<REAL>> tab(n);
+        ln_src.assign(n, 0);
+        ln_total = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            ln_src[i] = ln_total;
+            tab[i] = LearnLoad<REAL>{m[i]->d_lpos, m[i]->d_alpha_ent, m[i]->d_omega_lay, (uint32_t)ln_total, (uint32_t)m[i]->n_layers};
+            ln_total += m[i]->n_layers;
+        }
+        HIPCHK(hipMalloc((void**)&d_ln_items, n * sizeof(SmallLearnItem<REAL>)));
+        HIPCHK(hipMalloc((void**)&d_ln_tab, n * sizeof(LearnLoad<REAL>)));
+        HIPCHK(hipMalloc((void**)&d_ln_in, 2 * ln_total * sizeof(REAL)));
+        HIPCHK(hipMalloc((void**)&d_ln_bad, 2 * sizeof(uint32_t)));
+        HIPCHK(hipMemcpy(d_ln_items, items.data(), n * sizeof(SmallLearnItem<REAL>), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_ln_tab, tab.data(), n * sizeof(LearnLoad<REAL>), hipMemcpyHostToDevice));
+        ln_groups = std::move(groups_);
+        return BDDMMA_OK;
+    }
+    int launch_learned(REAL omega, uint32_t n_iters, bool ov)
+    {
+        for (const LnGroup& g : ln_groups) {
+            hipLaunchKernelGGL(g.fn, dim3(g.count), dim3(g.threads), g.lds, stream, (const SmallLearnItem<REAL>*)(d_ln_items + g.first), omega, n_iters, ov ? 1u : 0u);
+            HIPCHK(hipGetLastError());
+        }
+        for (S* s : m) s->small_launched();
+        return BDDMMA_OK;
+    }
+    int learned_iterations(const void* w, const void* omega_vec, double omega, uint64_t num_itr, int on_dev) override
+    {
+        int rc;
+        const uint32_t n = (uint32_t)m.size();
+        if (!w) { err = "batch learned_iterations: dist_weights is null"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if ((rc = check_state())) return rc;
+        for (uint32_t i = 0; i < n; ++i)
+            if (!m[i]->small_ln_ok) {
+                err = "batch member " + std::to_string(i) + ": learned iterations do not fit one workgroup's LDS (bddmma_fused_small_learned is 0)";
+                return BDDMMA_ERR_UNSUPPORTED;
+            }
+        HIPCHK(hipSetDevice(device));
+        if (!ln_ready) {
+            if ((rc = ln_prepare())) return rc;
+            ln_ready = true;
+        }
+        const bool ov = omega_vec != nullptr;
+        // host inputs: checked here, before anything is copied
+        if (!on_dev) {
+            const void* arr[2] = {w, omega_vec};
+            const char* what[2] = {"dist_weights", "omega_vec"};
+            for (int a = 0; a < 2; ++a) {
+                const REAL* h = (const REAL*)arr[a];
+                if (!h) continue;
+                for (uint32_t i = 0; i < n; ++i)
+                    for (uint64_t l = 0; l < m[i]->n_layers; ++l) {
+                        const REAL x = h[ln_src[i] + l];
+                        if (!(x >= REAL(0) && x < std::numeric_limits<REAL>::infinity())) {
+                            err = "batch member " + std::to_string(i) + ": " + what[a] + "[" + std::to_string(l) + "] is negative or not finite";
+                            return BDDMMA_ERR_INVALID_ARGUMENT;
+                        }
+                    }
+            }
+        }
+        // The batch stream behind everything queued on the members (their earlier learned launches read the buffers written next); then one
+        // kernel checks every member's values and moves them into place.  The members' own state is not touched before the check is read.
+        for (uint32_t i = 0; i < n; ++i) {
+            HIPCHK(hipEventRecord(ev_in[i], m[i]->stream));
+            HIPCHK(hipStreamWaitEvent(stream, ev_in[i], 0));
+        }
+        const REAL *dw = (const REAL*)w, *dov = (const REAL*)omega_vec;
+        if (!on_dev) {
+            HIPCHK(hipMemcpyAsync(d_ln_in, w, ln_total * sizeof(REAL), hipMemcpyHostToDevice, stream));
+            dw = d_ln_in;
+            if (ov) {
+                HIPCHK(hipMemcpyAsync(d_ln_in + ln_total, omega_vec, ln_total * sizeof(REAL), hipMemcpyHostToDevice, stream));
+                dov = d_ln_in + ln_total;
+            }
+        }
+        HIPCHK(hipMemsetAsync(d_ln_bad, 0xFF, 2 * sizeof(uint32_t), stream));
+        hipLaunchKernelGGL((k_batch_learn_load<REAL>), dim3(n), dim3(256), 0, stream, (const LearnLoad<REAL>*)d_ln_tab, dw, dov, d_ln_bad);
+        HIPCHK(hipGetLastError());
+        uint32_t bad[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+        HIPCHK(hipMemcpyAsync(bad, d_ln_bad, sizeof(bad), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (bad[0] != 0xFFFFFFFFu || bad[1] != 0xFFFFFFFFu) {
+            const bool in_w = bad[0] != 0xFFFFFFFFu;
+            err = "batch member " + std::to_string(in_w ? bad[0] : bad[1]) + ": some of its " + (in_w ? "dist_weights" : "omega_vec") + " are negative or not finite";
+            (void)join_out();
+            return BDDMMA_ERR_INVALID_ARGUMENT;
+        }
+        if (num_itr == 0) return join_out();
+        // set_initial_lb_change, once per solver: the bounds before and after the first iteration, enqueued on the member's stream and fetched
+        // at the end — so the first iteration is a launch of its own when a member still wants it (n then m learned iterations are n + m)
+        std::vector<char> want(n, 0);
+        bool any = false;
+        for (uint32_t i = 0; i < n; ++i) {
+            want[i] = !std::isfinite(m[i]->initial_lb_change);
+            any = any || want[i];
+            if (want[i] && (rc = m[i]->lower_bound_enqueue(0))) { err = m[i]->err; (void)join_out(); return rc; }
+        }
+        uint64_t left = num_itr;
+        const REAL omega_r = (REAL)omega;
+        if (any) {
+            if ((rc = join_in())) { (void)join_out(); return rc; }
+            rc = launch_learned(omega_r, 1, ov);
+            const int rc2 = join_out();
+            if (rc || rc2) return rc ? rc : rc2;
+            for (uint32_t i = 0; i < n; ++i)
+                if (want[i] && (rc = m[i]->lower_bound_enqueue(1))) { err = m[i]->err; return rc; }
+            --left;
+        }
+        if (left) {
+            if ((rc = join_in())) { (void)join_out(); return rc; }
+            while (left) {
+                const uint32_t chunk = (uint32_t)std::min<uint64_t>(left, 1u << 14);   // as SolverT::iterations
+                if ((rc = launch_learned(omega_r, chunk, ov))) break;
+                left -= chunk;
+            }
+            const int rc2 = join_out();
+            if (rc || rc2) return rc ? rc : rc2;
+        }
+        for (uint32_t i = 0; i < n; ++i)
+            if (want[i]) {
+                double a = 0.0, b = 0.0;
+                if ((rc = m[i]->lower_bound_fetch(0, &a)) || (rc = m[i]->lower_bound_fetch(1, &b))) { err = m[i]->err; return rc; }
+                m[i]->initial_lb_change = std::abs(a - b);
+            }
+        return BDDMMA_OK;
+    }
 
     int lower_bounds(double* out) override
     {

@@ -191,6 +191,13 @@ struct SolverT final : SolverBase {
     uint32_t small_lds = 0;
     SmallDev small{};
     uint32_t* d_small_lds = nullptr;
+    // learned iterations inside one launch (kernels/small.hpp: k_learned_small): the plain layout (records in LDS or not on this form's own
+    // budget) + omega per layer.  The kernels live in solver_sl_f32.hip / _f64.hip: sl_prepare() resolves this
+    // solver's and raises its dynamic-LDS limit on the first call that launches it.
+    bool small_ln_ok = false, small_ln_rl = false, sl_ready = false;
+    uint32_t small_ln_lds = 0;
+    SmallDev small_ln{};
+    SmallLearn<REAL> small_ln_arg{};
     // streaming solve sweeps, third generation: a lane per layer (kernels/narrow3.hpp: k_fwd_narrow3 / k_bwd_narrow3)
     bool use_narrow3 = false;
     uint32_t *d_lrec = nullptr, *d_lrec_off = nullptr;
@@ -645,6 +652,26 @@ struct SolverT final : SolverBase {
                 small_nw = np <= 1 ? 1 : np <= 2 ? 2 : np <= 4 ? 4 : np <= 8 ? 8 : 16;
                 small_ok = true;
                 fused_small = true;
+                small_ln = small;
+                small_ln.rec_cap = (max_hops + 1u) * 1024u;
+                uint32_t max_layers = 0;
+                for (uint32_t p = 0; p < np; ++p) max_layers = std::max(max_layers, L.res.pack_hdr[8 * (size_t)p + 3]);
+                small_ln_arg.om_stride = max_layers;
+                auto learned_bytes = [&]() {
+                    const uint32_t plain = small_lds_bytes((uint32_t)sizeof(REAL), np, (uint32_t)n_vars, (uint32_t)n_layers, small_ln);
+                    return small_learn_lds_bytes((uint32_t)sizeof(REAL), np, res2_nl, max_layers, plain, small_ln_arg.off_om);
+                };
+                uint32_t lbytes = learned_bytes();
+                small_ln_rl = lbytes + 512 <= lds_cu;
+                if (!small_ln_rl) {
+                    small_ln.rec_cap = 0;
+                    lbytes = learned_bytes();
+                }
+                if (lbytes + 512 <= lds_cu) {
+                    small_ln_lds = lbytes;
+                    small_ln_ok = true;
+                    fused_small_learned = true;
+                }
             }
         }
         resolve_kernels();
@@ -875,6 +902,12 @@ struct SolverT final : SolverBase {
     }
 
     int ov_prepare();  // fills ov_sweep and raises its limits (solver_ov.hpp)
+    // the learned one-workgroup kernels (solver_sl.hpp): this solver's instantiation, and the batch form's for a (waves, records in LDS) pair
+    using SmallLnFn = void (*)(SmallDev, DevPtrs<REAL>, PackDev, SmallLearn<REAL>, REAL, uint32_t);
+    using SmallLnBatchFn = void (*)(const SmallLearnItem<REAL>*, REAL, uint32_t, uint32_t);
+    Kern<SmallLnFn> small_ln_kern;
+    int sl_prepare();
+    static SmallLnBatchFn sl_batch_fn(int nw, bool rl);
     bool ov_ready = false;
     // One sweep: the wide and the narrow packs (one launch where `mixed`; forward only with mixed_fwd), then the huge ones.
     int launch_sweep(bool bwd, const Sweep& s, const REAL* delta_lay, REAL omega, int kclass, bool ov = false)
@@ -1121,6 +1154,32 @@ struct SolverT final : SolverBase {
         small_launched();
         return BDDMMA_OK;
     }
+    // n learned iterations in one launch (k_learned_small): the weights from d_alpha_ent, omega per layer from d_omega_lay (`ov`) or the scalar
+    bool small_learned_usable() const { return small_ln_ok && small_usable(); }
+    int launch_small_learned(REAL omega, bool ov, uint32_t n)
+    {
+        int rc;
+        if (!sl_ready) {
+            if ((rc = sl_prepare())) return rc;
+            sl_ready = true;
+        }
+        if (!bwd_valid && (rc = backward_run())) return rc;  // as mma_forward
+        SmallLearn<REAL> ln = small_ln_arg;
+        ln.alpha_ent = d_alpha_ent;
+        ln.omega_lay = ov ? d_omega_lay : nullptr;
+        hipLaunchKernelGGL(small_ln_kern.fn, dim3(1), dim3(64 * small_nw), small_ln_kern.lds, stream, small_ln, ptrs(d_delta_lay), pdev(nb_, 0, 0), ln, omega, n);
+        HIPCHK(hipGetLastError());
+        small_launched();
+        return BDDMMA_OK;
+    }
+    // (d_alpha_ent and d_omega_lay must exist: BatchT::learned_iterations allocates them first)
+    SmallLearnItem<REAL> small_learn_item() const
+    {
+        SmallLearn<REAL> ln = small_ln_arg;
+        ln.alpha_ent = d_alpha_ent;
+        ln.omega_lay = d_omega_lay;
+        return SmallLearnItem<REAL>{small_ln, ptrs(d_delta_lay), pdev(nb_, 0, 0), ln};
+    }
     // the same launch as an item of a batch (solver_bt.hpp: one workgroup per member of BatchT); the run_solver fields are the batch's
     SmallItem<REAL> small_item() const { return SmallItem<REAL>{small, ptrs(d_delta_lay), pdev(nb_, 0, 0), RunStep{d_lb_partial, nb_.n_packs + wb_.n_packs + hb_.n_packs, nullptr, nullptr}}; }
     int iterations(double omega, uint64_t n) override
@@ -1276,7 +1335,25 @@ struct SolverT final : SolverBase {
         lb_post = lb_initial;
         bool converged = false;
         uint64_t tracked = 0, itr = 0, ran = 0;
-        for (itr = 0; itr < num_itr; ++itr) {
+        // One-workgroup instances without a stopping rule: the iterations the history does not reach run inside one launch each chunk
+        // (k_learned_small; n then m learned iterations are n + m, and a launch leaves the state this loop starts from).  The first
+        // iteration is a launch of its own where the initial change is still to be set: its bound is enqueued behind it.
+        uint64_t fused_n = (!track_lb && small_learned_usable()) ? num_itr - std::min(num_itr, cfi) : 0;
+        if (fused_n > 0) {
+            uint64_t left = fused_n;
+            if (want_initial) {
+                if ((rc = launch_small_learned(omega_r, ov, 1)) || (rc = lower_bound_enqueue(1))) return rc;
+                --left;
+            }
+            while (left) {
+                const uint32_t chunk = (uint32_t)std::min<uint64_t>(left, 1u << 14);   // as iterations()
+                if ((rc = launch_small_learned(omega_r, ov, chunk))) return rc;
+                left -= chunk;
+            }
+            ran = fused_n;
+        }
+        const bool loop_runs = fused_n < num_itr;   // false: the last launch has made the exit exchange itself
+        for (itr = fused_n; itr < num_itr; ++itr) {
             prof_active = profiling && (prof_iter++ % prof_stride == 0);
             weighted_exchange();  // forward_iteration_learned_mm_dist: compute_delta of the deferred differences (:68)
             if ((rc = mma_forward(omega_r, d_delta_lay, ov))) return rc;
@@ -1322,7 +1399,7 @@ struct SolverT final : SolverBase {
             }
         }
         // exit: the isotropic exchange of the last backward pass's differences — the state bddmma_iteration leaves
-        if (ran > 0 && (rc = exchange())) return rc;
+        if (ran > 0 && loop_runs && (rc = exchange())) return rc;
         if (ran > 0 && !track_lb && want_initial) {
             double a = 0.0, b = 0.0;
             if ((rc = lower_bound_fetch(0, &a)) || (rc = lower_bound_fetch(1, &b))) return rc;

@@ -91,6 +91,11 @@ class bdd_hip_parallel_mma:
     def fused_small(self) -> bool:
         """whole iterations run inside one launch (the instance fits one workgroup; csrc/kernels/small.hpp)"""
         return bool(self._L.bddmma_fused_small(self._h))
+    def fused_small_learned(self) -> bool:
+        """True when learned_iterations() runs whole learned iterations inside one launch too (with improvement_slope <= 0; batches of
+        such solvers: bdd_hip_batch.learned_iterations)"""
+        return bool(self._L.bddmma_fused_small_learned(self._h))
+
     def nontemporal_loads(self) -> bool:
         """the solve sweeps run in the instantiation that loads potentials and staging tables non-temporally (footprint beyond the caches' reach)"""
         return bool(self._L.bddmma_nontemporal_loads(self._h))
@@ -625,6 +630,21 @@ class bdd_hip_batch:
 
     def iterations(self, n, omega=0.5):
         self._check(self._L.bddmma_batch_iterations(self._h, float(omega), int(n)), self._h)
+
+    def learned_iterations(self, dist_weights, num_itr, omega=0.5, omega_vec=None):
+        """learned_iterations(w_i, num_itr, omega, improvement_slope=0.0) — with omega_vec its omega_vec form — of every member i, one
+        workgroup per member.  dist_weights / omega_vec: the members' REAL[nr_layers] one behind the other in the members' order (numpy
+        arrays or device tensors, both of one kind).  Every member must be fused_small_learned().  include/bdd_mma.h:
+        bddmma_learned_iterations_batch."""
+        n = sum(s.nr_layers() for s in self.solvers)
+        w, w_dev = self.solvers[0]._learned_buf(dist_weights, n, "dist_weights")
+        ov = None
+        if omega_vec is not None:
+            ov, ov_dev = self.solvers[0]._learned_buf(omega_vec, n, "omega_vec")
+            if ov_dev != w_dev:
+                raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: dist_weights and omega_vec must both be on the host or "
+                                       "both on the device")
+        self._check(self._L.bddmma_learned_iterations_batch(self._h, w, ov, float(omega), int(num_itr), w_dev), self._h)
 
     def time_iterations(self, n, omega=0.5) -> float:
         """iterations(n) between hipEvents on the batch's stream (first launch to last): elapsed device milliseconds"""

@@ -173,6 +173,10 @@ int bddmma_solve_sweep_kind(const bddmma_solver* s);
 /* 1 when the instance fits one workgroup and bddmma_iterations / bddmma_run_solver run whole iterations inside one launch (sweeps, exchanges
  * and run_solver's tests with workgroup barriers in between, csrc/kernels/small.hpp; variant_flags bit 19 turns it off), else 0. */
 int bddmma_fused_small(const bddmma_solver* s);
+/* 1 when bddmma_learned_iterations / _omega_vec run whole learned iterations inside one launch too (k_learned_small): bddmma_fused_small
+ * holds and the learned layout — the plain one plus an omega per layer — fits the CU's LDS as well.  With improvement_slope <= 0 the iterations that compute_history_for_itr does not reach then run fused; with a stopping rule
+ * (improvement_slope > 0) every iteration keeps the four launches.  variant_flags bit 19 turns it off together with bddmma_fused_small. */
+int bddmma_fused_small_learned(const bddmma_solver* s);
 /* 1 when the narrow packs' solve sweeps run in the instantiation that loads what a sweep reads once (potentials, staging tables) non-temporally. */
 int bddmma_nontemporal_loads(const bddmma_solver* s);
 int bddmma_precision(const bddmma_solver* s);
@@ -462,6 +466,18 @@ const char* bddmma_batch_last_error(const bddmma_batch* b);
 uint64_t bddmma_batch_size(const bddmma_batch* b);
 /* bddmma_iterations(member, omega, n) for every member */
 int bddmma_batch_iterations(bddmma_batch* b, double omega, uint64_t n);
+/* bddmma_learned_iterations(member i, w_i, .., num_itr, omega, 0.0, NULL, NULL, NULL, 0, 0.0, .., NULL) for every member i — or, with
+ * omega_vec non-null, bddmma_learned_iterations_omega_vec with member i's part of it: one workgroup per member, one launch per kernel
+ * instantiation present, results bit-equal to those calls (each member's set-once initial bound change included).
+ * dist_weights, and omega_vec when given: the members' REAL[nr_layers] in the public layer order, one behind the other in the members'
+ * order at bddmma_batch_create; both on the host or both on the device (on_device).  One kernel checks and loads all of them.
+ * Refusals, each before any member's costs, deferred differences, delta or initial change is touched, bddmma_batch_last_error naming
+ * the member: BDDMMA_ERR_STATE as for every batch call; BDDMMA_ERR_UNSUPPORTED for a member whose bddmma_fused_small_learned is 0;
+ * BDDMMA_ERR_INVALID_ARGUMENT for a negative or non-finite value (naming the array too).  num_itr == 0 does nothing.  With device
+ * inputs the host waits only for the check of the values and, where a member's initial change is still unset, for its two bounds.
+ * (Named after bddmma_learned_iterations, which it is for every member; the bddmma_batch_ prefix is kept for the batch object's own calls.) */
+int bddmma_learned_iterations_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec /* or NULL */, double omega,
+                                    uint64_t num_itr, int on_device);
 /* bddmma_run_solver(member, NULL, max_iter, tolerance, improvement_slope, time_limit, 0, &res[i]) for every member i: each member's tests
  * run inside its workgroup against its own control block and each stops on its own criterion; the host relaunches chunks of iterations
  * until every member has stopped or reached max_iter.  res (bddmma_batch_size entries, may be NULL): member i's iterations, bounds and
