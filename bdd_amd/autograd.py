@@ -6,7 +6,7 @@ mirrors); the differences are the ones include/bdd_mma.h has from the reference'
 
 Conventions of every function
   solvers     a list of bdd_hip_parallel_mma of one precision on one device, or a bdd_hip_batch: its members in order.  (Only
-              DualIterations.forward does anything else with a batch than with the list of its members.)
+              DualIterations — forward and backward — does anything else with a batch than with the list of its members.)
   tensors     1-D, contiguous, on the solvers' device, of the solvers' precision (torch.float32 / torch.float64 — the reference asks for
               torch's default dtype instead).  A batch tensor is the concatenation over the solvers, in list order, of each solver's array:
                 per layer     nr_layers() values in the public layer order (get_solver_costs, get_primal_variable_index) — there are
@@ -213,9 +213,13 @@ class DualIterations(torch.autograd.Function):
               counts; each count is remembered.  The last three outputs are None unless compute_history_for_itrs > 0 (they start as
               zeros: an entry the history does not reach keeps that) and are not differentiable.
     backward  bddmma_grad_learned_iterations per solver with track_grad_for_num_itr = min(iterations done, grad_dual_itr_max_itr) and
-              track_grad_after_itr = done - that: the untracked iterations are treated as constants, as in the reference.  Gradients for
+              track_grad_after_itr = done - that: the untracked iterations are treated as constants, as in the reference.  For a
+              bdd_hip_batch whose members are all fused_small_learned() and ran the same number of iterations, ONE
+              batch.grad_iterations (bddmma_grad_learned_iterations_batch: one workgroup per member) between the members'
+              set_solver_costs instead of that loop, with the same results (bit-equal in float, and in double wherever no variable
+              sits in more than two BDDs).  Gradients for
               lo, hi, def_mm, dist_weights and omega; one omega shared by several solvers gets the sum of their values, added in list
-              order in the solvers' precision.  State contract of that call: a solver holds the saved input state on entry (set here) and
+              order in the solvers' precision (on the torch side in both forms).  State contract of that call: a solver holds the saved input state on entry (set here) and
               again on return, both sweep states invalid; it refuses with BDDMMA_ERR_STATE (BddMmaError) while an L-BFGS wrapper is
               attached, and with BDDMMA_ERR_INVALID_ARGUMENT for a non-finite incoming gradient or a negative or non-finite weight or
               omega, each time leaving the solver untouched.  The reference's randomize_num_iterations belongs to its training loop and
@@ -273,13 +277,22 @@ class DualIterations(torch.autograd.Function):
         g_w = torch.zeros_like(dist_weights_batch)
         scalar = ctx.omega_scalar is not None
         g_om = torch.zeros(len(z.solvers), dtype=z.dtype, device=omega.device) if scalar else torch.zeros_like(omega)
+        done = ctx.iterations_done
+        batched = z.batch is not None and len(set(done)) == 1 and all(s.fused_small_learned() for s in z.solvers)
         with _Ordered(z.solvers):
             for i, (s, l) in enumerate(zip(z.solvers, z.slices(z.layers))):
                 s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], def_mm_batch[l])
-                n = min(ctx.iterations_done[i], ctx.grad_dual_itr_max_itr)
+                if batched:
+                    continue
+                n = min(done[i], ctx.grad_dual_itr_max_itr)
                 s.grad_iterations(dist_weights_batch[l], g_lo[l], g_hi[l], g_mm[l], omega=ctx.omega_scalar if scalar else 0.5,
-                                  track_grad_after_itr=ctx.iterations_done[i] - n, track_grad_for_num_itr=n, num_caches=ctx.num_caches,
+                                  track_grad_after_itr=done[i] - n, track_grad_for_num_itr=n, num_caches=ctx.num_caches,
                                   omega_vec=None if scalar else omega[l], out=(g_w[l], g_om[i:i + 1] if scalar else g_om[l]))
+            if batched:   # one workgroup per member, every member's arrays at once; g_om[i] is member i's own sum
+                n = min(done[0], ctx.grad_dual_itr_max_itr)
+                z.batch.grad_iterations(dist_weights_batch, g_lo, g_hi, g_mm, omega=ctx.omega_scalar if scalar else 0.5,
+                                        track_grad_after_itr=done[0] - n, track_grad_for_num_itr=n, num_caches=ctx.num_caches,
+                                        omega_vec=None if scalar else omega, out=(g_w, g_om))
         if scalar:
             total = g_om[0]
             for i in range(1, len(z.solvers)):

@@ -483,6 +483,18 @@ class bdd_hip_batch {
     {
         check(bddmma_learned_iterations_batch(b_, dev_dist_weights, dev_omega_vec, omega, num_itr, 1));
     }
+    // grad_iterations(...) of every member with its part of every device array (bdd_hip_parallel_mma::grad_iterations; the members' arrays
+    // one behind the other), one workgroup per member: dev_grad_omega has size() entries, the concatenated per-layer array with
+    // dev_omega_vec.  Contract: bddmma_grad_learned_iterations_batch.
+    void grad_iterations_dev(const REAL* dev_dist_weights, REAL* dev_grad_lo, REAL* dev_grad_hi, REAL* dev_grad_mm, REAL* dev_grad_dist_weights_out,
+                             REAL* dev_grad_omega, REAL omega_scalar, int track_grad_after_itr, int track_grad_for_num_itr, int num_caches,
+                             const REAL* dev_omega_vec = nullptr)
+    {
+        if (track_grad_after_itr < 0 || track_grad_for_num_itr < 0 || num_caches < 0) throw std::invalid_argument("grad_iterations: negative count");
+        check(bddmma_grad_learned_iterations_batch(b_, dev_dist_weights, dev_omega_vec, (double)omega_scalar, dev_grad_lo, dev_grad_hi, dev_grad_mm,
+                                                   dev_grad_dist_weights_out, dev_grad_omega, (uint64_t)track_grad_after_itr,
+                                                   (uint64_t)track_grad_for_num_itr, (uint64_t)num_caches, 1));
+    }
     std::vector<bddmma_run_result> run_solver(const size_t max_iter = 1000, const double tolerance = 1e-6, const double improvement_slope = 1e-9,
                                               const double time_limit = 3600.0)
     {

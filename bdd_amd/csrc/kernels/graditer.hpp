@@ -1,6 +1,6 @@
 // kernels/graditer.hpp — the reverse of the two passes of a learned MMA iteration (bdd_cuda_learned_mma.cu:308-385 with :418-621,
-// grad_iterations): k_gi_down reverses a backward pass, k_gi_up a forward pass.  Included by solver_gi.hpp only (translation units
-// solver_gi_f32.hip / solver_gi_f64.hip), behind kernels.hpp.
+// grad_iterations): k_gi_down reverses a backward pass, k_gi_up a forward pass.  Included by solver_gi.hpp (translation units
+// solver_gi_f32.hip / solver_gi_f64.hip) and, for the sweeps' bodies, by kernels/gradsmall.hpp; behind kernels.hpp.
 //
 // A pass is described by what it read and wrote (GiArgs): the arc costs before (pre) and after it (post), the potentials F and T its
 // min-marginals m_a[l] = min over the nodes u of l of F[u] + pre_a[l] + T[child_a(u)] were taken with, its mm[l] = omega_l (m_hi - m_lo), and
@@ -57,9 +57,43 @@ struct GiFold {
 
 // Steps (3) and (4) for layer l at its head: dc = what reached the post costs through the potentials, (m0, m1) the layer's min-marginals.
 // Returns t (0: no seeds) and writes the layer's outputs.
+// PIN (k_grad_small_batch): the products and sums below spelled out operation by operation, with contraction off.  Written as expressions
+// they are contracted by the compiler as it sees fit in each kernel, and the narrow kernels k_gi_down / k_gi_up — whose bits the batch form
+// promises — came out as: g_alpha's S_lo g_lo + S_hi g_hi two rounded products and a sum in float, fma(g_lo, S_lo, S_hi g_hi) in double;
+// g_omega by one fma; g_hi + t by one fma; g_lo - t a subtraction of the rounded t in float, one fma in double.  The pinned form states
+// exactly that, so that the fused kernel's bits do not depend on what surrounds this function there
+// (tests/test_gpu_grad_small.py::test_batch_equals_each_member_on_the_four_launch_path holds the two together).
+__device__ __forceinline__ float gi_fma(float x, float y, float z) { return __builtin_fmaf(x, y, z); }
+__device__ __forceinline__ double gi_fma(double x, double y, double z) { return __builtin_fma(x, y, z); }
 template <typename REAL>
+__device__ __forceinline__ REAL gi_dual_pinned(const GiArgs<REAL>& a, uint32_t l, REAL dc0, REAL dc1, REAL m0, REAL m1)
+{
+#pragma clang fp contract(off)
+    REAL g0 = dc0 + a.g_lo[l], g1 = dc1 + a.g_hi[l];
+    const REAL dmm = a.g_mm[l] + (a.mm[l] >= REAL(0) ? -g1 : g0);
+    const REAL al = a.alpha[l];
+    const uint32_t v = (uint32_t)a.var[l];
+    a.gS[2 * (size_t)l] = al * g0;
+    a.gS[2 * (size_t)l + 1] = al * g1;
+    const REAL p1 = a.S[2 * (size_t)v + 1] * g1;
+    const REAL sg = sizeof(REAL) == 4 ? a.S[2 * (size_t)v] * g0 + p1 : gi_fma(g0, a.S[2 * (size_t)v], p1);
+    a.g_alpha[l] = a.g_alpha[l] + sg;
+    REAL t = REAL(0);
+    if (m0 < inf_v<REAL>() && m1 < inf_v<REAL>()) {
+        a.g_omega[l] = gi_fma(m1 - m0, dmm, a.g_omega[l]);
+        const REAL om = a.omega_lay ? a.omega_lay[l] : a.omega;
+        t = om * dmm;
+        g0 = sizeof(REAL) == 4 ? g0 - t : gi_fma(-dmm, om, g0);
+        g1 = gi_fma(dmm, om, g1);
+    }
+    a.g_lo[l] = g0;
+    a.g_hi[l] = g1;
+    return t;
+}
+template <typename REAL, bool PIN = false>
 __device__ __forceinline__ REAL gi_dual(const GiArgs<REAL>& a, uint32_t l, REAL dc0, REAL dc1, REAL m0, REAL m1)
 {
+    if constexpr (PIN) return gi_dual_pinned(a, l, dc0, dc1, m0, m1);
     REAL g0 = dc0 + a.g_lo[l], g1 = dc1 + a.g_hi[l];
     const REAL dmm = a.g_mm[l] + (a.mm[l] >= REAL(0) ? -g1 : g0);
     const REAL al = a.alpha[l];
@@ -80,11 +114,11 @@ __device__ __forceinline__ REAL gi_dual(const GiArgs<REAL>& a, uint32_t l, REAL 
 }
 
 // the layer fold of both sweeps: A0 / A1 what each slot adds to the layer's sums, P0 / P1 its path values (FULL), runs kept in Q0 / Q1 / I0 / I1
-template <typename REAL, bool FULL, typename DONE>
+template <typename REAL, bool FULL, typename BAR, typename DONE>
 __device__ __forceinline__ void gi_fold(const PullPack<REAL>& pc, const uint32_t* Lid, uint32_t n, const REAL* A0, const REAL* A1, const REAL* P0,
                                         const REAL* P1, REAL* Q0, REAL* Q1, uint32_t* I0, uint32_t* I1, DONE done)
 {
-    pull_layer_fold(
+    pull_layer_fold_bar<BAR>(
         pc, Lid, n, [&](uint32_t j) { return GiFold<REAL>{A0[j], A1[j], j, j}; },
         [&](GiFold<REAL> v, GiFold<REAL> w) {
             GiFold<REAL> r{v.s0 + w.s0, v.s1 + w.s1, v.i0, v.i1};
@@ -98,12 +132,12 @@ __device__ __forceinline__ void gi_fold(const PullPack<REAL>& pc, const uint32_t
         [&](uint32_t j) { return GiFold<REAL>{Q0[j], Q1[j], I0[j], I1[j]}; }, done);
 }
 
-template <typename REAL, bool NARROW, bool GLOBAL, bool FULL>
-__global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gi_down(DevPtrs<REAL> d, PackDev pk, const uint32_t* par_ptr, const uint32_t* par, uint32_t ww,
-                                                                        unsigned char* scratch, GiArgs<REAL> a)
+// The sweeps' bodies for the pack `pc`: k_gi_down / k_gi_up run them with the workgroup's pack and PullBlockBar (__syncthreads()) as BAR,
+// k_grad_small_batch (kernels/gradsmall.hpp) with a wave's pack and a wave-level ordering point.
+template <typename REAL, bool NARROW, bool FULL, typename BAR, bool PIN = false>
+__device__ __forceinline__ void gi_down_body(const DevPtrs<REAL>& d, const PackDev& pk, const PullPack<REAL>& pc, const uint32_t* par_ptr, const uint32_t* par,
+                                             uint32_t ww, const GiArgs<REAL>& a)
 {
-    if (blockIdx.x >= pk.n_packs) return;
-    const PullPack<REAL> pc = pull_pack<REAL, NARROW, GLOBAL>(d, pk, ww, scratch, gi_lds_bytes(sizeof(REAL), ww));
     REAL* const S = pc.base;                    // [hop parity][arc][slot]: what the node sends along the arc
     REAL* const P0 = pc.base + 4 * (size_t)ww;  // F + pre + T[child] through the lo arc per slot
     REAL* const P1 = pc.base + 5 * (size_t)ww;
@@ -130,12 +164,12 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gi_down(DevPtrs<
                 P1[j] = (f + a.pre[2 * (size_t)nd.layer + 1]) + th;
             }
         });
-        __syncthreads();
+        BAR::sync();
         // ---- the layer's sums and arg-mins; (3), (4) at its head: only the head touches its layer's slots of S here
-        gi_fold<REAL, FULL>(pc, Lid, n, Sc, Sc + ww, P0, P1, Q0, Q1, I0, I1, [&](uint32_t l, GiFold<REAL> v) {
+        gi_fold<REAL, FULL, BAR>(pc, Lid, n, Sc, Sc + ww, P0, P1, Q0, Q1, I0, I1, [&](uint32_t l, GiFold<REAL> v) {
             const uint32_t L = lbase + l;
             if constexpr (FULL) {
-                const REAL t = gi_dual(a, L, v.s0, v.s1, P0[v.i0], P1[v.i1]);
+                const REAL t = gi_dual<REAL, PIN>(a, L, v.s0, v.s1, P0[v.i0], P1[v.i1]);
                 if (t != REAL(0)) {
                     Sc[v.i0] -= t;
                     Sc[ww + v.i1] += t;
@@ -147,16 +181,23 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gi_down(DevPtrs<
                 a.g_hi[L] += v.s1;
             }
         });
-        __syncthreads();  // the next hop overwrites P, Q, I and Lid and pulls from this hop's S
+        BAR::sync();  // the next hop overwrites P, Q, I and Lid and pulls from this hop's S
     }
 }
 
-template <typename REAL, bool NARROW, bool GLOBAL>
-__global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gi_up(DevPtrs<REAL> d, PackDev pk, const uint32_t* par_ptr, const uint32_t* par, uint32_t ww,
-                                                                      unsigned char* scratch, GiArgs<REAL> a)
+template <typename REAL, bool NARROW, bool GLOBAL, bool FULL>
+__global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gi_down(DevPtrs<REAL> d, PackDev pk, const uint32_t* par_ptr, const uint32_t* par, uint32_t ww,
+                                                                        unsigned char* scratch, GiArgs<REAL> a)
 {
     if (blockIdx.x >= pk.n_packs) return;
     const PullPack<REAL> pc = pull_pack<REAL, NARROW, GLOBAL>(d, pk, ww, scratch, gi_lds_bytes(sizeof(REAL), ww));
+    gi_down_body<REAL, NARROW, FULL, PullBlockBar>(d, pk, pc, par_ptr, par, ww, a);
+}
+
+template <typename REAL, bool NARROW, typename BAR, bool PIN = false>
+__device__ __forceinline__ void gi_up_body(const DevPtrs<REAL>& d, const PackDev& pk, const PullPack<REAL>& pc, const uint32_t* par_ptr, const uint32_t* par,
+                                           uint32_t ww, const GiArgs<REAL>& a)
+{
     REAL* const D = pc.base;                    // [hop parity][slot]: dF
     REAL* const V0 = pc.base + 2 * (size_t)ww;  // F + post lo cost per slot; after the children's arg-min: what the node took over its lo arc
     REAL* const V1 = pc.base + 3 * (size_t)ww;
@@ -180,10 +221,10 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gi_up(DevPtrs<RE
             V0[j] = f + a.post[2 * (size_t)nd.layer];
             V1[j] = f + a.post[2 * (size_t)nd.layer + 1];
         });
-        __syncthreads();
+        BAR::sync();
         // ---- the children's arg-min (parent, arc): first in parent table order wins a tie; a root or an unreachable node names nobody
         gr_name_parents(pc, par_ptr, par, nbn + pc.wdelta, nn, V0, V1, AP);
-        __syncthreads();
+        BAR::sync();
         // ---- dF = the incoming gF + dF of the children that name this node; the path values of the min-marginals
         pull_slots<REAL, NARROW, false>(d, pc, nb, n, lbase, nullptr, [&](uint32_t j, uint32_t, const PullNode& nd) {
             const Pull2<REAL> t = gr_take_up(nd, j, nn, AP, Dn);
@@ -194,9 +235,9 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gi_up(DevPtrs<RE
             P0[j] = (f + a.pre[2 * (size_t)nd.layer]) + gr_child_T(a.T, nbn, nd.lo);
             P1[j] = (f + a.pre[2 * (size_t)nd.layer + 1]) + gr_child_T(a.T, nbn, nd.hi);
         });
-        __syncthreads();  // AP is dead: the fold keeps its runs' minima there
-        gi_fold<REAL, true>(pc, Lid, n, V0, V1, P0, P1, Q0, Q1, I0, I1, [&](uint32_t l, GiFold<REAL> v) {
-            const REAL t = gi_dual(a, lbase + l, v.s0, v.s1, P0[v.i0], P1[v.i1]);
+        BAR::sync();  // AP is dead: the fold keeps its runs' minima there
+        gi_fold<REAL, true, BAR>(pc, Lid, n, V0, V1, P0, P1, Q0, Q1, I0, I1, [&](uint32_t l, GiFold<REAL> v) {
+            const REAL t = gi_dual<REAL, PIN>(a, lbase + l, v.s0, v.s1, P0[v.i0], P1[v.i1]);
             if (t != REAL(0)) {
                 Dc[v.i0] -= t;
                 Dc[v.i1] += t;
@@ -205,18 +246,25 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gi_up(DevPtrs<RE
                 if (c1 < nn) a.g_out[nbn + c1] += t;
             }
         });
-        __syncthreads();  // the next hop overwrites every array but this hop's dF
+        BAR::sync();  // the next hop overwrites every array but this hop's dF
     }
+}
+
+template <typename REAL, bool NARROW, bool GLOBAL>
+__global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gi_up(DevPtrs<REAL> d, PackDev pk, const uint32_t* par_ptr, const uint32_t* par, uint32_t ww,
+                                                                      unsigned char* scratch, GiArgs<REAL> a)
+{
+    if (blockIdx.x >= pk.n_packs) return;
+    const PullPack<REAL> pc = pull_pack<REAL, NARROW, GLOBAL>(d, pk, ww, scratch, gi_lds_bytes(sizeof(REAL), ww));
+    gi_up_body<REAL, NARROW, PullBlockBar>(d, pk, pc, par_ptr, par, ww, a);
 }
 
 // ---- elementwise
 // S[v] = {sum of -d over d < 0, sum of d over d > 0} over the layers of v, in the order of the variable -> layer table (d in layer order)
+// (the `_at` functions: one variable / layer of each, shared with k_grad_small_batch, kernels/gradsmall.hpp)
 template <typename REAL>
-__global__ void k_gi_sums(const REAL* __restrict__ dl, const uint32_t* __restrict__ var_ptr, const uint32_t* __restrict__ var_layers, REAL* __restrict__ S,
-                          uint32_t n_vars)
+__device__ __forceinline__ void gi_sums_at(const REAL* dl, const uint32_t* var_ptr, const uint32_t* var_layers, REAL* S, uint32_t v)
 {
-    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= n_vars) return;
     REAL s0 = 0, s1 = 0;
     for (uint32_t k = var_ptr[v], e = var_ptr[v + 1]; k < e; ++k) {
         const REAL x = dl[var_layers[k]];
@@ -226,13 +274,18 @@ __global__ void k_gi_sums(const REAL* __restrict__ dl, const uint32_t* __restric
     S[2 * (size_t)v] = s0;
     S[2 * (size_t)v + 1] = s1;
 }
-// gS[v] = the sum of gS[l] over the layers of v, same order
 template <typename REAL>
-__global__ void k_gi_var_sums(const REAL* __restrict__ gS, const uint32_t* __restrict__ var_ptr, const uint32_t* __restrict__ var_layers, REAL* __restrict__ gSv,
-                              uint32_t n_vars)
+__global__ void k_gi_sums(const REAL* __restrict__ dl, const uint32_t* __restrict__ var_ptr, const uint32_t* __restrict__ var_layers, REAL* __restrict__ S,
+                          uint32_t n_vars)
 {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n_vars) return;
+    gi_sums_at(dl, var_ptr, var_layers, S, v);
+}
+// gS[v] = the sum of gS[l] over the layers of v, same order
+template <typename REAL>
+__device__ __forceinline__ void gi_var_sums_at(const REAL* gS, const uint32_t* var_ptr, const uint32_t* var_layers, REAL* gSv, uint32_t v)
+{
     REAL s0 = 0, s1 = 0;
     for (uint32_t k = var_ptr[v], e = var_ptr[v + 1]; k < e; ++k) {
         s0 += gS[2 * (size_t)var_layers[k]];
@@ -241,14 +294,27 @@ __global__ void k_gi_var_sums(const REAL* __restrict__ gS, const uint32_t* __res
     gSv[2 * (size_t)v] = s0;
     gSv[2 * (size_t)v + 1] = s1;
 }
+template <typename REAL>
+__global__ void k_gi_var_sums(const REAL* __restrict__ gS, const uint32_t* __restrict__ var_ptr, const uint32_t* __restrict__ var_layers, REAL* __restrict__ gSv,
+                              uint32_t n_vars)
+{
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_vars) return;
+    gi_var_sums_at(gS, var_ptr, var_layers, gSv, v);
+}
 // the gradient of the differences a pass consumed (:503-518): gd[l] = d[l] >= 0 ? gS_hi[v] : -gS_lo[v]
+template <typename REAL>
+__device__ __forceinline__ void gi_gd_at(const REAL* dl, const REAL* gSv, const int32_t* var, REAL* gd, uint32_t l)
+{
+    const uint32_t v = (uint32_t)var[l];
+    gd[l] = dl[l] >= REAL(0) ? gSv[2 * (size_t)v + 1] : -gSv[2 * (size_t)v];
+}
 template <typename REAL>
 __global__ void k_gi_gd(const REAL* __restrict__ dl, const REAL* __restrict__ gSv, const int32_t* __restrict__ var, REAL* __restrict__ gd, uint32_t n)
 {
     const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
     if (l >= n) return;
-    const uint32_t v = (uint32_t)var[l];
-    gd[l] = dl[l] >= REAL(0) ? gSv[2 * (size_t)v + 1] : -gSv[2 * (size_t)v];
+    gi_gd_at(dl, gSv, var, gd, l);
 }
 // the gradient of a scalar omega: the per-layer values summed in double by one workgroup, every thread its strided share in layer order, then a
 // tree over the threads — a fixed order

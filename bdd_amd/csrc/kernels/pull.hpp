@@ -125,9 +125,14 @@ __device__ __forceinline__ Pull2<X> pull_add(Pull2<X> v, Pull2<X> w) { return {v
 //   at(j)       the value of slot j                 put(j, v)   keep a run's value, j its first slot
 //   comb(v, w)  v combined with the later w         get(j)      ... and read it back
 //   done(l, v)  the value of layer l, at its head
+//   BAR::sync() the barrier between the two levels: __syncthreads() where the pack is a workgroup's (PullBlockBar), a wave-level ordering
+//               point where it is one wave's among several of a workgroup (kernels/gradsmall.hpp)
 // The caller's barrier follows.
-template <typename REAL, typename AT, typename COMB, typename PUT, typename GET, typename DONE>
-__device__ __forceinline__ void pull_layer_fold(const PullPack<REAL>& pc, const uint32_t* Lid, uint32_t n, AT at, COMB comb, PUT put, GET get, DONE done)
+struct PullBlockBar {   // the pack is a workgroup's
+    static __device__ __forceinline__ void sync() { __syncthreads(); }
+};
+template <typename BAR, typename REAL, typename AT, typename COMB, typename PUT, typename GET, typename DONE>
+__device__ __forceinline__ void pull_layer_fold_bar(const PullPack<REAL>& pc, const uint32_t* Lid, uint32_t n, AT at, COMB comb, PUT put, GET get, DONE done)
 {
     auto run_start = [&](uint32_t j, uint32_t l) { return l != PULL_NO_LAYER && (j % PULL_CHUNK == 0 || j == 0 || Lid[j - 1] != l); };
     auto is_head = [&](uint32_t j, uint32_t l) { return l != PULL_NO_LAYER && (j == 0 || Lid[j - 1] != l); };
@@ -139,7 +144,7 @@ __device__ __forceinline__ void pull_layer_fold(const PullPack<REAL>& pc, const 
             put(j, v);
         }
     }
-    __syncthreads();
+    BAR::sync();
     for (uint32_t j = pc.tid; j < n; j += pc.T) {
         const uint32_t l = Lid[j];
         if (is_head(j, l)) {
@@ -148,6 +153,11 @@ __device__ __forceinline__ void pull_layer_fold(const PullPack<REAL>& pc, const 
             done(l, v);
         }
     }
+}
+template <typename REAL, typename AT, typename COMB, typename PUT, typename GET, typename DONE>
+__device__ __forceinline__ void pull_layer_fold(const PullPack<REAL>& pc, const uint32_t* Lid, uint32_t n, AT at, COMB comb, PUT put, GET get, DONE done)
+{
+    pull_layer_fold_bar<PullBlockBar>(pc, Lid, n, at, comb, put, get, done);
 }
 
 }  // namespace bddmma

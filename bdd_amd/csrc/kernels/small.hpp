@@ -97,6 +97,24 @@ inline uint32_t small_learn_lds_bytes(uint32_t real_size, uint32_t n_packs, uint
     return o + ((n_packs - 1u) * max_layers + small_stage_stride(nl)) * real_size;
 }
 
+// RECORD (k_grad_small_batch, kernels/gradsmall.hpp: the backward of the learned iterations): what the reverse of iteration k reads, written to
+// global memory at the pass boundaries — in front of iteration k (and behind the last one, k = n_iters) the arc costs, the deferred
+// differences in layer order and the costs-to-terminal; behind its forward sweep the arc costs, the differences and the costs-from-root.
+// One block of 6 ls + 2 ss values per iteration, ls / ss the solver's layer / slot counts rounded up to 4: c (2 ls) | dm (ls) | T (ss) | c1 (2 ls) |
+// mm1 (ls) | F (ss); the block behind the last iteration holds the first three.  Layers and slots are the solver's.
+template <typename REAL>
+struct SmallRecord {
+    REAL* base;
+    uint32_t ls, ss;
+    __host__ __device__ size_t stride() const { return 6 * (size_t)ls + 2 * (size_t)ss; }
+    __host__ __device__ REAL* c(uint32_t k) const { return base + k * stride(); }          // in front of iteration k
+    __host__ __device__ REAL* dm(uint32_t k) const { return c(k) + 2 * (size_t)ls; }
+    __host__ __device__ REAL* T(uint32_t k) const { return dm(k) + ls; }
+    __host__ __device__ REAL* c1(uint32_t k) const { return T(k) + ss; }                    // behind its forward sweep
+    __host__ __device__ REAL* mm1(uint32_t k) const { return c1(k) + 2 * (size_t)ls; }
+    __host__ __device__ REAL* F(uint32_t k) const { return mm1(k) + ls; }
+};
+
 // The workgroup's work, shared by k_iterate_small (one instance per launch) and k_iterate_small_batch (one instance per workgroup).
 // NW waves, pack p on wave p (n_packs <= NW); RL: the packs' records live in LDS too (1 KiB per hop), else they stream from L2 eight hops ahead
 // LEARNED (k_learned_small, k_learned_small_batch): n learned iterations,
@@ -107,10 +125,11 @@ inline uint32_t small_learn_lds_bytes(uint32_t real_size, uint32_t n_packs, uint
 // omega from its layer's slot.  The plain exchange behind the last backward sweep and the plain epilogue leave what the four-launch path
 // leaves: the last backward pass's differences deferred, delta their isotropic exchange, the bound's partial sums.  No run_solver (run.ctl
 // is null there), so no early return at all.
-template <typename REAL, int NW, bool RL, bool LEARNED = false>
+template <typename REAL, int NW, bool RL, bool LEARNED = false, bool RECORD = false>
 __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<REAL>& d, const PackDev& pk, REAL omega, uint32_t n_iters, const RunStep& run,
-                                              const SmallLearn<REAL>* ln = nullptr)
+                                              const SmallLearn<REAL>* ln = nullptr, const SmallRecord<REAL>* rec = nullptr)
 {
+    static_assert(!RECORD || LEARNED, "only the learned iterations are recorded");
     constexpr uint32_t S = sizeof(REAL);
     constexpr uint32_t NT = 64 * NW;
     using P2 = typename Pair<REAL>::type;
@@ -319,10 +338,29 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
         for (uint32_t v = tid + NT; v < sm.n_vars; v += NT) generic(v);
     };
 
+    // RECORD: this wave's pack -> the record of iteration k; `mid`: behind the forward sweep.  The caller's barrier follows (the exchange
+    // behind it overwrites the differences).
+    auto record = [&](uint32_t k, bool mid) {
+        if constexpr (RECORD) {
+            if (!has_pack) return;
+            P2* const cg = reinterpret_cast<P2*>(mid ? rec->c1(k) : rec->c(k)) + layer0;
+            REAL* const dg = (mid ? rec->mm1(k) : rec->dm(k)) + layer0;
+            REAL* const pg = (mid ? rec->F(k) : rec->T(k)) + slot0;
+            for (uint32_t j = (uint32_t)lane; j < nlayers; j += 64u) {
+                cg[j] = lds_ld<P2>(dyn_lds, wbC + j * (uint32_t)sizeof(P2));
+                dg[j] = lds_ld<REAL>(dyn_lds, db + j * (uint32_t)sizeof(P2));
+            }
+            for (uint32_t j = (uint32_t)lane; j < nslots; j += 64u) pg[j] = lds_ld<REAL>(dyn_lds, (mid ? wbF : wb) + j * S);
+        }
+    };
     constexpr std::integral_constant<bool, false> PLAIN_EX{};
     constexpr std::integral_constant<bool, LEARNED> ITER_EX{};
     uint32_t it = 0;
     for (; it < n_iters; ++it) {
+        if constexpr (RECORD) {
+            record(it, false);
+            __syncthreads();
+        }
         if constexpr (LEARNED) {   // forward_iteration_learned_mm_dist: the weighted exchange of the deferred differences in front of the sweep
             exchange(false, ITER_EX);
             __syncthreads();
@@ -390,6 +428,10 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
             }
         }
         __syncthreads();
+        if constexpr (RECORD) {
+            record(it, true);
+            __syncthreads();
+        }
 #ifdef BDDMMA_EXP_SMALL_SKIP
         if (!(BDDMMA_EXP_SMALL_SKIP & 2))
 #endif
@@ -487,6 +529,10 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
         }
     }
     (void)it;
+    if constexpr (RECORD) {
+        record(n_iters, false);
+        __syncthreads();
+    }
     if constexpr (LEARNED) {   // the exit state: the last backward pass's differences deferred, delta their isotropic exchange
         exchange(true, PLAIN_EX);
         __syncthreads();

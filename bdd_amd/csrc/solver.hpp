@@ -175,6 +175,11 @@ struct BatchBase {
     // SolverBase::learned_iterations(w_i, num_itr, omega, slope 0, no history) of every member, or its omega_vec form; dist_weights /
     // omega_vec: the members' REAL[nr_layers] one behind the other in the caller's order (include/bdd_mma.h: bddmma_learned_iterations_batch)
     virtual int learned_iterations(const void* dist_weights, const void* omega_vec, double omega, uint64_t num_itr, int on_device) = 0;
+    // SolverBase::grad_learned_iterations of every member with its part of every array, one workgroup per member in one launch
+    // (include/bdd_mma.h: bddmma_grad_learned_iterations_batch)
+    virtual int grad_learned_iterations(const void* dist_weights, const void* omega_vec, double omega, void* grad_lo, void* grad_hi, void* grad_mm,
+                                        void* grad_dist_weights_out, void* grad_omega_out, uint64_t track_grad_after_itr, uint64_t track_grad_for_num_itr,
+                                        uint64_t num_caches, int on_device) = 0;
 };
 // Refuses (before any device call): BDDMMA_ERR_INVALID_ARGUMENT for n == 0, a null member or a member listed twice; BDDMMA_ERR_UNSUPPORTED for
 // a member that is not fused_small or differs from member 0 in precision or device; BDDMMA_ERR_STATE for profiling / an L-BFGS wrapper.

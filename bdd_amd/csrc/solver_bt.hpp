@@ -6,6 +6,7 @@
 #include <mutex>
 
 #include "solver_impl.hpp"
+#include "kernels/gradsmall.hpp"
 
 namespace bddmma {
 
@@ -40,7 +41,7 @@ struct BatchT final : BatchBase {
         for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1})
             if (e) (void)hipEventDestroy(e);
         if (d_items) (void)hipFree(d_items);
-        for (void* q : {(void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad})
+        for (void* q : {(void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad})
             if (q) (void)hipFree(q);
         if (d_ctl) (void)hipFree(d_ctl);
         if (h_ctl) (void)hipHostFree(h_ctl);
@@ -362,6 +363,205 @@ struct BatchT final : BatchBase {
                 m[i]->initial_lb_change = std::abs(a - b);
             }
         return BDDMMA_OK;
+    }
+
+    // ---- the backward of the learned iterations (kernels/gradsmall.hpp: k_grad_small_batch; the kernels compile in solver_gs_f32.hip / _f64.hip)
+    // One workgroup per member runs the whole call: the tracked iterations once, recording, then their reverse.  The workspace — per member
+    // the entry state, the arguments, the reverse's scratch and the records of every tracked iteration — is the batch's: allocated before
+    // any member is touched, grown only when a call tracks more iterations than any call before it, freed with the batch.
+    using GsFn = typename S::GradSmallFn;
+    struct GsGroup {
+        GsFn fn;
+        uint32_t threads, lds, first, count;
+    };
+    std::vector<GsGroup> gs_groups;
+    std::vector<GradSmallItem<REAL>> gs_items;   // host copy, in launch order (member order within a group)
+    std::vector<uint64_t> gs_slab_off;           // per item: first value of its slab for gs_n_rec tracked iterations
+    GradSmallItem<REAL>* d_gs_items = nullptr;
+    REAL *d_gs_ws = nullptr, *d_gs_io = nullptr; // the workspace; host arguments and results on the device: 5 inputs | 5 outputs
+    uint32_t* d_gs_bad = nullptr;                // k_grad_small_load's five words
+    uint64_t gs_n_rec = 0, gs_total = 0;         // tracked iterations the workspace holds; values of all members' layers
+    bool gs_ready = false;
+
+    int gs_prepare()
+    {
+        const uint32_t n = (uint32_t)m.size();
+        if (!ln_ready) {
+            if (int rc = ln_prepare()) return rc;
+            ln_ready = true;
+        }
+        for (S* s : m)
+            if (int rc = s->sm_prepare()) { err = s->err; return rc; }   // the parent tables of the pull sweeps
+        std::vector<uint32_t> ord(n);
+        for (uint32_t i = 0; i < n; ++i) ord[i] = i;
+        auto key = [&](uint32_t i) { return (uint32_t)m[i]->small_nw * 2u + (m[i]->small_ln_rl ? 1u : 0u); };
+        std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });
+        auto up4 = [](uint64_t x) { return (uint32_t)((x + 3) & ~3ull); };
+        std::vector<GsGroup> groups_;
+        gs_items.assign(n, GradSmallItem<REAL>{});
+        for (uint32_t j = 0; j < n; ++j) {
+            const S* s = m[ord[j]];
+            GradSmallItem<REAL>& it = gs_items[j];
+            it.fw = s->small_learn_item();
+            it.par_ptr = s->d_sm_nptr; it.par = s->d_sm_npar;
+            it.var = s->d_var; it.var_ptr = s->d_var_ptr; it.var_layers = s->d_var_layers; it.lpos = s->d_lpos;
+            it.alpha_ent = s->d_alpha_ent; it.omega_lay = s->d_omega_lay;
+            it.ww = s->pack_width;
+            it.L = (uint32_t)s->n_layers; it.N = (uint32_t)s->n_slots; it.V = (uint32_t)s->n_vars;
+            it.ls = up4(s->n_layers); it.ss = up4(s->n_slots); it.vs = up4(s->n_vars);
+            it.src = (uint32_t)ln_src[ord[j]];
+            it.member = ord[j];
+            if (groups_.empty() || key(ord[j]) != key(ord[groups_.back().first]))
+                groups_.push_back(GsGroup{S::gs_batch_fn(s->small_nw, s->small_ln_rl), 64u * (uint32_t)s->small_nw, 0u, j, 0u});
+            GsGroup& g = groups_.back();
+            // the forward's LDS, or a wave's arrays of the reverse sweeps per pack, or the 256 doubles of the scalar omega's sum
+            const uint32_t rev = (uint32_t)(s->nb_.n_packs * gi_lds_bytes(sizeof(REAL), s->pack_width));
+            g.lds = std::max({g.lds, s->small_ln_lds, rev, 2048u});
+            ++g.count;
+        }
+        for (const GsGroup& g : groups_) {
+            if (g.lds > m[0]->lds_cu) { err = "batch grad_learned_iterations: the reverse sweeps do not fit the LDS"; return BDDMMA_ERR_UNSUPPORTED; }
+            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(g.fn), g.lds)) return rc;
+        }
+        gs_total = ln_total;
+        HIPCHK(hipMalloc((void**)&d_gs_items, n * sizeof(GradSmallItem<REAL>)));
+        HIPCHK(hipMalloc((void**)&d_gs_io, (10 * gs_total + n) * sizeof(REAL)));
+        HIPCHK(hipMalloc((void**)&d_gs_bad, 5 * sizeof(uint32_t)));
+        gs_groups = std::move(groups_);
+        return BDDMMA_OK;
+    }
+    // the workspace for n_rec tracked iterations and the items that point into it
+    int gs_workspace(uint64_t n_rec)
+    {
+        if (d_gs_ws && n_rec <= gs_n_rec) return BDDMMA_OK;
+        uint64_t total = 0;
+        gs_slab_off.assign(gs_items.size(), 0);
+        for (size_t j = 0; j < gs_items.size(); ++j) {
+            gs_slab_off[j] = total;
+            total += gs_slab_values(gs_items[j].ls, gs_items[j].ss, gs_items[j].vs, n_rec);
+        }
+        REAL* ws = nullptr;
+        if (hipMalloc((void**)&ws, total * sizeof(REAL)) != hipSuccess) {
+            (void)hipGetLastError();
+            err = "batch grad_learned_iterations: no memory for the records of " + std::to_string(n_rec) + " tracked iterations";
+            return BDDMMA_ERR_DEVICE;
+        }
+        HIPCHK(hipStreamSynchronize(stream));   // nothing in flight reads the old workspace or items
+        if (d_gs_ws) (void)hipFree(d_gs_ws);
+        d_gs_ws = ws;
+        gs_n_rec = n_rec;
+        for (size_t j = 0; j < gs_items.size(); ++j) gs_items[j].ws = d_gs_ws + gs_slab_off[j];
+        HIPCHK(hipMemcpy(d_gs_items, gs_items.data(), gs_items.size() * sizeof(GradSmallItem<REAL>), hipMemcpyHostToDevice));
+        return BDDMMA_OK;
+    }
+    int grad_learned_iterations(const void* w, const void* omega_vec, double omega, void* grad_lo, void* grad_hi, void* grad_mm, void* grad_w_out,
+                                void* grad_omega_out, uint64_t after, uint64_t n_track, uint64_t num_caches, int on_dev) override
+    {
+        (void)num_caches;   // every tracked iteration is recorded: nothing is replayed, and the result does not depend on it
+        int rc;
+        const char* const me = "batch grad_learned_iterations";
+        const uint32_t n = (uint32_t)m.size();
+        if (!w || !grad_lo || !grad_hi || !grad_mm || !grad_w_out || !grad_omega_out) { err = std::string(me) + ": null pointer"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if ((rc = check_state())) return rc;
+        for (uint32_t i = 0; i < n; ++i)
+            if (!m[i]->small_ln_ok) {
+                err = "batch member " + std::to_string(i) + ": learned iterations do not fit one workgroup's LDS (bddmma_fused_small_learned is 0)";
+                return BDDMMA_ERR_UNSUPPORTED;
+            }
+        const bool ov = omega_vec != nullptr;
+        if (!ov && !(omega >= 0.0 && omega < std::numeric_limits<double>::infinity())) { err = std::string(me) + ": omega is negative or not finite"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if (n_track > 0xFFFFFFFFull) { err = std::string(me) + ": too many tracked iterations"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        HIPCHK(hipSetDevice(device));
+        if (!gs_ready) {
+            if ((rc = gs_prepare())) return rc;
+            gs_ready = true;
+        }
+        if ((rc = gs_workspace(n_track))) return rc;
+        const uint64_t n_omega = ov ? gs_total : n;
+        // The batch stream behind everything queued on the members; then one kernel checks every array, moves the arguments into place and
+        // saves every member's entry state.  No member's state is written before the check has been read.
+        for (uint32_t i = 0; i < n; ++i) {
+            HIPCHK(hipEventRecord(ev_in[i], m[i]->stream));
+            HIPCHK(hipStreamWaitEvent(stream, ev_in[i], 0));
+        }
+        GradSmallIO<REAL> io{};
+        if (on_dev) {
+            io.w = (const REAL*)w; io.ov = (const REAL*)omega_vec;
+            io.in_lo = (const REAL*)grad_lo; io.in_hi = (const REAL*)grad_hi; io.in_mm = (const REAL*)grad_mm;
+            io.lo = (REAL*)grad_lo; io.hi = (REAL*)grad_hi; io.mm = (REAL*)grad_mm; io.gw = (REAL*)grad_w_out; io.gom = (REAL*)grad_omega_out;
+        } else {
+            const void* src[5] = {w, omega_vec, grad_lo, grad_hi, grad_mm};
+            REAL* dst[5];
+            for (int k = 0; k < 5; ++k) {
+                dst[k] = d_gs_io + (uint64_t)k * gs_total;
+                if (src[k]) HIPCHK(hipMemcpyAsync(dst[k], src[k], gs_total * sizeof(REAL), hipMemcpyHostToDevice, stream));
+            }
+            io.w = dst[0]; io.ov = ov ? dst[1] : nullptr; io.in_lo = dst[2]; io.in_hi = dst[3]; io.in_mm = dst[4];
+            REAL* const o = d_gs_io + 5 * gs_total;
+            io.lo = o; io.hi = o + gs_total; io.mm = o + 2 * gs_total; io.gw = o + 3 * gs_total; io.gom = o + 4 * gs_total;
+        }
+        HIPCHK(hipMemsetAsync(d_gs_bad, 0xFF, 5 * sizeof(uint32_t), stream));
+        hipLaunchKernelGGL(S::gs_load_fn(), dim3(n), dim3(256), 0, stream, (const GradSmallItem<REAL>*)d_gs_items, io, d_gs_bad);
+        HIPCHK(hipGetLastError());
+        uint32_t bad[5];
+        HIPCHK(hipMemcpyAsync(bad, d_gs_bad, sizeof(bad), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        {
+            // the per-member call's order: the first member with an offending value, and of its arrays the first the call would have checked
+            static const char* const what[5] = {"omega_vec", "dist_weights", "grad_lo", "grad_hi", "grad_mm"};
+            const uint32_t first = *std::min_element(bad, bad + 5);
+            if (first != 0xFFFFFFFFu) {
+                int k = 0;
+                while (bad[k] != first) ++k;
+                err = "batch member " + std::to_string(first) + ": some of its " + what[k] + (k < 2 ? " are negative or not finite" : " are not finite");
+                (void)join_out();
+                return BDDMMA_ERR_INVALID_ARGUMENT;
+            }
+        }
+        const hipMemcpyKind out_kind = on_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (n_track == 0) {   // the in-out arrays stay as they are, both outputs are zero
+            if (on_dev) {
+                HIPCHK(hipMemsetAsync(grad_w_out, 0, gs_total * sizeof(REAL), stream));
+                HIPCHK(hipMemsetAsync(grad_omega_out, 0, n_omega * sizeof(REAL), stream));
+            } else {
+                std::memset(grad_w_out, 0, gs_total * sizeof(REAL));
+                std::memset(grad_omega_out, 0, n_omega * sizeof(REAL));
+            }
+            return join_out();
+        }
+        // ---- the members are touched from here on
+        std::vector<char> dvar_valid(n);
+        for (uint32_t i = 0; i < n; ++i) dvar_valid[i] = m[i]->delta_var_valid;
+        if ((rc = join_in())) { (void)join_out(); return rc; }
+        const REAL omega_r = (REAL)omega;
+        uint64_t left = after;
+        while (left && !rc) {   // the untracked iterations: the fused learned launches
+            const uint32_t chunk = (uint32_t)std::min<uint64_t>(left, 1u << 14);
+            rc = launch_learned(omega_r, chunk, ov);
+            left -= chunk;
+        }
+        if (!rc)
+            for (const GsGroup& g : gs_groups) {
+                hipLaunchKernelGGL(g.fn, dim3(g.count), dim3(g.threads), g.lds, stream, (const GradSmallItem<REAL>*)(d_gs_items + g.first), omega_r, (uint32_t)n_track,
+                                   ov ? 1u : 0u, io);
+                if (hipGetLastError() != hipSuccess) { err = std::string(me) + ": launch failed"; rc = BDDMMA_ERR_DEVICE; break; }
+            }
+        // the state contract of the per-member call: the entry values are back (the kernel's last phase), both sweep states are invalid
+        for (uint32_t i = 0; i < n; ++i) {
+            m[i]->small_launched();
+            m[i]->costs_changed();
+            m[i]->delta_var_valid = dvar_valid[i];
+        }
+        if (!rc && !on_dev) {
+            const REAL* const o = d_gs_io + 5 * gs_total;
+            void* dst[5] = {grad_lo, grad_hi, grad_mm, grad_w_out, grad_omega_out};
+            for (int k = 0; k < 5 && !rc; ++k)
+                if (hipMemcpyAsync(dst[k], o + (uint64_t)k * gs_total, (k == 4 ? n_omega : gs_total) * sizeof(REAL), out_kind, stream) != hipSuccess) rc = BDDMMA_ERR_DEVICE;
+            if (!rc && hipStreamSynchronize(stream) != hipSuccess) rc = BDDMMA_ERR_DEVICE;
+            if (rc) err = std::string(me) + ": copying the results failed";
+        }
+        const int rc2 = join_out();
+        return rc ? rc : rc2;
     }
 
     int lower_bounds(double* out) override

@@ -74,6 +74,8 @@ struct PullSweep {
 #ifndef BDDMMA_EX_ACC
 #define BDDMMA_EX_ACC double
 #endif
+template <typename REAL> struct GradSmallItem;   // kernels/gradsmall.hpp
+template <typename REAL> struct GradSmallIO;
 template <typename REAL>
 struct SolverT final : SolverBase {
     // device buffers
@@ -908,6 +910,12 @@ struct SolverT final : SolverBase {
     Kern<SmallLnFn> small_ln_kern;
     int sl_prepare();
     static SmallLnBatchFn sl_batch_fn(int nw, bool rl);
+    // The backward of the learned iterations for a batch (kernels/gradsmall.hpp; BatchT::grad_learned_iterations): the kernels live in
+    // solver_gs_f32.hip / _f64.hip, a translation unit of their own as the ones above.
+    using GradSmallFn = void (*)(const GradSmallItem<REAL>*, REAL, uint32_t, uint32_t, GradSmallIO<REAL>);
+    using GradSmallLoadFn = void (*)(const GradSmallItem<REAL>*, GradSmallIO<REAL>, uint32_t*);
+    static GradSmallFn gs_batch_fn(int nw, bool rl);
+    static GradSmallLoadFn gs_load_fn();
     bool ov_ready = false;
     // One sweep: the wide and the narrow packs (one launch where `mixed`; forward only with mixed_fwd), then the huge ones.
     int launch_sweep(bool bwd, const Sweep& s, const REAL* delta_lay, REAL omega, int kclass, bool ov = false)

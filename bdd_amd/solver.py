@@ -646,6 +646,38 @@ class bdd_hip_batch:
                                        "both on the device")
         self._check(self._L.bddmma_learned_iterations_batch(self._h, w, ov, float(omega), int(num_itr), w_dev), self._h)
 
+    def grad_iterations(self, dist_weights, grad_lo, grad_hi, grad_mm, omega=0.5, track_grad_after_itr=0, track_grad_for_num_itr=1, num_caches=1,
+                        omega_vec=None, out=None):
+        """grad_iterations(...) of every member i with its part of every array, one workgroup per member in one launch instead of a loop of
+        per-solver calls.  Every layer array is the members' REAL[nr_layers] one behind the other in the members' order; both iteration
+        counts are the same for all members.  Returns (grad_lo, grad_hi, grad_mm, grad_dist_weights, grad_omega); grad_omega has one entry per
+        member (member i's own sum), the concatenated per-layer array with omega_vec.  NumPy inputs give new NumPy arrays; with device
+        tensors grad_lo / grad_hi / grad_mm are updated in place and `out` = (grad_dist_weights, grad_omega) device buffers, as in the
+        per-solver method.  Every member must be fused_small_learned().  State contract and error codes: include/bdd_mma.h,
+        bddmma_grad_learned_iterations_batch."""
+        s0 = self.solvers[0]
+        n = sum(s.nr_layers() for s in self.solvers)
+        n_om = n if omega_vec is not None else len(self.solvers)
+        dev = _is_dev(grad_lo)
+        w, w_dev = s0._learned_buf(dist_weights, n, "dist_weights")
+        ov, ov_dev = s0._learned_buf(omega_vec, n, "omega_vec") if omega_vec is not None else (None, w_dev)
+        if w_dev != int(dev) or ov_dev != int(dev):
+            raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: the arrays of a batch call must all be on the host or all "
+                                   "on the device")
+        tail = (int(track_grad_after_itr), int(track_grad_for_num_itr), int(num_caches))
+        call = self._L.bddmma_grad_learned_iterations_batch
+        if dev:
+            assert out is not None and len(out) == 2, "device gradients need device output buffers: out=(grad_dist_weights, grad_omega)"
+            ptrs = [_dev_ptr(x, k, s0.value_type) for x, k in zip((grad_lo, grad_hi, grad_mm, out[0], out[1]), (n, n, n, n, n_om))]
+            self._check(call(self._h, w, ov, float(omega), *ptrs, *tail, 1), self._h)
+            return grad_lo, grad_hi, grad_mm, out[0], out[1]
+        g = [np.array(x, dtype=s0.value_type, order="C") for x in (grad_lo, grad_hi, grad_mm)]
+        for x in g:
+            assert x.size == n, f"expected {n} values, got {x.size}"
+        res = [np.zeros(n, s0.value_type), np.zeros(n_om, s0.value_type)]
+        self._check(call(self._h, w, ov, float(omega), *(_ptr(x) for x in g + res), *tail, 0), self._h)
+        return g[0], g[1], g[2], res[0], res[1]
+
     def time_iterations(self, n, omega=0.5) -> float:
         """iterations(n) between hipEvents on the batch's stream (first launch to last): elapsed device milliseconds"""
         ms = C.c_double()

@@ -478,6 +478,34 @@ int bddmma_batch_iterations(bddmma_batch* b, double omega, uint64_t n);
  * (Named after bddmma_learned_iterations, which it is for every member; the bddmma_batch_ prefix is kept for the batch object's own calls.) */
 int bddmma_learned_iterations_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec /* or NULL */, double omega,
                                     uint64_t num_itr, int on_device);
+/* bddmma_grad_learned_iterations(member i, its part of every array, ..) for every member i, with the same two iteration counts for all
+ * members: ONE workgroup per member runs the whole call in one launch per kernel instantiation present — the tracked iterations once,
+ * recording what their reverse reads, then the reverse (kernels/gradsmall.hpp) — where the per-member call issues about 25 launches and
+ * copies per tracked iteration and synchronises the host once per member.
+ * Arrays: every layer array is the members' REAL[nr_layers] in the public layer order, one behind the other in the members' order at
+ * bddmma_batch_create.  grad_lo / grad_hi / grad_mm are in-out, grad_dist_weights_out is written.  grad_omega_out is
+ * REAL[bddmma_batch_size] with a scalar omega — member i's own sum in entry i — and the concatenated per-layer array with omega_vec.
+ * on_device is one flag for all arrays, as in bddmma_learned_iterations_batch.
+ * Results: in float every result is bit-equal to the per-member call.  In double they are bit-equal wherever no variable sits in more than
+ * two BDDs, and elsewhere within the summation order of the tracked iterations' exchange — the statement made above for the fused forward
+ * iterations, whose kernel runs them here.
+ * State contract: that of the per-member call.  On return every member's arc costs, deferred differences and delta are the entry values
+ * bit for bit, and both sweep states are invalid.
+ * Refusals, each decided before any member's state is touched, bddmma_batch_last_error naming the member and, for a bad value, the array:
+ * BDDMMA_ERR_STATE as for every batch call; BDDMMA_ERR_UNSUPPORTED for a member whose bddmma_fused_small_learned is 0;
+ * BDDMMA_ERR_INVALID_ARGUMENT for a null pointer (omega_vec excepted), a non-finite incoming gradient, or a negative or non-finite weight
+ * or omega.  One launch checks all arrays; the member named is the first with an offending value, the array the first of its arrays in the
+ * per-member call's order of checks (omega_vec, dist_weights, grad_lo, grad_hi, grad_mm).
+ * track_grad_for_num_itr == 0: the in-out arrays stay unchanged, both outputs are zero-filled.
+ * num_caches is accepted and does not change the result, as in the per-member contract; this form does not replay at all: it records every
+ * tracked iteration's inputs once, 6 nr_layers + 2 slots values per member and tracked iteration, in a workspace the batch owns.  The
+ * workspace is allocated before any member is touched (a failure leaves every member untouched), grows only when a call tracks more
+ * iterations than any call before it, and is freed by bddmma_batch_destroy.
+ * Ordering: that of the other batch calls; the host waits only for the one read of the argument check (and, with host arrays, for the
+ * results). */
+int bddmma_grad_learned_iterations_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec /* or NULL */, double omega,
+                                         void* grad_lo, void* grad_hi, void* grad_mm, void* grad_dist_weights_out, void* grad_omega_out,
+                                         uint64_t track_grad_after_itr, uint64_t track_grad_for_num_itr, uint64_t num_caches, int on_device);
 /* bddmma_run_solver(member, NULL, max_iter, tolerance, improvement_slope, time_limit, 0, &res[i]) for every member i: each member's tests
  * run inside its workgroup against its own control block and each stops on its own criterion; the host relaunches chunks of iterations
  * until every member has stopped or reached max_iter.  res (bddmma_batch_size entries, may be NULL): member i's iterations, bounds and
