@@ -25,7 +25,9 @@ Conventions of every function
               that no caller has to synchronise: inputs written by kernels still queued on the current stream are read after them,
               outputs are read after they are written, and memory of an input that torch's caching allocator reuses later is not
               overwritten while a handle still reads it.  Use the same current stream for a Function's forward and for what consumes
-              its outputs, as with any torch operator.
+              its outputs, as with any torch operator.  DualIterations' two batched paths make batch calls only, which run on the
+              batch's own stream and order themselves against every member's: there the one pair is the batch's (bdd_hip_batch.stream_wait
+              / stream_signal) instead of a pair per member.
 Every backward is once_differentiable, takes a missing incoming gradient (None) as zeros and runs on the stream that is current
 when autograd calls it.
 """
@@ -206,17 +208,17 @@ class DualIterations(torch.autograd.Function):
     (lo, hi, def_mm, sol_avg, lb_first_diff_avg, lb_second_diff_avg).
 
     forward   learned_iterations on every solver, from the given costs and deferred differences — for a bdd_hip_batch whose members are all
-              fused_small_learned(), with improvement_slope <= 0 and no history, ONE batch.learned_iterations between the members'
-              set_solver_costs and get_solver_costs (the same results: bit-equal in float, and in double wherever no variable sits in
-              more than two BDDs).  omega is a tensor: one value (the scalar
+              fused_small_learned(), with improvement_slope <= 0 and no history, three batch calls and none on a member: ONE
+              batch.set_solver_costs, ONE batch.learned_iterations and ONE batch.get_solver_costs (the same results: bit-equal in float,
+              and in double wherever no variable sits in more than two BDDs).  omega is a tensor: one value (the scalar
               call) or one per layer (learned_iterations' omega_vec).  With improvement_slope > 0 the solvers may stop at different
               counts; each count is remembered.  The last three outputs are None unless compute_history_for_itrs > 0 (they start as
               zeros: an entry the history does not reach keeps that) and are not differentiable.
     backward  bddmma_grad_learned_iterations per solver with track_grad_for_num_itr = min(iterations done, grad_dual_itr_max_itr) and
               track_grad_after_itr = done - that: the untracked iterations are treated as constants, as in the reference.  For a
               bdd_hip_batch whose members are all fused_small_learned() and ran the same number of iterations, ONE
-              batch.grad_iterations (bddmma_grad_learned_iterations_batch: one workgroup per member) between the members'
-              set_solver_costs instead of that loop, with the same results (bit-equal in float, and in double wherever no variable
+              batch.set_solver_costs and ONE batch.grad_iterations (bddmma_grad_learned_iterations_batch: one workgroup per member)
+              instead of that loop, with the same results (bit-equal in float, and in double wherever no variable
               sits in more than two BDDs).  Gradients for
               lo, hi, def_mm, dist_weights and omega; one omega shared by several solvers gets the sum of their values, added in list
               order in the solvers' precision (on the torch side in both forms).  State contract of that call: a solver holds the saved input state on entry (set here) and
@@ -245,13 +247,11 @@ class DualIterations(torch.autograd.Function):
         omega_scalar = None if per_layer_omega else float(omega.reshape(-1)[0].item())
         done = []
         if z.batch is not None and not float(improvement_slope) > 0 and history == 0 and all(s.fused_small_learned() for s in z.solvers):
-            with _Ordered(z.solvers):
-                for s, l in zip(z.solvers, z.slices(z.layers)):
-                    s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], def_mm_batch[l])
+            with _Ordered([z.batch]):   # batch calls only: each orders itself against the members' streams
+                z.batch.set_solver_costs(lo_costs_batch, hi_costs_batch, def_mm_batch)
                 z.batch.learned_iterations(dist_weights_batch, int(num_iterations), omega=0.5 if per_layer_omega else omega_scalar,
                                            omega_vec=omega if per_layer_omega else None)
-                for s, l in zip(z.solvers, z.slices(z.layers)):
-                    s.get_solver_costs(out=(lo[l], hi[l], mm[l]))
+                z.batch.get_solver_costs(out=(lo, hi, mm))
             ctx.iterations_done, ctx.omega_scalar = [int(num_iterations)] * len(z.solvers), omega_scalar
             return lo, hi, mm, sol_avg, lb1, lb2
         with _Ordered(z.solvers):
@@ -279,20 +279,21 @@ class DualIterations(torch.autograd.Function):
         g_om = torch.zeros(len(z.solvers), dtype=z.dtype, device=omega.device) if scalar else torch.zeros_like(omega)
         done = ctx.iterations_done
         batched = z.batch is not None and len(set(done)) == 1 and all(s.fused_small_learned() for s in z.solvers)
-        with _Ordered(z.solvers):
-            for i, (s, l) in enumerate(zip(z.solvers, z.slices(z.layers))):
-                s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], def_mm_batch[l])
-                if batched:
-                    continue
-                n = min(done[i], ctx.grad_dual_itr_max_itr)
-                s.grad_iterations(dist_weights_batch[l], g_lo[l], g_hi[l], g_mm[l], omega=ctx.omega_scalar if scalar else 0.5,
-                                  track_grad_after_itr=done[i] - n, track_grad_for_num_itr=n, num_caches=ctx.num_caches,
-                                  omega_vec=None if scalar else omega[l], out=(g_w[l], g_om[i:i + 1] if scalar else g_om[l]))
-            if batched:   # one workgroup per member, every member's arrays at once; g_om[i] is member i's own sum
+        if batched:   # one workgroup per member, every member's arrays at once; g_om[i] is member i's own sum
+            with _Ordered([z.batch]):
+                z.batch.set_solver_costs(lo_costs_batch, hi_costs_batch, def_mm_batch)
                 n = min(done[0], ctx.grad_dual_itr_max_itr)
                 z.batch.grad_iterations(dist_weights_batch, g_lo, g_hi, g_mm, omega=ctx.omega_scalar if scalar else 0.5,
                                         track_grad_after_itr=done[0] - n, track_grad_for_num_itr=n, num_caches=ctx.num_caches,
                                         omega_vec=None if scalar else omega, out=(g_w, g_om))
+        else:
+            with _Ordered(z.solvers):
+                for i, (s, l) in enumerate(zip(z.solvers, z.slices(z.layers))):
+                    s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], def_mm_batch[l])
+                    n = min(done[i], ctx.grad_dual_itr_max_itr)
+                    s.grad_iterations(dist_weights_batch[l], g_lo[l], g_hi[l], g_mm[l], omega=ctx.omega_scalar if scalar else 0.5,
+                                      track_grad_after_itr=done[i] - n, track_grad_for_num_itr=n, num_caches=ctx.num_caches,
+                                      omega_vec=None if scalar else omega[l], out=(g_w[l], g_om[i:i + 1] if scalar else g_om[l]))
         if scalar:
             total = g_om[0]
             for i in range(1, len(z.solvers)):

@@ -495,6 +495,33 @@ class bdd_hip_batch {
                                                    dev_grad_dist_weights_out, dev_grad_omega, (uint64_t)track_grad_after_itr,
                                                    (uint64_t)track_grad_for_num_itr, (uint64_t)num_caches, 1));
     }
+    // set_solver_costs followed by backward_run / get_solver_costs of every member in one launch each, with the members' REAL[nr_layers]
+    // one behind the other in the members' order.  Device pointers as in bdd_hip_parallel_mma (any of them may be null: that part is
+    // skipped; the host does not wait), or host vectors (empty: skipped).  Contract: bddmma_set_solver_costs_batch / bddmma_get_solver_costs_batch.
+    void set_solver_costs(const REAL* dev_lo, const REAL* dev_hi, const REAL* dev_deferred_mm_diff)
+    {
+        check(bddmma_set_solver_costs_batch(b_, dev_lo, dev_hi, dev_deferred_mm_diff, 1));
+    }
+    using SOLVER_COSTS_VECS = std::tuple<std::vector<REAL>, std::vector<REAL>, std::vector<REAL>>;
+    void set_solver_costs(const SOLVER_COSTS_VECS& c)
+    {
+        auto p = [](const std::vector<REAL>& v) { return v.empty() ? nullptr : v.data(); };
+        check(bddmma_set_solver_costs_batch(b_, p(std::get<0>(c)), p(std::get<1>(c)), p(std::get<2>(c)), 0));
+    }
+    void get_solver_costs(REAL* dev_lo, REAL* dev_hi, REAL* dev_deferred_mm_diff) const
+    {
+        check(bddmma_get_solver_costs_batch(b_, dev_lo, dev_hi, dev_deferred_mm_diff, 1));
+    }
+    SOLVER_COSTS_VECS get_solver_costs(const size_t total_layers) const
+    {
+        SOLVER_COSTS_VECS c{std::vector<REAL>(total_layers), std::vector<REAL>(total_layers), std::vector<REAL>(total_layers)};
+        check(bddmma_get_solver_costs_batch(b_, std::get<0>(c).data(), std::get<1>(c).data(), std::get<2>(c).data(), 0));
+        return c;
+    }
+    // stream_wait — the batch's later calls start after everything queued on `hip_stream` so far; stream_signal — the reverse
+    // (bddmma_stream_wait_batch / bddmma_stream_signal_batch)
+    void stream_wait(void* hip_stream) { check(bddmma_stream_wait_batch(b_, hip_stream)); }
+    void stream_signal(void* hip_stream) { check(bddmma_stream_signal_batch(b_, hip_stream)); }
     std::vector<bddmma_run_result> run_solver(const size_t max_iter = 1000, const double tolerance = 1e-6, const double improvement_slope = 1e-9,
                                               const double time_limit = 3600.0)
     {

@@ -455,6 +455,16 @@ int bddmma_grad_learned_iterations_batch(bddmma_batch* b, const void* dist_weigh
                                           track_grad_for_num_itr, num_caches, on_device);
     });
 }
+int bddmma_set_solver_costs_batch(bddmma_batch* b, const void* lo, const void* hi, const void* mm, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) { return i->set_solver_costs(lo, hi, mm, on_device); });
+}
+int bddmma_get_solver_costs_batch(bddmma_batch* b, void* lo, void* hi, void* mm, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) { return i->get_solver_costs(lo, hi, mm, on_device); });
+}
+int bddmma_stream_wait_batch(bddmma_batch* b, void* hip_stream) { return guarded_batch(b, [&](BatchBase* i) { return i->stream_wait((hipStream_t)hip_stream); }); }
+int bddmma_stream_signal_batch(bddmma_batch* b, void* hip_stream) { return guarded_batch(b, [&](BatchBase* i) { return i->stream_signal((hipStream_t)hip_stream); }); }
 int bddmma_batch_time_iterations(bddmma_batch* b, double omega, uint64_t n, double* ms)
 {
     return guarded_batch(b, [&](BatchBase* i) {

@@ -180,6 +180,13 @@ struct BatchBase {
     virtual int grad_learned_iterations(const void* dist_weights, const void* omega_vec, double omega, void* grad_lo, void* grad_hi, void* grad_mm,
                                         void* grad_dist_weights_out, void* grad_omega_out, uint64_t track_grad_after_itr, uint64_t track_grad_for_num_itr,
                                         uint64_t num_caches, int on_device) = 0;
+    // SolverBase::set_solver_costs followed by backward_run of every member / SolverBase::get_solver_costs of every member, one launch per
+    // kernel instantiation present; the arrays as in learned_iterations, each may be null (include/bdd_mma.h: bddmma_set_solver_costs_batch)
+    virtual int set_solver_costs(const void* lo, const void* hi, const void* mm, int on_device) = 0;
+    virtual int get_solver_costs(void* lo, void* hi, void* mm, int on_device) = 0;
+    // the batch stream behind everything queued on `other` so far / the reverse, by an event the batch owns; the host does not wait
+    virtual int stream_wait(hipStream_t other) = 0;
+    virtual int stream_signal(hipStream_t other) = 0;
 };
 // Refuses (before any device call): BDDMMA_ERR_INVALID_ARGUMENT for n == 0, a null member or a member listed twice; BDDMMA_ERR_UNSUPPORTED for
 // a member that is not fused_small or differs from member 0 in precision or device; BDDMMA_ERR_STATE for profiling / an L-BFGS wrapper.

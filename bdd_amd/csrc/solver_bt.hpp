@@ -7,6 +7,7 @@
 
 #include "solver_impl.hpp"
 #include "kernels/gradsmall.hpp"
+#include "kernels/batchcosts.hpp"
 
 namespace bddmma {
 
@@ -38,10 +39,10 @@ struct BatchT final : BatchBase {
         if (device >= 0) (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         for (hipEvent_t e : ev_in) (void)hipEventDestroy(e);
-        for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1})
+        for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1, ev_order})
             if (e) (void)hipEventDestroy(e);
         if (d_items) (void)hipFree(d_items);
-        for (void* q : {(void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad})
+        for (void* q : {(void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage})
             if (q) (void)hipFree(q);
         if (d_ctl) (void)hipFree(d_ctl);
         if (h_ctl) (void)hipHostFree(h_ctl);
@@ -562,6 +563,154 @@ struct BatchT final : BatchBase {
         }
         const int rc2 = join_out();
         return rc ? rc : rc2;
+    }
+
+    // ---- the members' solver costs, all at once (kernels/batchcosts.hpp: k_small_set_batch, k_small_get_batch; the kernels compile in
+    // solver_bc_f32.hip / _f64.hip).  The set kernel is grouped by the members' wave count, as the iteration kernels are; bc_items[j].src is
+    // the first value of that member in the concatenated arrays, which are in the caller's order.  Host arrays pass through one staging
+    // buffer the batch owns (lo | hi | mm, bc_total values each), allocated before any member is touched and freed with the batch.
+    struct BcGroup {
+        CostsSetFn<REAL> fn;
+        uint32_t threads, lds, first, count;
+    };
+    std::vector<BcGroup> bc_groups;
+    CostsItem<REAL>* d_bc_items = nullptr;
+    REAL* d_bc_stage = nullptr;
+    uint64_t bc_total = 0, bc_stage_cap = 0;   // values of all members' layers; values the staging buffer holds
+    bool bc_ready = false;
+    hipEvent_t ev_order = nullptr;             // stream_wait / stream_signal: timing disabled, created on first use
+
+    int bc_prepare(bool host_arrays)
+    {
+        const uint32_t n = (uint32_t)m.size();
+        if (!bc_ready) {
+            std::vector<uint32_t> ord(n);
+            for (uint32_t i = 0; i < n; ++i) ord[i] = i;
+            std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return m[a]->small_nw < m[b]->small_nw; });
+            std::vector<uint64_t> src(n);
+            uint64_t total = 0;
+            for (uint32_t i = 0; i < n; ++i) {
+                src[i] = total;
+                total += m[i]->n_layers;
+            }
+            if (total > 0xFFFFFFFFull) { err = "batch solver costs: too many layers"; return BDDMMA_ERR_UNSUPPORTED; }
+            std::vector<CostsItem<REAL>> items(n);
+            std::vector<BcGroup> groups_;
+            for (uint32_t j = 0; j < n; ++j) {
+                const S* s = m[ord[j]];
+                const SmallDev& sm = s->small;
+                items[j] = CostsItem<REAL>{sm.pack_hdr, sm.rec, sm.rec_off, s->d_lpos, s->d_T, s->d_lohi, s->d_mm_binned, s->d_lb_partial,
+                                           sm.rec_words, sm.ns, sm.nl, sm.n_packs, 0u, (uint32_t)s->n_layers, (uint32_t)src[ord[j]]};
+                if (groups_.empty() || s->small_nw != m[ord[groups_.back().first]]->small_nw)
+                    groups_.push_back(BcGroup{costs_set_fn<REAL>(s->small_nw), 64u * (uint32_t)s->small_nw, 0u, j, 0u});
+                BcGroup& g = groups_.back();
+                g.lds = std::max(g.lds, sm.n_packs * costs_region_bytes((uint32_t)sizeof(REAL), sm.ns, sm.nl));
+                ++g.count;
+            }
+            for (const BcGroup& g : groups_) {
+                if (g.lds > m[0]->lds_cu) { err = "batch set_solver_costs: the costs-to-terminal do not fit the LDS"; return BDDMMA_ERR_UNSUPPORTED; }
+                if (int rc = raise_lds_limit(reinterpret_cast<const void*>(g.fn), g.lds)) return rc;
+            }
+            if (!d_bc_items) HIPCHK(hipMalloc((void**)&d_bc_items, n * sizeof(CostsItem<REAL>)));
+            HIPCHK(hipMemcpy(d_bc_items, items.data(), n * sizeof(CostsItem<REAL>), hipMemcpyHostToDevice));
+            bc_groups = std::move(groups_);
+            bc_total = total;
+            bc_ready = true;
+        }
+        if (host_arrays && bc_stage_cap < 3 * bc_total) {
+            REAL* st = nullptr;
+            HIPCHK(hipMalloc((void**)&st, std::max<uint64_t>(3 * bc_total, 1) * sizeof(REAL)));
+            if (d_bc_stage) {
+                (void)hipStreamSynchronize(stream);   // nothing in flight reads the old buffer
+                (void)hipFree(d_bc_stage);
+            }
+            d_bc_stage = st;
+            bc_stage_cap = 3 * bc_total;
+        }
+        return BDDMMA_OK;
+    }
+    // the batch stream behind everything queued on every member's stream (join_in without the members' backward sweeps)
+    int members_in()
+    {
+        for (size_t i = 0; i < m.size(); ++i) {
+            HIPCHK(hipEventRecord(ev_in[i], m[i]->stream));
+            HIPCHK(hipStreamWaitEvent(stream, ev_in[i], 0));
+        }
+        return BDDMMA_OK;
+    }
+    int set_solver_costs(const void* lo, const void* hi, const void* mm, int on_dev) override
+    {
+        int rc;
+        if ((rc = check_state())) return rc;
+        if (!lo && !hi && !mm) return BDDMMA_OK;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bc_prepare(!on_dev))) return rc;
+        if ((rc = members_in())) return rc;
+        // ---- the members are touched from here on
+        const REAL* a[3] = {(const REAL*)lo, (const REAL*)hi, (const REAL*)mm};
+        hipError_t e = hipSuccess;
+        if (!on_dev)
+            for (int k = 0; k < 3 && e == hipSuccess; ++k)
+                if (a[k]) {
+                    REAL* const st = d_bc_stage + (uint64_t)k * bc_total;
+                    e = hipMemcpyAsync(st, a[k], bc_total * sizeof(REAL), hipMemcpyHostToDevice, stream);
+                    a[k] = st;
+                }
+        for (size_t g = 0; g < bc_groups.size() && e == hipSuccess; ++g) {
+            const BcGroup& G = bc_groups[g];
+            hipLaunchKernelGGL(G.fn, dim3(G.count), dim3(G.threads), G.lds, stream, (const CostsItem<REAL>*)(d_bc_items + G.first), a[0], a[1], a[2]);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && !on_dev) e = hipStreamSynchronize(stream);   // the caller may reuse its arrays on return
+        // the host-side state after set_solver_costs and backward_run: the costs-to-terminal are those of the new costs, the cached bound
+        // is stale; delta_var_valid stays.  Behind a failure nothing is known to be valid.
+        for (S* s : m) {
+            s->costs_changed();
+            s->lb_cached = false;
+            ++s->lb_gen;
+            s->bwd_valid = e == hipSuccess;
+        }
+        const int rc2 = join_out();
+        if (e != hipSuccess) { err = std::string("batch set_solver_costs: ") + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        return rc2;
+    }
+    int get_solver_costs(void* lo, void* hi, void* mm, int on_dev) override
+    {
+        int rc;
+        if ((rc = check_state())) return rc;
+        if (!lo && !hi && !mm) return BDDMMA_OK;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bc_prepare(!on_dev))) return rc;
+        if ((rc = members_in())) return rc;
+        void* const out[3] = {lo, hi, mm};
+        REAL* o[3];
+        for (int k = 0; k < 3; ++k) o[k] = !out[k] ? nullptr : on_dev ? (REAL*)out[k] : d_bc_stage + (uint64_t)k * bc_total;
+        hipLaunchKernelGGL(costs_get_fn<REAL>(), dim3((uint32_t)m.size()), dim3(256), 0, stream, (const CostsItem<REAL>*)d_bc_items, o[0], o[1], o[2]);
+        hipError_t e = hipGetLastError();
+        if (!on_dev) {
+            for (int k = 0; k < 3 && e == hipSuccess; ++k)
+                if (out[k]) e = hipMemcpyAsync(out[k], o[k], bc_total * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        }
+        const int rc2 = join_out();
+        if (e != hipSuccess) { err = std::string("batch get_solver_costs: ") + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        return rc2;
+    }
+    int stream_wait(hipStream_t other) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (!ev_order) HIPCHK(hipEventCreateWithFlags(&ev_order, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(ev_order, other));
+        HIPCHK(hipStreamWaitEvent(stream, ev_order, 0));
+        return BDDMMA_OK;
+    }
+    int stream_signal(hipStream_t other) override
+    {
+        HIPCHK(hipSetDevice(device));
+        if (!ev_order) HIPCHK(hipEventCreateWithFlags(&ev_order, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(ev_order, stream));
+        HIPCHK(hipStreamWaitEvent(other, ev_order, 0));
+        return BDDMMA_OK;
     }
 
     int lower_bounds(double* out) override

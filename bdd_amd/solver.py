@@ -678,6 +678,56 @@ class bdd_hip_batch:
         self._check(call(self._h, w, ov, float(omega), *(_ptr(x) for x in g + res), *tail, 0), self._h)
         return g[0], g[1], g[2], res[0], res[1]
 
+    def _costs_args(self, arrays, what):
+        """three per-layer arrays of a batch call (None: skipped) as pointers and the on_device flag; device tensors or NumPy, all of
+        one kind"""
+        s0 = self.solvers[0]
+        n = sum(s.nr_layers() for s in self.solvers)
+        given = [x for x in arrays if x is not None]
+        dev = bool(given) and _is_dev(given[0])
+        if any(_is_dev(x) != dev for x in given):
+            raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: the arrays of a batch call must all be on the host or all "
+                                   "on the device")
+        if dev:
+            return [None if x is None else _dev_ptr(x, n, s0.value_type) for x in arrays], 1
+        for x in given:
+            assert x.size == n, f"{what}: expected {n} values, got {x.size}"
+        return [_ptr(x) for x in arrays], 0
+
+    def set_solver_costs(self, lo, hi, mm):
+        """set_solver_costs(lo_i, hi_i, mm_i) followed by backward_run() of every member i in one launch: the members' REAL[nr_layers]
+        one behind the other in the members' order.  Device tensors take the device path (the host does not wait), NumPy arrays the
+        host path; None leaves that part of every member's state as it is.  include/bdd_mma.h: bddmma_set_solver_costs_batch."""
+        vt = self.solvers[0].value_type
+        arrays = [x if x is None or _is_dev(x) else np.ascontiguousarray(x, dtype=vt) for x in (lo, hi, mm)]
+        ptrs, dev = self._costs_args(arrays, "set_solver_costs")
+        self._check(self._L.bddmma_set_solver_costs_batch(self._h, *ptrs, dev), self._h)
+
+    def get_solver_costs(self, out=None):
+        """get_solver_costs() of every member in one launch: (lo, hi, mm), the members' values one behind the other.  out: three device
+        buffers, any of them None (skipped) — written in the batch stream's order, the host does not wait; without it three new NumPy
+        arrays.  include/bdd_mma.h: bddmma_get_solver_costs_batch."""
+        if out is not None:
+            out = tuple(out)
+            assert len(out) == 3 and all(x is None or _is_dev(x) for x in out), "out: three device buffers (or None)"
+            ptrs, _ = self._costs_args(list(out), "get_solver_costs")
+            self._check(self._L.bddmma_get_solver_costs_batch(self._h, *ptrs, 1), self._h)
+            return out
+        n = sum(s.nr_layers() for s in self.solvers)
+        lo, hi, mm = (np.zeros(n, self.solvers[0].value_type) for _ in range(3))
+        self._check(self._L.bddmma_get_solver_costs_batch(self._h, _ptr(lo), _ptr(hi), _ptr(mm), 0), self._h)
+        return lo, hi, mm
+
+    # ---- ordering against other streams (include/bdd_mma.h: bddmma_stream_wait_batch / bddmma_stream_signal_batch)
+    def stream_wait(self, hip_stream=0):
+        """what the batch's calls queue from now on starts after everything queued so far on `hip_stream` (a raw hipStream_t as an
+        integer, e.g. torch.cuda.current_stream().cuda_stream; 0 / None: the default stream).  The host does not wait."""
+        self._check(self._L.bddmma_stream_wait_batch(self._h, C.c_void_p(int(hip_stream or 0))), self._h)
+
+    def stream_signal(self, hip_stream=0):
+        """the reverse: what is queued on `hip_stream` from now on starts after everything the batch's calls have queued so far"""
+        self._check(self._L.bddmma_stream_signal_batch(self._h, C.c_void_p(int(hip_stream or 0))), self._h)
+
     def time_iterations(self, n, omega=0.5) -> float:
         """iterations(n) between hipEvents on the batch's stream (first launch to last): elapsed device milliseconds"""
         ms = C.c_double()

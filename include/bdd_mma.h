@@ -506,6 +506,33 @@ int bddmma_learned_iterations_batch(bddmma_batch* b, const void* dist_weights, c
 int bddmma_grad_learned_iterations_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec /* or NULL */, double omega,
                                          void* grad_lo, void* grad_hi, void* grad_mm, void* grad_dist_weights_out, void* grad_omega_out,
                                          uint64_t track_grad_after_itr, uint64_t track_grad_for_num_itr, uint64_t num_caches, int on_device);
+/* bddmma_set_solver_costs(member i, its part of lo / hi / mm, ..) followed by bddmma_backward_run(member i) for every member i: one
+ * workgroup per member scatters the member's values and runs its plain backward sweep out of LDS, one launch per wave count present —
+ * where the per-member call is three copies, three kernels and a host synchronisation, and leaves the costs-to-terminal stale, so that
+ * the next batch call had to launch a backward sweep per member first.
+ * Arrays: the members' REAL[nr_layers] in the public layer order, one behind the other in the members' order at bddmma_batch_create,
+ * all on the host or all on the device (on_device).  Each of the three may be NULL: that part of the members' state is left as it is.
+ * All three NULL: BDDMMA_OK, nothing is done.  No value is checked, as bddmma_set_solver_costs checks none.
+ * State afterwards: that of the two per-member calls — arc costs, deferred differences, costs-to-terminal and the bound's partial sums
+ * bit-equal to theirs, the backward state valid, the forward state invalid; delta and the costs-from-root are untouched.
+ * Ordering: that of the other batch calls.  With device arrays the host does not wait at all; host arrays pass through one staging
+ * buffer the batch owns (allocated before any member is touched, freed by bddmma_batch_destroy) with one host synchronisation.
+ * Refusals: b == NULL is BDDMMA_ERR_INVALID_ARGUMENT; BDDMMA_ERR_STATE as for every batch call, every member left untouched.
+ * (Named after the per-member calls, as bddmma_learned_iterations_batch is; likewise the three entries below.) */
+int bddmma_set_solver_costs_batch(bddmma_batch* b, const void* lo /* or NULL */, const void* hi /* or NULL */, const void* mm /* or NULL */,
+                                  int on_device);
+/* bddmma_get_solver_costs(member i, its part of lo / hi / mm, ..) for every member i in one launch: the same array layout, the same
+ * refusals, NULL outputs are skipped, results bit-equal to the per-member calls.  Device outputs are written in the order of the
+ * batch's stream and the host does not wait (bddmma_stream_signal_batch orders a reader's stream behind them); host outputs pass
+ * through the staging buffer with one host synchronisation.  No member's state changes. */
+int bddmma_get_solver_costs_batch(bddmma_batch* b, void* lo /* or NULL */, void* hi /* or NULL */, void* mm /* or NULL */, int on_device);
+/* bddmma_stream_wait / bddmma_stream_signal for the batch's own stream, on which every batch call runs: whatever a batch call queues
+ * after bddmma_stream_wait_batch starts after everything queued on `hip_stream` so far; whatever is queued on `hip_stream` after
+ * bddmma_stream_signal_batch starts after everything the batch's calls have queued so far.  One event the batch owns (timing disabled,
+ * created on first use); neither waits on the host.  A caller whose work between the two is batch calls only needs this one pair instead
+ * of a pair per member: every batch call orders itself against the members' streams. */
+int bddmma_stream_wait_batch(bddmma_batch* b, void* hip_stream);
+int bddmma_stream_signal_batch(bddmma_batch* b, void* hip_stream);
 /* bddmma_run_solver(member, NULL, max_iter, tolerance, improvement_slope, time_limit, 0, &res[i]) for every member i: each member's tests
  * run inside its workgroup against its own control block and each stops on its own criterion; the host relaunches chunks of iterations
  * until every member has stopped or reached max_iter.  res (bddmma_batch_size entries, may be NULL): member i's iterations, bounds and
