@@ -23,7 +23,10 @@ struct SolverBase {
     uint32_t pack_width = 0, wide_pack_width = 0, wide_slot_base = 0;
     uint64_t dev_bytes = 0;          // bytes of the arrays the solver holds
     uint64_t dev_alloc_bytes = 0;    // bytes hipMalloc'd for them (arena capacity included: >= dev_bytes)
-    bool fwd_valid = false, bwd_valid = false;  // forward_state_valid_ / backward_state_valid_ (bdd_cuda_base.h:205-206)
+    bool fwd_valid = false, bwd_valid = false;  // forward_state_valid_ / backward_state_valid_ (bdd_cuda_base.h:205-206): d_F / d_T in memory are current
+    // lb_partial belongs to the current costs: set by every backward sweep, cleared by whatever clears bwd_valid.  Differs from bwd_valid after
+    // the on-chip solve sweeps of iteration() (kernels/narrow4.hpp), which leave the bound's partial sums but no costs-to-terminal in memory.
+    bool lb_valid = false;
     uint64_t cost_epoch = 0;                    // counts the calls that changed arc costs other than through a solve sweep (update_costs, set_cost, gradient steps, ...)
     bool deterministic = false;
     std::vector<uint64_t> nodes_per_hop, layers_per_hop;
@@ -79,6 +82,7 @@ struct SolverBase {
     bool fused_small = false;   // whole iterations in one launch (diagnostics: bddmma_fused_small)
     bool fused_small_learned = false;   // ... and whole learned iterations (bddmma_fused_small_learned)
     bool nt_loads = false;      // the solve sweeps' non-temporal instantiation (diagnostics: bddmma_nontemporal_loads)
+    bool pot_on_chip = false;   // iteration()'s solve sweeps rebuild F and T on chip (diagnostics: bddmma_potentials_on_chip)
     // run_solver (include/run_solver_util.h:10-77) around iteration(): termination tests on the device, see solver_impl.hpp
     virtual int run_plain(uint64_t max_iter, double tolerance, double slope, double time_limit, int verbose, bddmma_run_result* res) = 0;
     virtual int forward_mm(double omega, void* delta, int on_device) = 0;

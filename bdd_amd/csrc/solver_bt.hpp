@@ -668,7 +668,7 @@ struct BatchT final : BatchBase {
             s->costs_changed();
             s->lb_cached = false;
             ++s->lb_gen;
-            s->bwd_valid = e == hipSuccess;
+            s->bwd_valid = s->lb_valid = e == hipSuccess;
         }
         const int rc2 = join_out();
         if (e != hipSuccess) { err = std::string("batch set_solver_costs: ") + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }

@@ -143,7 +143,7 @@ struct SolverT final : SolverBase {
     // pending bound is no longer "the bound of the current costs" (SolverBase::cost_epoch)
     void costs_changed()
     {
-        fwd_valid = bwd_valid = x_layer_valid = false;
+        fwd_valid = bwd_valid = lb_valid = x_layer_valid = false;
         ++cost_epoch;
     }
     CostQuot* d_cost_q = nullptr;      // update_costs: per-variable quotients (kernels.hpp: k_cost_quotients)
@@ -202,6 +202,9 @@ struct SolverT final : SolverBase {
     SmallLearn<REAL> small_ln_arg{};
     // streaming solve sweeps, third generation: a lane per layer (kernels/narrow3.hpp: k_fwd_narrow3 / k_bwd_narrow3)
     bool use_narrow3 = false;
+    // ... and inside iteration() with the potentials on chip (kernels/narrow4.hpp): 0, or the kernels' hop capacity (10 / 16)
+    int onchip_hc = 0;
+    uint32_t onchip_mode = 0;
     uint32_t *d_lrec = nullptr, *d_lrec_off = nullptr;
     uint32_t lrec_words = 0;
     uint32_t huge_pack_width = 0;
@@ -592,6 +595,23 @@ struct SolverT final : SolverBase {
             n12_nt = false;
 #endif
         nt_loads = n3_nt || n12_nt;
+        // The solve sweeps of iteration() with F and T rebuilt in registers (kernels/narrow4.hpp): third-generation packs that start from the
+        // resident headers and have at most 16 hops, float (the double form spills).  The smallest capacity that holds the longest pack.
+        // variant_flags bit 21: off (the tests' twin); bits 22 / 23: only T / only F on chip, where that pair is built (4 packs, 10 hops).
+        if constexpr (sizeof(REAL) == 4) {
+            if (use_narrow3 && res_hdr_ok && !n3_nt && !(opts && (opts->variant_flags & 0x200000u))) {
+                uint32_t max_hops = 0;
+                for (uint32_t p = 0; p < nb_.n_packs; ++p) max_hops = std::max(max_hops, L.res.pack_hdr[8 * (size_t)p + 5] & 0xFFFFu);
+                onchip_hc = max_hops <= 10 ? 10 : max_hops <= 16 ? 16 : 0;
+                const uint32_t part = opts ? (opts->variant_flags >> 22) & 3u : 0u;
+                if (onchip_hc == 16) onchip_mode = 3;
+                if (part == 1 || part == 2) {
+                    if (onchip_hc == 10 && wpb == 4) onchip_mode = part;
+                    else onchip_hc = 0;
+                }
+                pot_on_chip = onchip_hc != 0;
+            }
+        }
         if (wb_.n_packs) {
             // one workgroup per wide pack, thread t owns the nodes t + i * wide_threads of a hop (kernels.hpp: k_fwd_wide2)
             // two nodes of a hop per thread: half the wavefronts at the hop's two barriers and two independent chains per lane.  Wide-only
@@ -758,6 +778,7 @@ struct SolverT final : SolverBase {
         Kern<WideFn> wide;
         Kern<MixedFn> mixed;  // SOLVE, where init() admitted `mixed`: narrow + wide in one launch
         HugeFn huge = nullptr;
+        bool reads_pot = true, stores_pot = true;  // SOLVE: the sweep reads T (forward) / F (backward) from memory, and stores F / T there
         const void* narrow_fn() const { return res2 ? (const void*)res2 : res ? (const void*)res : rec ? (const void*)rec : (const void*)narrow; }
     };
     struct Kernels {
@@ -769,6 +790,7 @@ struct SolverT final : SolverBase {
         Kern<SmallFn> small;           // small_ok: whole iterations in one launch
         Kern<TransFn> transpose[2];    // staged projection: [TO_LAYERS]
         Kern<LincombFn> lincomb[2];    // [the five-vector form]
+        Sweep onchip[2];               // onchip_hc: iteration()'s solve sweeps with the potentials on chip, [backward]
     } kern;
     Sweep ov_sweep[2];  // [backward]: the SOLVE sweeps with omega per layer (OV), filled by ov_prepare()
     // OV: the instantiation that takes omega per layer from d_omega_lay (learned iterations with omega_vec), SOLVE only.  The <true> form is
@@ -832,6 +854,20 @@ struct SolverT final : SolverBase {
         }
         return s;
     }
+    // k_fwd_narrow4 / k_bwd_narrow4 (float): the pair that keeps both potentials on chip for 4 / 8 packs per workgroup of <= 10 hops; the
+    // backward kernel that rebuilds F and stores T for packs of <= 16 hops (the forward form does not fit its registers there: the third
+    // generation's forward sweep stays); the pairs that keep one potential (variant_flags bits 22, 23: the decomposition of NOTES round 10)
+    // for the headline's 4 packs and 10 hops
+    RecFn onchip_fn(bool bwd, bool rebuild, bool store) const
+    {
+        if (onchip_hc == 16) return pick<4, 8>(wpb, [&](auto W) -> RecFn { return &k_bwd_narrow4<REAL, W.value, 16, true, true>; });
+        if (rebuild && !store)
+            return pick<4, 8>(wpb, [&](auto W) -> RecFn {
+                return bwd ? &k_bwd_narrow4<REAL, W.value, 10, true, false> : &k_fwd_narrow4<REAL, W.value, 10, true, false>;
+            });
+        if (rebuild) return bwd ? &k_bwd_narrow4<REAL, 4, 10, true, true> : &k_fwd_narrow4<REAL, 4, 10, true, true>;
+        return bwd ? &k_bwd_narrow4<REAL, 4, 10, false, false> : &k_fwd_narrow4<REAL, 4, 10, false, false>;
+    }
     // everything but the OV sweeps; called once, at the end of init()
     void resolve_kernels()
     {
@@ -839,6 +875,21 @@ struct SolverT final : SolverBase {
             kern.sweep[bwd][FWD_PLAIN] = resolve_sweep<FWD_PLAIN, false>(bwd);
             kern.sweep[bwd][FWD_SOLVE] = resolve_sweep<FWD_SOLVE, false>(bwd);
             kern.sweep[bwd][FWD_SOLUTION] = resolve_sweep<FWD_SOLUTION, false>(bwd);  // backward: BWD_MARGINALS
+        }
+        if (onchip_hc) {
+            // the third generation's launch (grid, staging area, records) with the kernels of kernels/narrow4.hpp.  onchip_mode: 0 both
+            // potentials on chip, 1 T only (the forward sweep still stores F, the backward one reads it), 2 F only, 3 F only behind the third
+            // generation's own forward sweep (packs of 11-16 hops)
+            for (int bwd = 0; bwd < 2; ++bwd) {
+                Sweep s = kern.sweep[bwd][FWD_SOLVE];
+                if (onchip_mode == 3 && !bwd) { kern.onchip[0] = s; continue; }
+                const bool rebuild = onchip_mode == 0 || (onchip_mode == 1) == !bwd;  // forward rebuilds T, backward F
+                const bool store = onchip_mode != 0 && rebuild;  // the pairs that keep one potential on chip store the other one's partner: <1, 1> with <0, 0>
+                if constexpr (sizeof(REAL) == 4) s.rec = onchip_fn(bwd, rebuild, onchip_mode == 3 || store);
+                s.reads_pot = !rebuild;
+                s.stores_pot = onchip_mode == 3 || store;
+                kern.onchip[bwd] = s;
+            }
         }
         kern.ex_threads = exch_small ? EXS_THREADS : exch_medium ? EXM_THREADS : EX_THREADS;
         pick<EXS_THREADS, EXM_THREADS, EX_THREADS>(kern.ex_threads, [&](auto T_) {
@@ -890,6 +941,9 @@ struct SolverT final : SolverBase {
         int rc = BDDMMA_OK;
         for (const auto& dir : k.sweep)
             for (const Sweep& s : dir)
+                if ((rc = raise_lds_limits(s))) return rc;
+        if (onchip_hc)
+            for (const Sweep& s : k.onchip)
                 if ((rc = raise_lds_limits(s))) return rc;
         for (const auto* e : {&k.ex[0], &k.ex[1], &k.ex_w, &k.ex_raw})
             if ((rc = raise_lds_limit(*e))) return rc;
@@ -1018,12 +1072,14 @@ struct SolverT final : SolverBase {
         HIPCHK(hipSetDevice(device));
         int rc = launch_bwd(BWD_PLAIN, nullptr, REAL(0), BDDMMA_K_OTHER);
         if (rc) return rc;
-        bwd_valid = true;
+        bwd_valid = lb_valid = true;
         return BDDMMA_OK;
     }
+    // the bound's partial sums of the current costs: what the last backward sweep left (lb_valid), else a plain backward sweep
+    int bound_run() { return lb_valid ? BDDMMA_OK : backward_run(); }
     int lower_bound(double* lb) override
     {
-        int rc = backward_run();
+        int rc = bound_run();
         if (rc) return rc;
         if (lb_cached) {
             *lb = lb_cache;
@@ -1065,7 +1121,7 @@ struct SolverT final : SolverBase {
     int lower_bound_enqueue(int slot) override
     {
         if (slot < 0 || slot > 1) { err = "lower_bound_enqueue: slot must be 0 or 1"; return BDDMMA_ERR_INVALID_ARGUMENT; }
-        int rc = backward_run();
+        int rc = bound_run();
         if (rc) return rc;
         lb_slot_gen[slot] = lb_gen;
         if (lb_cached) {
@@ -1089,7 +1145,7 @@ struct SolverT final : SolverBase {
             lb_slot_known[slot] = true;
         }
         *lb = lb_slot_value[slot];
-        if (lb_slot_gen[slot] == lb_gen && bwd_valid) {  // no backward launch since: this is the bound of the current costs
+        if (lb_slot_gen[slot] == lb_gen && lb_valid) {  // no backward launch since: this is the bound of the current costs
             lb_cache = *lb;
             lb_cached = true;
         }
@@ -1113,28 +1169,34 @@ struct SolverT final : SolverBase {
     }
 
     // ov: omega per layer from d_omega_lay (learned iterations with omega_vec; ov_sweep)
-    int mma_forward(REAL omega, const REAL* delta_lay, bool ov = false)
+    // on_chip: the caller allows the sweeps that keep potentials on chip (kernels/narrow4.hpp) — iteration() alone; taken where the rule
+    // of init() holds (onchip_hc) and no L-BFGS wrapper wants x in layer order from the backward sweeps
+    bool onchip_usable(bool ov) const { return onchip_hc != 0 && !ov && d_x_layer == nullptr; }
+    int mma_forward(REAL omega, const REAL* delta_lay, bool ov = false, bool on_chip = false)
     {
         int rc;
-        if (!bwd_valid && (rc = backward_run())) return rc;  // bdd_cuda_parallel_mma.cu:211-212
-        rc = launch_sweep(false, ov ? ov_sweep[0] : kern.sweep[0][FWD_SOLVE], delta_lay, omega, BDDMMA_K_FORWARD_MM, ov);
+        const Sweep& s = ov ? ov_sweep[0] : (on_chip && onchip_usable(ov)) ? kern.onchip[0] : kern.sweep[0][FWD_SOLVE];
+        if (s.reads_pot && !bwd_valid && (rc = backward_run())) return rc;  // bdd_cuda_parallel_mma.cu:211-212 (not for a sweep that rebuilds the costs-to-terminal)
+        rc = launch_sweep(false, s, delta_lay, omega, BDDMMA_K_FORWARD_MM, ov);
         x_layer_valid = false;  // the forward sweep rewrites the deferred values by entry only
         if (rc) return rc;
-        fwd_valid = true;
-        bwd_valid = false;
+        fwd_valid = s.stores_pot;
+        bwd_valid = lb_valid = false;
         return BDDMMA_OK;
     }
-    int mma_backward(REAL omega, const REAL* delta_lay, bool ov = false)
+    int mma_backward(REAL omega, const REAL* delta_lay, bool ov = false, bool on_chip = false)
     {
-        if (!fwd_valid) {
+        const Sweep& s = ov ? ov_sweep[1] : (on_chip && onchip_usable(ov)) ? kern.onchip[1] : kern.sweep[1][BWD_SOLVE];
+        if (s.reads_pot && !fwd_valid) {
             err = "backward_mm requires a valid forward state (call forward_mm first)";  // assert at :304
             return BDDMMA_ERR_STATE;
         }
-        int rc = launch_sweep(true, ov ? ov_sweep[1] : kern.sweep[1][BWD_SOLVE], delta_lay, omega, BDDMMA_K_BACKWARD_MM, ov);
+        int rc = launch_sweep(true, s, delta_lay, omega, BDDMMA_K_BACKWARD_MM, ov);
         if (rc) return rc;
         x_layer_valid = d_x_layer != nullptr;
         fwd_valid = false;
-        bwd_valid = true;
+        bwd_valid = s.stores_pot;
+        lb_valid = true;
         return BDDMMA_OK;
     }
     // ---- instances that fit one workgroup: n iterations inside one launch (kernels/small.hpp).  Not while event pairs are wanted per launch
@@ -1148,7 +1210,7 @@ struct SolverT final : SolverBase {
         ++lb_gen;
         x_layer_valid = false;
         fwd_valid = false;
-        bwd_valid = true;
+        bwd_valid = lb_valid = true;
         delta_var_valid = false;
     }
     int launch_small(REAL omega, uint32_t n, const RunStep& rstep)
@@ -1211,9 +1273,9 @@ struct SolverT final : SolverBase {
         int rc;
         if (small_usable() && !run_stop) return launch_small((REAL)omega, 1, RunStep{});
         prof_active = profiling && (prof_iter++ % prof_stride == 0);
-        if ((rc = mma_forward((REAL)omega, d_delta_lay))) return rc;
+        if ((rc = mma_forward((REAL)omega, d_delta_lay, false, true))) return rc;
         if ((rc = exchange())) return rc;
-        if ((rc = mma_backward((REAL)omega, d_delta_lay))) return rc;
+        if ((rc = mma_backward((REAL)omega, d_delta_lay, false, true))) return rc;
         if ((rc = exchange(true))) return rc;
         return BDDMMA_OK;
     }
@@ -1732,7 +1794,7 @@ struct SolverT final : SolverBase {
         int rc;
         if ((rc = forward_run())) return rc;  // bdd_cuda_base.cu:720
         if ((rc = launch_bwd(BWD_MARGINALS, nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
-        bwd_valid = true;
+        bwd_valid = lb_valid = true;
         return marginals_out(sorted, var, mm0, mm1, on_device);
     }
     // the per-layer pair a marginal sweep left in d_tmp0 / d_tmp1 (min-marginals, sum-marginals) -> the caller, in layer order or gathered
@@ -1865,7 +1927,7 @@ struct SolverT final : SolverBase {
         int rc;
         if ((rc = forward_run())) return rc;
         if ((rc = launch_bwd(BWD_MARGINALS, nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
-        bwd_valid = true;
+        bwd_valid = lb_valid = true;
         REAL* dst = on_device ? (REAL*)out : d_tmp0;  // in place over mm0 when the result goes to the host
         hipLaunchKernelGGL((k_diff<REAL, REAL>), dim3(cdiv(n_layers, 256)), dim3(256), 0, stream, dst, (const REAL*)d_tmp1, (const REAL*)d_tmp0, (uint32_t)n_layers);
         if (!on_device) return copy_out(out, dst, n_layers * sizeof(REAL), 0);
@@ -2070,7 +2132,7 @@ struct SolverT final : SolverBase {
         if ((rc = distribute_delta())) return rc;                 // :265
         if ((rc = forward_run())) return rc;                      // min_marginals_cuda(), :266
         if ((rc = launch_bwd(BWD_MARGINALS, nullptr, REAL(0), BDDMMA_K_OTHER))) return rc;
-        bwd_valid = true;
+        bwd_valid = lb_valid = true;
         HIPCHK(hipMemsetAsync(d_counts, 0, 4 * sizeof(uint32_t), stream));
         REAL* c0 = d_delta_c;               // 2V scratch: [0,V) cost_delta_0, [V,2V) cost_delta_1
         REAL* c1 = d_delta_c + n_vars;

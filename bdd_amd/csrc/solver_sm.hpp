@@ -142,7 +142,7 @@ int SolverT<REAL>::sm_launch_fwd()
 template <typename REAL>
 int SolverT<REAL>::sm_launch_bwd()
 {
-    bwd_valid = false;  // ... and the costs from terminal; the cached bound goes with them (flush_backward_states, bdd_cuda_base.cu:1011)
+    bwd_valid = lb_valid = false;  // ... and the costs from terminal; the cached bound goes with them (flush_backward_states, bdd_cuda_base.cu:1011)
     lb_cached = false;
     ++lb_gen;
     return launch_pull(sm_bwd_sweep());

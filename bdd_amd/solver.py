@@ -99,6 +99,10 @@ class bdd_hip_parallel_mma:
     def nontemporal_loads(self) -> bool:
         """the solve sweeps run in the instantiation that loads potentials and staging tables non-temporally (footprint beyond the caches' reach)"""
         return bool(self._L.bddmma_nontemporal_loads(self._h))
+
+    def potentials_on_chip(self) -> bool:
+        """the solve sweeps of iteration() / iterations() / run_solver rebuild F and T on chip instead of storing and reloading them"""
+        return bool(self._L.bddmma_potentials_on_chip(self._h))
     def device(self) -> int:
         """index of the GPU the solver lives on"""
         return int(self._L.bddmma_device(self._h))

@@ -107,7 +107,12 @@ typedef struct bddmma_options {
                                           launch, k_iterate_small, for <= 16 narrow packs of 64 slots with layers of <= 2 nodes)
                                   bit 20: the streaming solve sweeps' instantiations that load potentials and staging tables non-temporally
                                           whatever the footprint (rule: arrays beyond 640 MiB; first generation, and second in double,
-                                          packs of 128 slots, 4 / 8 per workgroup; the third generation's own: double beyond 640 MiB) */
+                                          packs of 128 slots, 4 / 8 per workgroup; the third generation's own: double beyond 640 MiB)
+                                  bit 21: solve sweeps of iteration() keep F and T in memory (narrow3) (rule: float, third generation, packs that
+                                          start from the resident headers and have <= 16 hops rebuild both potentials on chip inside
+                                          bddmma_iteration / _iterations / _run_solver, k_fwd_narrow4 / k_bwd_narrow4; a test hook: same results)
+                                  bits 22, 23: of those sweeps only the one that rebuilds T (22) / F (23) on chip, the other potential through
+                                          memory (measurement hooks; built for 4 packs per workgroup and <= 10 hops, elsewhere as bit 21) */
     uint32_t pack_fill;        /* slots of a narrow pack's hop that further BDDs are packed into, in [2, pack_width] (default 0 = pack_width).
                                   Smaller values give more, emptier packs (more wavefronts for the same nodes); measured slower on every
                                   instance (NOTES.md section 6: the sweeps are bound by instructions issued, not by latency), kept for experiments */
@@ -179,6 +184,9 @@ int bddmma_fused_small(const bddmma_solver* s);
 int bddmma_fused_small_learned(const bddmma_solver* s);
 /* 1 when the narrow packs' solve sweeps run in the instantiation that loads what a sweep reads once (potentials, staging tables) non-temporally. */
 int bddmma_nontemporal_loads(const bddmma_solver* s);
+/* 1 when the solve sweeps of bddmma_iteration / _iterations / _run_solver rebuild the costs-from-root and costs-to-terminal on chip instead of
+ * storing and reloading them (csrc/kernels/narrow4.hpp; variant_flags bit 21 turns it off).  bddmma_solve_sweep_kind stays STREAMING3. */
+int bddmma_potentials_on_chip(const bddmma_solver* s);
 int bddmma_precision(const bddmma_solver* s);
 int bddmma_device(const bddmma_solver* s);
 /* nr_bdds(var): int32[nr_variables] (get_num_bdds_per_var, bdd_cuda_base.h:166) */
