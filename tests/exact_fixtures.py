@@ -22,7 +22,11 @@ STATE_SEEDS = (1, 2)                             # exact_state seeds of the sing
 # exact_iteration_inputs seeds per family, (scalar omega, omega_vec): the first seed from 1 on for which the restatement alone meets the
 # conditions of tests/test_exact_fixtures.py::test_iterations_fixture (exact in float32, headroom, tie share, mm = 0 share, both signs of mm)
 ITERATION_SEEDS = {"assignment8": (3, 1), "cover10_w64": (2, 2), "cover10_w128": (2, 2), "cover10_w256": (2, 2), "huge": (1, 1), "knapsack_w64": (1, 1),
-                   "mixed": (1, 2), "split_bdds": (1, 1), "staggered_rows": (1, 1), "wide2": (1, 2)}
+                   "mixed": (1, 2), "split_bdds": (1, 1), "staggered_rows": (1, 1), "wide2": (1, 2),
+                   # the chained families: the instance, and so the seeds, of staggered_rows, knapsack_w64 and mixed.  chained_general with omega_vec:
+                   # no seed in 1..32 keeps the headroom (the closest, seed 6, exceeds it 1.5 times, the others 1.9 to 325 times): that form is left out (None)
+                   "chained_rows": (1, 1), "chained_knapsack": (1, 1), "chained_wide": (1, 2), "chained_wide2": (1, 2), "chained_general": (1, None)}
+ITERATION_CASES = [(f, ov) for f in sorted(ITERATION_SEEDS) for ov in (False, True) if ITERATION_SEEDS[f][ov] is not None]
 STATES = tuple(f"seed{s}" for s in STATE_SEEDS) + ("zero_costs",)
 
 

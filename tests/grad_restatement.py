@@ -155,7 +155,7 @@ class Gradients(SumMarginals):
         """(x [N, k], cost [N] with inf for the assignments that do not end in the top sink) of BDD b, as SumMarginals.brute_force"""
         l0, l1 = self.bdd_layer_ptr[b], self.bdd_layer_ptr[b + 1]
         k = l1 - l0
-        assert 0 < k <= 16
+        assert 0 < k <= 19
         N = 1 << k
         x = (np.arange(N)[:, None] >> np.arange(k)[None, :]) & 1
         node = np.full(N, self.layer_node_ptr[l0], np.int64)

@@ -61,7 +61,7 @@ class SumMarginals(LearnedMma):
         quasi-reduced), so that assignments and root -> top paths are the same thing."""
         l0, l1 = self.bdd_layer_ptr[b], self.bdd_layer_ptr[b + 1]
         k = l1 - l0
-        assert 0 < k <= 16
+        assert 0 < k <= 19
         N = 1 << k
         x = (np.arange(N)[:, None] >> np.arange(k)[None, :]) & 1   # assignment i takes arc x[i, j] in layer l0 + j
         node = np.full(N, self.layer_node_ptr[l0], np.int64)
@@ -152,6 +152,24 @@ def wide_rows(seed=21):
         co = rng.integers(1, 40, size=k)
         col.add_linear(co, "<=", int(co.sum() // 2), vs)
     for _ in range(30):
+        col.add_covering(np.sort(rng.choice(V, size=5, replace=False)))
+    return col, rng.normal(0, 3, col.nr_variables()).round(3)
+
+
+def general_rows(seed=77):
+    """the instance of tests/test_layout.py::test_roundtrip_chained_packs: 14 knapsack rows of 15-19 variables (layers of 59-135 nodes: wide
+    packs at pack width 64), 30 of 8-12 variables (layers of up to ~40 nodes: narrow packs) and 40 covering rows of 5 — with pack_stagger
+    several chained packs of both kinds"""
+    from bdd_amd import BddCollection
+    rng = np.random.Generator(np.random.PCG64(seed))
+    col = BddCollection()
+    V = 60
+    for lo_k, hi_k, top, n in ((15, 20, 40, 14), (8, 13, 12, 30)):
+        for _ in range(n):
+            k = int(rng.integers(lo_k, hi_k))
+            co = rng.integers(1, top, size=k)
+            col.add_linear(co, "<=", int(co.sum() // 2), np.sort(rng.choice(V, size=k, replace=False)))
+    for _ in range(40):
         col.add_covering(np.sort(rng.choice(V, size=5, replace=False)))
     return col, rng.normal(0, 3, col.nr_variables()).round(3)
 

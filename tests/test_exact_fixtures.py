@@ -6,9 +6,9 @@ step, headroom and tie shares (pytest -s)."""
 import numpy as np
 import pytest
 
-from exact_fixtures import (HEADROOM, STATES, certificate, iterations_reference, model_of, recorded_values, single_shot_reference, tie_share,
-                            tracked_mm)
-from test_gpu_sum_marginals import FAMILIES
+from exact_fixtures import (HEADROOM, ITERATION_CASES, ITERATION_SEEDS, STATES, certificate, iterations_reference, model_of, recorded_values,
+                            single_shot_reference, tie_share, tracked_mm)
+from test_gpu_sum_marginals import CHAINED, FAMILIES, LAYOUT_OPTIONS, assert_chained_layout
 from test_layout import Layout
 
 TYPES = (np.float32, np.float64, np.longdouble)
@@ -52,8 +52,12 @@ def test_single_shot_fixture(family, state):
     assert np.any(wide["grad_lo"] != 0) and np.any(wide["grad_hi"] != 0)
 
 
-@pytest.mark.parametrize("omega_vec", [False, True], ids=["omega", "omega_vec"])
-@pytest.mark.parametrize("family", sorted(FAMILIES))
+def test_every_family_has_iteration_seeds():
+    assert set(ITERATION_SEEDS) == set(FAMILIES)
+    assert [(f, ov) for f in sorted(FAMILIES) for ov in (False, True) if (f, ov) not in ITERATION_CASES] == [("chained_general", True)]
+
+
+@pytest.mark.parametrize("family,omega_vec", ITERATION_CASES, ids=[f"{f}-{'omega_vec' if ov else 'omega'}" for f, ov in ITERATION_CASES])
 def test_iterations_fixture(family, omega_vec):
     refs = [iterations_reference(family, omega_vec, dt) for dt in TYPES]
     wide = refs[-1]
@@ -121,8 +125,7 @@ def test_slot_order_is_node_order(family):
     """the slots of a layer hold increasing instruction indices, in the layout the family's options give: the lowest slot of a tie is the
     restatement's lowest node, and a node's parents by slot are its parents by node"""
     col, _ = model_of(family)
-    opts = {k: v for k, v in FAMILIES[family][1].items() if k in ("pack_width", "wide_pack_width")}
-    lay = Layout(col, **opts)
+    lay = Layout(col, **{k: v for k, v in FAMILIES[family][1].items() if k in LAYOUT_OPTIONS})
     by_layer = {}
     for slot, (_, _, layer, _, _) in lay.decode().items():
         by_layer.setdefault(layer, []).append(slot)
@@ -134,3 +137,16 @@ def test_slot_order_is_node_order(family):
         assert np.all(np.diff(instr) > 0), (family, layer, instr[:8])
         widest = max(widest, len(slots))
     print(f"{family}: {lay.n_layers} layers, widest {widest} slots ({-(-widest // 16)} runs of 16), packs narrow / wide / huge {lay.np_n} / {lay.np_w} / {lay.np_h}")
+
+
+@pytest.mark.parametrize("family", sorted(CHAINED))
+def test_chained_families_are_chained(family):
+    """the families that stand for chained packs get them from the layout: the recorded hops of every pack, a pack with more hops than the
+    longest BDD has layers (a BDD starts below its first hop) and, with wide packs, fewer of them than wide BDDs; side by side without
+    pack_stagger.  The GPU tests assert the same, and the kind of the solve sweeps, on the solvers they build (assert_chained)."""
+    col, _ = model_of(family)
+    opts = {k: v for k, v in FAMILIES[family][1].items() if k in LAYOUT_OPTIONS}
+    assert opts.get("pack_stagger", 0) >= 2
+    assert_chained_layout(family, col, Layout(col, **opts))
+    with pytest.raises(AssertionError):
+        assert_chained_layout(family, col, Layout(col, **dict(opts, pack_stagger=0)))

@@ -20,7 +20,7 @@ from bdd_amd.capi import BddMmaError
 from bdd_amd.solver import bdd_hip_lbfgs, bdd_hip_parallel_mma
 from grad_iterations_restatement import grad_iterations_of, seeded_inputs
 from test_grad_iterations_restatement import SEEDS, instance_of
-from test_gpu_sum_marginals import FAMILIES
+from test_gpu_sum_marginals import FAMILIES, assert_chained
 
 pytestmark = pytest.mark.gpu
 
@@ -40,6 +40,7 @@ def _setup(family, precision, omega_vec=False, **extra):
     and the solver's type)"""
     col, costs = instance_of(family, precision)
     s = bdd_hip_parallel_mma(col, costs, precision=precision, **FAMILIES[family][1], **extra)
+    assert_chained(family, col, s)
     m = grad_iterations_of(col, precision)
     x = seeded_inputs(m, SEEDS[family][precision][omega_vec] or SEEDS[family]["double"][omega_vec])   # (compared with the restatement: tie-free seeds only, CASES)
     perm = s.bdd_major_order()
@@ -131,7 +132,7 @@ def _assert_same_state(before, s):
 
 
 @pytest.mark.parametrize("precision", ["double", "float"])
-@pytest.mark.parametrize("family", ["cover10_w128", "mixed", "huge"])
+@pytest.mark.parametrize("family", ["cover10_w128", "mixed", "huge", "chained_general"])
 def test_state_contract_and_errors(family, precision):
     s, m, x, perm, pub = _setup(family, precision, deterministic=True)
     L = s.nr_layers()
@@ -182,7 +183,7 @@ def test_state_contract_and_errors(family, precision):
 
 
 @pytest.mark.parametrize("precision", ["double", "float"])
-@pytest.mark.parametrize("family", ["mixed", "huge", "split_bdds"])
+@pytest.mark.parametrize("family", ["mixed", "huge", "split_bdds", "chained_general"])
 def test_device_buffers_and_memory(family, precision):
     s, m, x, perm, pub = _setup(family, precision, deterministic=True)
     L = s.nr_layers()

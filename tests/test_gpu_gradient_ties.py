@@ -18,9 +18,9 @@ import numpy as np
 import pytest
 
 from bdd_amd.solver import bdd_hip_parallel_mma
-from exact_fixtures import (STATES, TRACKED, UNTRACKED, certificate, iterations_reference, model_of, on_grid, recorded_values,
+from exact_fixtures import (ITERATION_CASES, STATES, TRACKED, UNTRACKED, certificate, iterations_reference, model_of, on_grid, recorded_values,
                             single_shot_reference)
-from test_gpu_sum_marginals import FAMILIES
+from test_gpu_sum_marginals import FAMILIES, assert_chained
 
 pytestmark = pytest.mark.gpu
 
@@ -36,6 +36,7 @@ class _Solvers:
     def get(self, deterministic=False):
         if deterministic not in self._s:
             self._s[deterministic] = bdd_hip_parallel_mma(self.col, None, precision=self.precision, deterministic=deterministic, **FAMILIES[self.family][1])
+            assert_chained(self.family, self.col, self._s[deterministic])
         s = self._s[deterministic]
         return s, s.bdd_major_order()
 
@@ -44,11 +45,22 @@ class _Solvers:
             s.close()
 
 
-@pytest.fixture(scope="module", params=[(f, p) for f in sorted(FAMILIES) for p in ("double", "float")], ids=lambda fp: f"{fp[0]}-{fp[1]}")
-def solvers(request):
-    x = _Solvers(*request.param)
-    yield x
-    x.close()
+# a family whose omega_vec form has no exact fixture (exact_fixtures.ITERATION_SEEDS: chained_general) runs the single-shot states and the
+# scalar omega through a fixture and tests of its own
+SCALAR_OMEGA_ONLY = [f for f in sorted(FAMILIES) if (f, True) not in ITERATION_CASES]
+
+
+def _solvers_fixture(families):
+    @pytest.fixture(scope="module", params=[(f, p) for f in families for p in ("double", "float")], ids=lambda fp: f"{fp[0]}-{fp[1]}")
+    def fixture(request):
+        x = _Solvers(*request.param)
+        yield x
+        x.close()
+    return fixture
+
+
+solvers = _solvers_fixture([f for f in sorted(FAMILIES) if f not in SCALAR_OMEGA_ONLY])
+solvers_scalar_omega = _solvers_fixture(SCALAR_OMEGA_ONLY)
 
 
 def _to_public(x, perm, dt):
@@ -75,6 +87,16 @@ def _assert_same(got, want, what, m, q):
 def test_single_shot_gradient(solvers, state):
     """two integer states and the all-zero costs with g on a grid of 2^-8 (every finite minimum a tie): min_marginal_diff() first — the
     forward kernels have no tie rule, this pins the fixture on the device —, then grad_all_min_marginal_differences(g)"""
+    _single_shot_gradient(solvers, state)
+
+
+@pytest.mark.parametrize("state", STATES)
+def test_single_shot_gradient_scalar_omega_families(solvers_scalar_omega, state):
+    """test_single_shot_gradient on the families of SCALAR_OMEGA_ONLY"""
+    _single_shot_gradient(solvers_scalar_omega, state)
+
+
+def _single_shot_gradient(solvers, state):
     s, perm = solvers.get()
     dt, m = s.value_type, solvers.m
     ref = single_shot_reference(solvers.family, state)
@@ -94,6 +116,16 @@ def test_learned_iterations_and_their_gradient(solvers, omega_vec, deterministic
     """one untracked and two tracked iterations from the exact state with d = 0: the forward iterations first (the `mm >= 0` and `d >= 0` rules
     of the forward passes decide a fifth to three quarters of the layer-passes), then all five outputs of grad_iterations with one cache and with
     two.  Exact sums do not depend on the order of the exchange's atomics: the default exchange must match as the deterministic one does."""
+    _learned_iterations_and_their_gradient(solvers, omega_vec, deterministic)
+
+
+@pytest.mark.parametrize("deterministic", [False, True], ids=["default_exchange", "deterministic"])
+def test_learned_iterations_and_their_gradient_scalar_omega_families(solvers_scalar_omega, deterministic):
+    """test_learned_iterations_and_their_gradient with the scalar omega on the families of SCALAR_OMEGA_ONLY"""
+    _learned_iterations_and_their_gradient(solvers_scalar_omega, False, deterministic)
+
+
+def _learned_iterations_and_their_gradient(solvers, omega_vec, deterministic):
     s, perm = solvers.get(deterministic)
     dt, m = s.value_type, solvers.m
     ref = iterations_reference(solvers.family, omega_vec)

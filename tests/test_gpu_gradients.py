@@ -18,7 +18,7 @@ from bdd_amd.capi import BddMmaError
 from bdd_amd.solver import bdd_hip_lbfgs, bdd_hip_parallel_mma
 from grad_restatement import Gradients, gradients_of, tie_free_state
 from test_grad_restatement import SEEDS
-from test_gpu_sum_marginals import FAMILIES
+from test_gpu_sum_marginals import FAMILIES, assert_chained
 
 pytestmark = pytest.mark.gpu
 
@@ -30,6 +30,7 @@ def _tie_free_solver(family, precision, **extra):
     make, opts = FAMILIES[family]
     col, costs = make()
     s = bdd_hip_parallel_mma(col, costs, precision=precision, **opts, **extra)
+    assert_chained(family, col, s)
     m = gradients_of(col, precision)
     lo, hi, g = tie_free_state(m, SEEDS[family])
     perm = s.bdd_major_order()
@@ -82,6 +83,7 @@ def test_antisymmetry_and_determinism_where_ties_are_frequent(family, precision)
     make, opts = FAMILIES[family]
     col, costs = make()
     s = bdd_hip_parallel_mma(col, costs, precision=precision, **opts)
+    assert_chained(family, col, s)
     m = gradients_of(col, precision)
     perm = s.bdd_major_order()
     g = np.random.Generator(np.random.PCG64(9)).normal(0, 1, s.nr_layers()).astype(s.value_type)
@@ -139,7 +141,7 @@ def _assert_same_state(before, s):
 
 
 @pytest.mark.parametrize("precision", ["double", "float"])
-@pytest.mark.parametrize("family", ["cover10_w128", "mixed", "huge"])
+@pytest.mark.parametrize("family", ["cover10_w128", "mixed", "huge", "chained_general"])
 def test_state_contract_and_errors(family, precision):
     s, m, g, perm = _tie_free_solver(family, precision, deterministic=True)
     L, B = s.nr_layers(), s.nr_bdds()
@@ -205,12 +207,13 @@ def test_with_lbfgs_wrapper_attached(precision):
 
 
 @pytest.mark.parametrize("precision", ["double", "float"])
-@pytest.mark.parametrize("family", ["cover10_w128", "mixed", "huge", "split_bdds"])
+@pytest.mark.parametrize("family", ["cover10_w128", "mixed", "huge", "split_bdds", "chained_general"])
 def test_small_operators(family, precision):
     """the three elementwise operators against their one-line NumPy formulas, host and device buffers"""
     make, opts = FAMILIES[family]
     col, costs = make()
     s = bdd_hip_parallel_mma(col, costs, precision=precision, **opts)
+    assert_chained(family, col, s)
     dt = s.value_type
     tdt = torch.float64 if precision == "double" else torch.float32
     L, V, B = s.nr_layers(), s.nr_variables(), s.nr_bdds()

@@ -10,9 +10,12 @@ import pytest
 
 from bdd_amd import BddCollection, to_bdd_collection
 from bdd_amd.capi import BddMmaError
-from bdd_amd.instances import assignment_ilp, random_set_cover
+from bdd_amd.instances import assignment_ilp, random_set_cover, random_set_cover_mixed
 from bdd_amd.solver import bdd_hip_lbfgs, bdd_hip_parallel_mma
 from learned_mma_restatement import LearnedMma
+from sum_marginals_restatement import knapsack_rows as _knapsack_rows
+from test_gpu_sum_marginals import LAYOUT_OPTIONS, assert_chained_layout
+from test_layout import Layout
 from util import GOLDEN, load_golden, pad_costs
 
 pytestmark = pytest.mark.gpu
@@ -80,6 +83,10 @@ def _assignment8():
     return to_bdd_collection(ilp), np.asarray(ilp.objective, np.float64)
 
 
+def _mixed_rows():
+    return random_set_cover_mixed(300, 200, 3, 16, seed=4)   # rows of 3 ... 16 variables
+
+
 NOFUSE = 0x80000   # variant_flags bit 19: four launches per iteration (the fused single-workgroup kernel has its own exchange)
 FAMILIES = {
     # name: (instance, options, expected solve_sweep_kind or None)
@@ -99,7 +106,23 @@ FAMILIES = {
     # accumulators) and the deterministic schedule on bins of ~20 k entries (float: ~120 KiB of differences, pairs and counts)
     "reduce_lds_128k": (lambda: random_set_cover(20_000, 14_000, 8, seed=3), dict(vars_per_bin=8192), None),
     "deterministic_large_bins": (lambda: random_set_cover(40_000, 20_000, 10, seed=4), dict(deterministic=True, vars_per_bin=4096), None),
+    # pack_stagger: chained packs (BDDs start below a pack's first hop, hop_root) — the general form of the streaming sweeps, in the first
+    # generation and (bit 13) with records, and the wide sweeps with roots below the first hop, in one launch with the narrow ones and apart
+    "chained_rows": (_mixed_rows, dict(resident_sweeps=1, pack_stagger=24), "streaming1"),
+    "chained_rows_records": (_mixed_rows, dict(resident_sweeps=1, pack_stagger=24, variant_flags=0x2000), "streaming2"),
+    "chained_knapsack": (_knapsack_rows, dict(pack_width=64, resident_sweeps=1, pack_stagger=24), "streaming1"),
+    "chained_mixed": (_wide, dict(pack_width=64, wide_pack_width=192, resident_sweeps=1, pack_stagger=60), "mixed"),
+    "chained_wide2": (_wide, dict(pack_width=64, wide_pack_width=192, resident_sweeps=1, pack_stagger=60, variant_flags=0x3), "streaming1"),
 }
+# the chained families and the family of test_gpu_sum_marginals.CHAINED whose instance and layout options they share
+CHAINED = {"chained_rows": "chained_rows", "chained_rows_records": "chained_rows", "chained_knapsack": "chained_knapsack", "chained_mixed": "chained_wide",
+           "chained_wide2": "chained_wide2"}
+
+
+def assert_chained(family, col, opts):
+    """a chained family's layout is chained: the recorded hops of every pack, a pack longer than the longest BDD (test_gpu_sum_marginals)"""
+    if family in CHAINED:
+        assert_chained_layout(CHAINED[family], col, Layout(col, **{k: v for k, v in opts.items() if k in LAYOUT_OPTIONS}))
 
 
 @pytest.mark.parametrize("precision", ["double", "float"])
@@ -107,6 +130,7 @@ FAMILIES = {
 def test_isotropic_weights_equal_plain_iterations(family, precision):
     make, opts, kind = FAMILIES[family]
     col, costs = make()
+    assert_chained(family, col, opts)
     a = bdd_hip_parallel_mma(col, costs, precision=precision, **opts)
     b = bdd_hip_parallel_mma(col, costs, precision=precision, **opts)
     if kind is not None:

@@ -13,7 +13,7 @@ from bdd_amd.capi import BddMmaError
 from bdd_amd.instances import random_set_cover, random_set_cover_mt
 from bdd_amd.solver import bdd_hip_lbfgs, bdd_hip_parallel_mma
 from learned_omega_restatement import LearnedOmegaMma
-from test_gpu_learned_mma import FAMILIES, ISO_TOL, NOFUSE, REF_TOL, _assert_close, _cover10, _dirichlet_weights, _same_state
+from test_gpu_learned_mma import FAMILIES, ISO_TOL, NOFUSE, REF_TOL, _assert_close, _cover10, _dirichlet_weights, _same_state, assert_chained
 from util import GOLDEN, load_golden, pad_costs
 
 pytestmark = pytest.mark.gpu
@@ -74,6 +74,7 @@ def _constant_vs_scalar(col, costs, precision, opts, kind=None, nt=False, exact=
 def test_constant_omega_vec_equals_scalar_bit_for_bit(family, precision):
     make, opts, kind = OV_FAMILIES[family]
     col, costs = make()
+    assert_chained(family, col, opts)
     a = _constant_vs_scalar(col, costs, precision, opts, kind, nt=family in NT_FAMILIES and (precision == "double" or "gen1" in family),
                             exact=not (family in ATOMIC_EXCHANGE and precision == "double"))
     if family == "wide2":
@@ -113,6 +114,7 @@ def test_random_omega_vec_in_every_family_vs_restatement(family, precision):
     """each family computes the address of a layer's omega its own way: random omega (with exact zeros) against the restatement"""
     make, opts, kind = OV_FAMILIES[family]
     col, costs = make()
+    assert_chained(family, col, opts)
     s = bdd_hip_parallel_mma(col, None, precision=precision, **opts)
     if kind is not None:
         assert s.solve_sweep_kind() == kind, s.solve_sweep_kind()

@@ -14,7 +14,8 @@ from bdd_amd.capi import BddMmaError
 from bdd_amd.instances import assignment_ilp, random_set_cover_mixed
 from bdd_amd.solver import bdd_hip_lbfgs, bdd_hip_parallel_mma
 from sum_marginals_restatement import (TWO_SIMPLEX_CLOSED_FORMS, SumMarginals, assignment8 as _assignment8, cover10 as _cover10, huge_rows as _huge,
-                                       knapsack_rows as _knapsack_rows, restatement_of, two_simplex, wide_rows as _wide)
+                                       general_rows as _general_rows, knapsack_rows as _knapsack_rows, restatement_of, two_simplex, wide_rows as _wide)
+from test_layout import Layout
 from util import pad_costs
 
 pytestmark = pytest.mark.gpu
@@ -53,7 +54,53 @@ FAMILIES = {
     "assignment8": (_assignment8, dict()),
     "staggered_rows": (_mixed_rows, dict()),
     "split_bdds": (_split, dict()),
+    # pack_stagger: chained packs — BDDs start below a pack's first hop (PackSet::hop_root), what the layout builds by itself for large
+    # instances with general linear rows.  The instance of an existing family each (the same references, seeds and certificates: the
+    # restatements never see the layout), and one with several chained workgroups of both kinds; CHAINED holds what the layout must show
+    "chained_rows": (_mixed_rows, dict(pack_stagger=24)),
+    "chained_knapsack": (_knapsack_rows, dict(pack_width=64, pack_stagger=24)),
+    "chained_wide": (_wide, dict(pack_width=64, wide_pack_width=192, pack_stagger=60)),
+    "chained_wide2": (_wide, dict(pack_width=64, wide_pack_width=192, pack_stagger=60, variant_flags=0x3)),
+    "chained_general": (_general_rows, dict(pack_width=64, wide_pack_width=192, pack_stagger=30)),
 }
+# Per chained family: the hops of every narrow pack, of every wide pack (tests/test_layout.py::Layout, from the options above) and the
+# solve_sweep_kind() observed on the MI355X (the kind is that of the narrow packs: the one narrow pack beside the chained wide pack is
+# not chained and, with resident_sweeps left to the rules, resident; chained_general's sweeps run narrow and wide packs in one launch).
+# A pack with more hops than the longest BDD has layers holds a BDD that starts below its first hop.
+# tests/test_exact_fixtures.py::test_chained_families_are_chained asserts the layout without a GPU, assert_chained() on every solver
+# built here: a change of the layout rules must not quietly move these cases back to side-by-side packs.
+CHAINED = {
+    "chained_rows": dict(narrow=(16, 24, 24, 24, 24, 3), wide=(), longest=16, kind="streaming1"),
+    "chained_knapsack": dict(narrow=(17,), wide=(), longest=14, kind="streaming1"),
+    "chained_wide": dict(narrow=(5,), wide=(36,), longest=20, kind="resident2"),
+    "chained_wide2": dict(narrow=(5,), wide=(36,), longest=20, kind="resident2"),
+    "chained_general": dict(narrow=(30, 30, 30, 5), wide=(29, 25, 16), longest=19, kind="mixed"),
+}
+LAYOUT_OPTIONS = ("pack_width", "wide_pack_width", "pack_stagger")
+
+
+def assert_chained_layout(family, col, lay):
+    """`lay`, the layout of the chained family's collection (a tests/test_layout.py::Layout built from the family's LAYOUT_OPTIONS), is
+    chained: the pack counts and hops of CHAINED, some pack longer than the longest BDD, and wide BDDs sharing wide packs"""
+    want = CHAINED[family]
+    hops = [tuple(int(h) for h in np.diff(S["pack_hop_ptr"].astype(np.int64))) if S["P"] else () for S in lay.sets]
+    longest = max(len(col.layer_widths(b)) for b in range(col.nr_bdds()))
+    assert longest == want["longest"], (family, longest)
+    assert (hops[0], hops[1], lay.np_h) == (want["narrow"], want["wide"], 0), (family, hops)
+    assert max(hops[0] + hops[1]) > longest, (family, hops, longest)
+    if want["wide"]:
+        assert max(hops[1]) > longest, (family, hops, longest)
+        n_wide_bdds = sum(1 for b in range(col.nr_bdds()) if max(col.layer_widths(b)) > lay.pack_width)
+        assert 0 < lay.np_w < n_wide_bdds, (family, lay.np_w, n_wide_bdds)
+
+
+def assert_chained(family, col, s):
+    """where a chained family's solver is built: the layout its options give is chained and the solve sweeps are the observed kind"""
+    if family not in CHAINED:
+        return
+    assert_chained_layout(family, col, Layout(col, **{k: v for k, v in FAMILIES[family][1].items() if k in LAYOUT_OPTIONS}))
+    assert (s.nr_packs(), s.solve_sweep_kind()) == (len(CHAINED[family]["narrow"]) + len(CHAINED[family]["wide"]), CHAINED[family]["kind"]), \
+        (family, s.nr_packs(), s.solve_sweep_kind())
 
 
 def _tolerance(m, dt):
@@ -89,6 +136,7 @@ def test_against_restatement(family, precision):
     make, opts = FAMILIES[family]
     col, costs = make()
     s = bdd_hip_parallel_mma(col, costs, precision=precision, **opts)
+    assert_chained(family, col, s)
     dt = s.value_type
     m = restatement_of(col, costs, precision)
     perm = s.bdd_major_order()
@@ -201,12 +249,13 @@ def _assert_same_state(a, b):
 
 
 @pytest.mark.parametrize("precision", ["double", "float"])
-@pytest.mark.parametrize("family", ["cover10_w128", "mixed", "huge"])
+@pytest.mark.parametrize("family", ["cover10_w128", "mixed", "huge", "chained_general"])
 def test_state_contract(family, precision):
     make, opts = FAMILIES[family]
     col, costs = make()
     a = bdd_hip_parallel_mma(col, costs, precision=precision, deterministic=True, **opts)
     b = bdd_hip_parallel_mma(col, costs, precision=precision, deterministic=True, **opts)
+    assert_chained(family, col, a)
     for s in (a, b):
         s.iterations(3)
     r1 = a.sum_marginals_cuda(False, True)

@@ -10,7 +10,7 @@ import pytest
 from bdd_amd import capi, to_bdd_collection
 from bdd_amd.instances import GRID_3X3, mrf_ilp
 from bdd_amd.solver import bdd_hip_parallel_mma
-from sum_marginals_restatement import TWO_SIMPLEX_CLOSED_FORMS, assignment8, cover10, knapsack_rows, restatement_of, two_simplex
+from sum_marginals_restatement import TWO_SIMPLEX_CLOSED_FORMS, assignment8, cover10, general_rows, knapsack_rows, restatement_of, two_simplex
 from test_capi_symbols import declared_symbols
 
 
@@ -23,12 +23,12 @@ def _mrf3x3():
     return to_bdd_collection(ilp), np.asarray(ilp.objective, np.float64)
 
 
-INSTANCES = {"cover10": _cover10_small, "assignment8": assignment8, "knapsack_rows": knapsack_rows, "mrf3x3": _mrf3x3}
+INSTANCES = {"cover10": _cover10_small, "assignment8": assignment8, "knapsack_rows": knapsack_rows, "mrf3x3": _mrf3x3, "general_rows": general_rows}
 
 
 @pytest.mark.parametrize("name", sorted(INSTANCES))
 def test_restatement_against_brute_force(name):
-    """both sides are float64 sums of at most 2^16 positive terms (worst-case rounding 2^16 * 1.1e-16 = 7e-12): rtol 1e-10"""
+    """both sides are float64 sums of at most 2^19 positive terms (general_rows; worst-case rounding 2^19 * 1.1e-16 = 6e-11): rtol 1e-10"""
     col, costs = INSTANCES[name]()
     m = restatement_of(col, costs, "double")
     sm_lo, sm_hi = m.log_sum_marginals(np.float64)
