@@ -81,6 +81,8 @@ class bdd_hip_parallel_mma {
     size_t nr_variables() const { return bddmma_nr_variables(h_); }
     size_t nr_bdds() const { return bddmma_nr_bdds(h_); }
     size_t nr_layers() const { return bddmma_nr_layers(h_); }
+    // a bdd_hip_batch can run this solver's learned iterations with their history inside one workgroup (bddmma_fused_small_history)
+    bool fused_small_history() const { return bddmma_fused_small_history(h_) == 1; }
     size_t nr_bdd_nodes() const { return bddmma_nr_bdd_nodes(h_); }
     size_t nr_hops() const { return bddmma_nr_hops(h_); }
     size_t nr_bdds(const size_t var) const
@@ -482,6 +484,24 @@ class bdd_hip_batch {
     void learned_iterations_dev(const REAL* dev_dist_weights, const size_t num_itr, const REAL omega = 0.5, const REAL* dev_omega_vec = nullptr)
     {
         check(bddmma_learned_iterations_batch(b_, dev_dist_weights, dev_omega_vec, omega, num_itr, 1));
+    }
+    // ... with the history of the last min(num_itr, compute_history_for_itr) iterations, computed inside the members' workgroups: sol_avg holds
+    // the members' REAL[nr_layers], lb_first_diff_avg / lb_second_diff_avg the members' REAL[nr_bdds], one behind the other; updated in
+    // place (the caller sizes them; an entry the history does not reach keeps its content).  Every member must be fused_small_history()
+    // (include/bdd_mma.h: bddmma_learned_iterations_history_batch).
+    void learned_iterations(const std::vector<REAL>& dist_weights, const size_t num_itr, const REAL omega, const std::vector<REAL>* omega_vec,
+                            const size_t compute_history_for_itr, const REAL history_avg_beta, std::vector<REAL>& sol_avg, std::vector<REAL>& lb_first_diff_avg,
+                            std::vector<REAL>& lb_second_diff_avg)
+    {
+        check(bddmma_learned_iterations_history_batch(b_, dist_weights.data(), omega_vec ? omega_vec->data() : nullptr, omega, num_itr, sol_avg.data(),
+                                                      lb_first_diff_avg.data(), lb_second_diff_avg.data(), compute_history_for_itr, history_avg_beta, 0));
+    }
+    void learned_iterations_dev(const REAL* dev_dist_weights, const size_t num_itr, const REAL omega, const REAL* dev_omega_vec,
+                                const size_t compute_history_for_itr, const REAL history_avg_beta, REAL* dev_sol_avg, REAL* dev_lb_first_diff_avg,
+                                REAL* dev_lb_second_diff_avg)
+    {
+        check(bddmma_learned_iterations_history_batch(b_, dev_dist_weights, dev_omega_vec, omega, num_itr, dev_sol_avg, dev_lb_first_diff_avg,
+                                                      dev_lb_second_diff_avg, compute_history_for_itr, history_avg_beta, 1));
     }
     // grad_iterations(...) of every member with its part of every device array (bdd_hip_parallel_mma::grad_iterations; the members' arrays
     // one behind the other), one workgroup per member: dev_grad_omega has size() entries, the concatenated per-layer array with

@@ -156,6 +156,7 @@ uint64_t bddmma_nr_packs(const bddmma_solver* s) { return s && s->impl ? s->impl
 int bddmma_solve_sweep_kind(const bddmma_solver* s) { return s && s->impl ? s->impl->solve_sweep_kind : -1; }
 int bddmma_fused_small(const bddmma_solver* s) { return s && s->impl ? (s->impl->fused_small ? 1 : 0) : -1; }
 int bddmma_fused_small_learned(const bddmma_solver* s) { return s && s->impl ? (s->impl->fused_small_learned ? 1 : 0) : -1; }
+int bddmma_fused_small_history(const bddmma_solver* s) { return s && s->impl ? (s->impl->fused_small_history ? 1 : 0) : -1; }
 int bddmma_nontemporal_loads(const bddmma_solver* s) { return s && s->impl ? (s->impl->nt_loads ? 1 : 0) : -1; }
 int bddmma_potentials_on_chip(const bddmma_solver* s) { return s && s->impl ? (s->impl->pot_on_chip ? 1 : 0) : -1; }
 int bddmma_precision(const bddmma_solver* s) { return s && s->impl ? s->impl->precision : -1; }
@@ -446,6 +447,15 @@ int bddmma_batch_iterations(bddmma_batch* b, double omega, uint64_t n)
 int bddmma_learned_iterations_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec, double omega, uint64_t num_itr, int on_device)
 {
     return guarded_batch(b, [&](BatchBase* i) { return i->learned_iterations(dist_weights, omega_vec, omega, num_itr, on_device); });
+}
+int bddmma_learned_iterations_history_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec, double omega, uint64_t num_itr, void* sol_avg,
+                                            void* lb_first_diff_avg, void* lb_second_diff_avg, uint64_t compute_history_for_itr, double history_avg_beta,
+                                            int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        return i->learned_iterations_history(dist_weights, omega_vec, omega, num_itr, sol_avg, lb_first_diff_avg, lb_second_diff_avg, compute_history_for_itr,
+                                             history_avg_beta, on_device);
+    });
 }
 int bddmma_grad_learned_iterations_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec, double omega, void* grad_lo, void* grad_hi,
                                          void* grad_mm, void* grad_dist_weights_out, void* grad_omega_out, uint64_t track_grad_after_itr,

@@ -1,5 +1,5 @@
 // kernels/small.hpp — instances that fit ONE workgroup: whole MMA iterations inside one launch (k_iterate_small, k_iterate_small_batch),
-// and whole learned iterations (k_learned_small, k_learned_small_batch).
+// and whole learned iterations (k_learned_small, k_learned_small_batch; with their history step: k_learned_small_hist_batch, kernels/smallhist.hpp).
 // Part of kernels.hpp (include that, not this file: the parts build on each other in its order).
 #pragma once
 
@@ -115,6 +115,54 @@ struct SmallRecord {
     __host__ __device__ REAL* F(uint32_t k) const { return mm1(k) + ls; }
 };
 
+// HISTORY (k_learned_small_hist_batch, kernels/smallhist.hpp: bddmma_learned_iterations_history_batch): the history step of
+// SolverT::learned_iterations (solver_impl.hpp, bdd_cuda_learned_mma.cu:211-254) behind the backward sweep of every iteration with index
+// >= hist_from, out of LDS:
+//   the arg-min path of every BDD (FWD_SOLUTION, kernels/narrow.hpp): each wave runs a plain forward pass over its pack's hops — costs-from-
+//           root from the current arc costs into the pack's F array, which the next forward solve sweep initialises again (after the launch's
+//           last iteration the epilogue stores them; the host state marks the costs-from-root invalid after every launch of whole
+//           iterations, so nothing reads them).  No LDS of its own: the on-path marks of a hop's nodes are the 64 dummy entries behind the
+//           pack's costs-from-root, indexed by the node's slot modulo 64 (a hop's slots are consecutive and at most 64; this pass pushes into
+//           no dummy entry), and a layer's decision waits in the .y half of its staging pair — dead between a backward sweep and the next
+//           exchange, which writes every pair before a sweep reads it — until the wave applies the sol_avg rule to its layers, coalesced.
+//           As other waves' exchange threads write this pack's pairs, a workgroup barrier separates the history step from the next exchange.
+//   the per-BDD bounds: thread b owns BDD b (a member has at most 64 BDDs per pack: every root is a node of hop 0) and reads T[root] from
+//           the LDS region of the root's pack; the bounds of the two steps before wait in lb_state, between steps and across launches.
+// `tracked` is the number of history steps of the call before this launch; the outputs are this member's part of the caller's arrays.
+// What the step reads lives in global memory (SmallHistMem, part of the member's item) and is fetched by scalar loads inside the step: held
+// in SGPRs through the solve sweeps it spilled the 16-wave instantiations, whose budget is 128 VGPRs, into scratch.
+template <typename REAL>
+struct SmallHistMem {
+    const uint32_t* root_slot;   // [n_bdds]: the solver's slot of BDD b's root (the order of bddmma_lower_bound_per_bdd)
+    REAL* lb_state;              // [2 n_bdds]: the bound of the last history step | of the one before it
+    REAL *sol_avg, *lb_first, *lb_second;   // this member's part of the caller's arrays
+    uint32_t n_bdds;
+    REAL beta;
+};
+template <typename REAL>
+struct SmallHist {
+    const SmallHistMem<REAL>* mem;
+    uint32_t hist_from, tracked;
+};
+// What the history form asks beyond the learned form (SolverT::small_hist_ok): a thread per BDD.  It holds by construction — every root is a
+// node of hop 0, so a pack has at most 64 BDDs and a member at most 64 per wave — and is checked because the kernel relies on it.
+inline bool small_hist_fits(uint64_t n_bdds, uint32_t nw) { return n_bdds <= 64ull * nw; }
+// compute_exp_moving_avg with the bits of k_ema (kernels/elementwise.hpp), whose sum the compiler contracts into one fused multiply-add —
+// in float around (1 - beta) * cur, the product beta * avg being rounded to float first; in double around beta * avg, with (1 - beta) * cur
+// rounded (k_ema's ISA: v_mul_f32, v_fmac_f64 / v_mul_f64, v_fmac_f64).  Written out, so that the same operations run wherever this is inlined.
+template <typename REAL>
+__device__ __forceinline__ REAL small_ema(REAL avg, REAL cur, REAL beta)
+{
+#pragma clang fp contract(off)
+    if constexpr (sizeof(REAL) == 4) {
+        const float ba = beta * avg;
+        return (float)__builtin_fma(1.0 - (double)beta, (double)cur, (double)ba);
+    } else {
+        const double oc = (1.0 - beta) * cur;
+        return __builtin_fma(beta, avg, oc);
+    }
+}
+
 // The workgroup's work, shared by k_iterate_small (one instance per launch) and k_iterate_small_batch (one instance per workgroup).
 // NW waves, pack p on wave p (n_packs <= NW); RL: the packs' records live in LDS too (1 KiB per hop), else they stream from L2 eight hops ahead
 // LEARNED (k_learned_small, k_learned_small_batch): n learned iterations,
@@ -125,11 +173,13 @@ struct SmallRecord {
 // omega from its layer's slot.  The plain exchange behind the last backward sweep and the plain epilogue leave what the four-launch path
 // leaves: the last backward pass's differences deferred, delta their isotropic exchange, the bound's partial sums.  No run_solver (run.ctl
 // is null there), so no early return at all.
-template <typename REAL, int NW, bool RL, bool LEARNED = false, bool RECORD = false>
+template <typename REAL, int NW, bool RL, bool LEARNED = false, bool RECORD = false, bool HISTORY = false>
 __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<REAL>& d, const PackDev& pk, REAL omega, uint32_t n_iters, const RunStep& run,
-                                              const SmallLearn<REAL>* ln = nullptr, const SmallRecord<REAL>* rec = nullptr)
+                                              const SmallLearn<REAL>* ln = nullptr, const SmallRecord<REAL>* rec = nullptr, const SmallHist<REAL>* hs = nullptr)
 {
     static_assert(!RECORD || LEARNED, "only the learned iterations are recorded");
+    static_assert(!HISTORY || LEARNED, "only the learned iterations have a history");
+    static_assert(!(HISTORY && RECORD), "the history form is not recorded");
     constexpr uint32_t S = sizeof(REAL);
     constexpr uint32_t NT = 64 * NW;
     using P2 = typename Pair<REAL>::type;
@@ -353,6 +403,97 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
             for (uint32_t j = (uint32_t)lane; j < nslots; j += 64u) pg[j] = lds_ld<REAL>(dyn_lds, (mid ? wbF : wb) + j * S);
         }
     };
+    // The history step behind a backward sweep and its barrier; `tracked`: the steps of the call before this one.  The caller's barrier follows.
+    auto history = [&](uint32_t tracked) {
+        if constexpr (HISTORY) {
+            // (the thread's indices through opaque registers: whatever this step derives from them — addresses into the caller's arrays, the
+            // root's LDS address — is computed here, not hoisted in front of the iterations, where it would stay live through the solve
+            // sweeps and cost the records-in-L2 instantiation of 16 waves its last registers)
+            uint32_t ht = tid, hl = (uint32_t)lane;
+            asm volatile("" : "+v"(ht), "+v"(hl));
+            const SmallHistMem<REAL>* hm = hs->mem;   // likewise: its fields by scalar loads, here
+            asm volatile("" : "+s"(hm));
+            // thread b's BDD: where its root's cost-to-terminal lies in LDS, and the bounds of the two history steps before — kept in
+            // global memory between the steps (and so across launches), not in registers that would live through the solve sweeps;
+            // requested here, used behind the pack's pass
+            const bool hb_own = ht < hm->n_bdds;
+            uint32_t hb_addr = 0;
+            REAL hb_second = REAL(0), hb_third = REAL(0);
+            if (hb_own) {
+                const uint32_t slot = hm->root_slot[ht];
+                uint32_t q = 0;
+                for (uint32_t k = 1; k < sm.n_packs; ++k)
+                    if (slot - sm.pack_hdr[8 * (size_t)k] < sm.pack_hdr[8 * (size_t)k + 1]) q = k;   // the pack whose slot range holds the root
+                hb_addr = sm.off_regions + q * region + (slot - sm.pack_hdr[8 * (size_t)q]) * S;
+                if (tracked >= 1) hb_second = hm->lb_state[ht];
+                if (tracked >= 2) hb_third = hm->lb_state[hm->n_bdds + ht];
+            }
+            if (has_pack) {
+                // the decisions per layer in the .y of the layer's staging pair (0 where no node of the layer is on the path, as the memset
+                // of the solution buffer leaves it); the on-path marks of a hop's nodes in the 64 dummy entries behind the costs-from-root,
+                // indexed by the slot modulo 64: this pass pushes into no dummy entry
+                constexpr uint32_t P2S = (uint32_t)sizeof(P2);
+                const uint32_t mk = wbF + sm.ns * S, f_end = res2_f_off(S, sm.ns) + sm.ns * S;
+                for (uint32_t o = hl; o < sm.ns; o += 64u) lds_st<REAL>(dyn_lds, wbF + o * S, INF);
+                lds_st<REAL>(dyn_lds, mk + hl * S, REAL(0));
+                for (uint32_t j = hl; j < nlayers; j += 64u) lds_st<REAL>(dyn_lds, db + j * P2S + S, REAL(0));
+                wave_sync();
+                for (uint32_t h = 0; h < nh; ++h) {
+                    const u4v r = RL ? lds_ld<u4v>(dyn_lds, rlane + h * 1024u) : __builtin_amdgcn_raw_buffer_load_b128(rr, hl * 16u, (rbase + h * 64u) * 16u, 0);
+                    const bool real = RL ? (r[2] & 0xFFFFu) != ll_dummy : r[3] != RES2_PAD;
+                    const uint32_t ll = r[2] & 0xFFFFu, fs = r[2] >> 16;
+                    const uint32_t own_mark = mk + ((fs / S) & 63u) * S;
+                    // every node of hop 0 is a root: cost-from-root 0 and on the path (flush_costs_from_root; FWD_SOLUTION's `j == rt`)
+                    const REAL f = h == 0 ? (real ? REAL(0) : INF) : lds_ld<REAL>(dyn_lds, wbF + fs);
+                    const bool on = real && (h == 0 || lds_ld<REAL>(dyn_lds, own_mark) != REAL(0));
+                    const REAL tl = lds_ld<REAL>(dyn_lds, wb + (r[0] & 0xFFFFu)), th = lds_ld<REAL>(dyn_lds, wb + (r[0] >> 16));
+                    const P2 cc = lds_ld<P2>(dyn_lds, wbC + ll);
+                    if (on) lds_st<REAL>(dyn_lds, own_mark, REAL(0));   // (before the marks of the next hop: its slots may have the same index)
+                    wave_sync();
+                    // compute_bdd_sol_func as FWD_SOLUTION evaluates it (kernels/narrow.hpp): this parenthesisation, not the solve sweeps'
+                    const REAL hi_path = f + (th + cc.y);
+                    const REAL lo_path = f + (tl + cc.x);
+                    const bool take_lo = (hi_path - lo_path) > 0;
+                    if (on) {
+                        lds_st<REAL>(dyn_lds, db + ll + S, take_lo ? REAL(0) : REAL(1));
+                        const uint32_t ct = take_lo ? (r[0] & 0xFFFFu) : (r[0] >> 16);   // the child taken: its slot, or a sink's entry
+                        if (ct < sm.ns * S) lds_st<REAL>(dyn_lds, mk + ((ct / S) & 63u) * S, REAL(1));
+                    }
+                    // the pushes; into a sink or from a padding lane: +inf into the lane's own slot (a padding lane's is a mark: min(mark, +inf))
+                    const uint32_t plo = r[1] & 0xFFFFu, phi = r[1] >> 16;
+                    const bool blo = plo < f_end, bhi = phi < f_end;
+                    lds_min(reinterpret_cast<REAL*>(dyn_lds + (blo ? wb + plo : wbF + fs)), blo ? f + cc.x : INF);
+                    lds_min(reinterpret_cast<REAL*>(dyn_lds + (bhi ? wb + phi : wbF + fs)), bhi ? f + cc.y : INF);
+                    wave_sync();
+                }
+                // sol_avg: copied at the first step of a call, the moving average afterwards (bdd_cuda_learned_mma.cu:217-222)
+                REAL* const so = hm->sol_avg + layer0;
+                for (uint32_t j = hl; j < nlayers; j += 64u) {
+                    const REAL x = lds_ld<REAL>(dyn_lds, db + j * P2S + S);
+                    so[j] = tracked == 0 ? x : small_ema(so[j], x, hm->beta);
+                }
+            }
+            // the per-BDD bounds (:224-252): the change against the step before, the change of the change, then the bounds rotate
+            if (hb_own) {
+                const REAL lb_last = lds_ld<REAL>(dyn_lds, hb_addr);
+                if (tracked >= 1) {
+                    REAL chg = lb_last - hb_second;
+                    REAL* const o1 = hm->lb_first + ht;
+                    if (tracked == 1) {
+                        *o1 = chg;
+                    } else {
+                        *o1 = small_ema(*o1, chg, hm->beta);
+                        const REAL prev_chg = hb_second - hb_third;
+                        chg = chg - prev_chg;
+                        REAL* const o2 = hm->lb_second + ht;
+                        *o2 = tracked == 2 ? chg : small_ema(*o2, chg, hm->beta);
+                    }
+                }
+                hm->lb_state[hm->n_bdds + ht] = hb_second;
+                hm->lb_state[ht] = lb_last;
+            }
+        }
+    };
     constexpr std::integral_constant<bool, false> PLAIN_EX{};
     constexpr std::integral_constant<bool, LEARNED> ITER_EX{};
     uint32_t it = 0;
@@ -504,6 +645,12 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
             }
         }
         __syncthreads();
+        if constexpr (HISTORY) {
+            if (it >= hs->hist_from) {   // (uniform)
+                history(hs->tracked + (it - hs->hist_from));
+                __syncthreads();   // the next exchange writes the staging pairs of every pack
+            }
+        }
         if constexpr (!LEARNED) {
 #ifdef BDDMMA_EXP_SMALL_SKIP
         if (!(BDDMMA_EXP_SMALL_SKIP & 8))

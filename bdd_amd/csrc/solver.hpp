@@ -81,6 +81,7 @@ struct SolverBase {
     std::shared_ptr<int> lbfgs_attached = std::make_shared<int>(0);
     bool fused_small = false;   // whole iterations in one launch (diagnostics: bddmma_fused_small)
     bool fused_small_learned = false;   // ... and whole learned iterations (bddmma_fused_small_learned)
+    bool fused_small_history = false;   // ... and their history step, in a batch (bddmma_fused_small_history)
     bool nt_loads = false;      // the solve sweeps' non-temporal instantiation (diagnostics: bddmma_nontemporal_loads)
     bool pot_on_chip = false;   // iteration()'s solve sweeps rebuild F and T on chip (diagnostics: bddmma_potentials_on_chip)
     // run_solver (include/run_solver_util.h:10-77) around iteration(): termination tests on the device, see solver_impl.hpp
@@ -179,6 +180,11 @@ struct BatchBase {
     // SolverBase::learned_iterations(w_i, num_itr, omega, slope 0, no history) of every member, or its omega_vec form; dist_weights /
     // omega_vec: the members' REAL[nr_layers] one behind the other in the caller's order (include/bdd_mma.h: bddmma_learned_iterations_batch)
     virtual int learned_iterations(const void* dist_weights, const void* omega_vec, double omega, uint64_t num_itr, int on_device) = 0;
+    // ... with compute_history_for_itr / history_avg_beta and the three history outputs: sol_avg as the layer arrays, the two per-BDD
+    // arrays the members' REAL[nr_bdds] one behind the other (include/bdd_mma.h: bddmma_learned_iterations_history_batch)
+    virtual int learned_iterations_history(const void* dist_weights, const void* omega_vec, double omega, uint64_t num_itr, void* sol_avg,
+                                           void* lb_first_diff_avg, void* lb_second_diff_avg, uint64_t compute_history_for_itr, double history_avg_beta,
+                                           int on_device) = 0;
     // SolverBase::grad_learned_iterations of every member with its part of every array, one workgroup per member in one launch
     // (include/bdd_mma.h: bddmma_grad_learned_iterations_batch)
     virtual int grad_learned_iterations(const void* dist_weights, const void* omega_vec, double omega, void* grad_lo, void* grad_hi, void* grad_mm,

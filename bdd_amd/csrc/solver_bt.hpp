@@ -8,6 +8,7 @@
 #include "solver_impl.hpp"
 #include "kernels/gradsmall.hpp"
 #include "kernels/batchcosts.hpp"
+#include "kernels/smallhist.hpp"
 
 namespace bddmma {
 
@@ -42,7 +43,7 @@ struct BatchT final : BatchBase {
         for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1, ev_order})
             if (e) (void)hipEventDestroy(e);
         if (d_items) (void)hipFree(d_items);
-        for (void* q : {(void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage})
+        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage})
             if (q) (void)hipFree(q);
         if (d_ctl) (void)hipFree(d_ctl);
         if (h_ctl) (void)hipHostFree(h_ctl);
@@ -265,14 +266,87 @@ struct BatchT final : BatchBase {
         for (S* s : m) s->small_launched();
         return BDDMMA_OK;
     }
+    // ---- ... with their history (kernels/smallhist.hpp: k_learned_small_hist_batch; the kernels compile in solver_sh_f32.hip / _f64.hip)
+    // Items in the learned groups' order (the same key: waves x records in LDS); a member's two bounds that cross launches live in its
+    // d_hist, allocated here before any member is touched.  Host outputs pass through hs_stage (sol_avg | lb_first | lb_second).
+    using HsFn = typename S::SmallHistFn;
+    std::vector<HsFn> hs_fn;       // per learned group
+    SmallHistItem<REAL>* d_hs_items = nullptr;
+    REAL* d_hs_stage = nullptr;
+    uint64_t hs_bdds = 0;          // BDDs of all members
+    bool hs_ready = false;
+
+    int hs_prepare()
+    {
+        const uint32_t n = (uint32_t)m.size();
+        std::vector<uint32_t> ord(n);
+        for (uint32_t i = 0; i < n; ++i) ord[i] = i;
+        auto key = [&](uint32_t i) { return (uint32_t)m[i]->small_nw * 2u + (m[i]->small_ln_rl ? 1u : 0u); };
+        std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return key(a) < key(b); });   // ln_prepare's order
+        std::vector<uint64_t> src_b(n);
+        uint64_t total_b = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            src_b[i] = total_b;
+            total_b += m[i]->n_bdds;
+        }
+        if (ln_total > 0xFFFFFFFFull || total_b > 0xFFFFFFFFull) { err = "batch learned_iterations: too many layers"; return BDDMMA_ERR_UNSUPPORTED; }
+        for (S* s : m)
+            if (!s->d_hist)
+                if (int rc = s->dalloc(&s->d_hist, s->n_layers + 5 * s->n_bdds)) { err = s->err; return rc; }
+        std::vector<SmallHistItem<REAL>> items(n);
+        for (uint32_t j = 0; j < n; ++j) {
+            const S* s = m[ord[j]];
+            // (of d_hist's L + 5 B values the per-member call uses all; it starts every call afresh, as this one does)
+            // (the outputs and beta: k_hist_items_call, per call)
+            items[j] = SmallHistItem<REAL>{s->small_learn_item(),
+                                           SmallHistMem<REAL>{s->d_root_slot, s->d_hist + s->n_layers, nullptr, nullptr, nullptr, (uint32_t)s->n_bdds, REAL(0)},
+                                           (uint32_t)ln_src[ord[j]], (uint32_t)src_b[ord[j]]};
+        }
+        std::vector<HsFn> fns;
+        for (const LnGroup& g : ln_groups) {
+            const S* s = m[ord[g.first]];
+            fns.push_back(S::sh_batch_fn(s->small_nw, s->small_ln_rl));
+            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(fns.back()), g.lds)) return rc;
+        }
+        if (!d_hs_items) HIPCHK(hipMalloc((void**)&d_hs_items, n * sizeof(SmallHistItem<REAL>)));
+        if (!d_hs_stage) HIPCHK(hipMalloc((void**)&d_hs_stage, std::max<uint64_t>(ln_total + 2 * total_b, 1) * sizeof(REAL)));
+        HIPCHK(hipMemcpy(d_hs_items, items.data(), n * sizeof(SmallHistItem<REAL>), hipMemcpyHostToDevice));
+        hs_fn = std::move(fns);
+        hs_bdds = total_b;
+        return BDDMMA_OK;
+    }
+    int launch_learned_hist(REAL omega, uint32_t n_iters, bool ov, uint32_t hist_from, uint32_t tracked)
+    {
+        for (size_t k = 0; k < ln_groups.size(); ++k) {
+            const LnGroup& g = ln_groups[k];
+            hipLaunchKernelGGL(hs_fn[k], dim3(g.count), dim3(g.threads), g.lds, stream, (const SmallHistItem<REAL>*)(d_hs_items + g.first), omega, n_iters, ov ? 1u : 0u,
+                               hist_from, tracked);
+            HIPCHK(hipGetLastError());
+        }
+        for (S* s : m) s->small_launched();
+        return BDDMMA_OK;
+    }
     int learned_iterations(const void* w, const void* omega_vec, double omega, uint64_t num_itr, int on_dev) override
+    {
+        return learned_iterations_history(w, omega_vec, omega, num_itr, nullptr, nullptr, nullptr, 0, 0.0, on_dev);
+    }
+    // cfi == 0: the call without a history, launch for launch what it was
+    int learned_iterations_history(const void* w, const void* omega_vec, double omega, uint64_t num_itr, void* sol_avg, void* lb1_avg, void* lb2_avg, uint64_t cfi,
+                                   double beta_d, int on_dev) override
     {
         int rc;
         const uint32_t n = (uint32_t)m.size();
         if (!w) { err = "batch learned_iterations: dist_weights is null"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if (cfi > 0 && (!sol_avg || !lb1_avg || !lb2_avg)) {
+            err = "batch learned_iterations: compute_history_for_itr > 0 needs sol_avg, lb_first_diff_avg and lb_second_diff_avg";
+            return BDDMMA_ERR_INVALID_ARGUMENT;
+        }
         if ((rc = check_state())) return rc;
         for (uint32_t i = 0; i < n; ++i)
-            if (!m[i]->small_ln_ok) {
+            if (cfi > 0 && !m[i]->small_hist_ok) {
+                err = "batch member " + std::to_string(i) + ": learned iterations with their history do not fit one workgroup (bddmma_fused_small_history is 0)";
+                return BDDMMA_ERR_UNSUPPORTED;
+            } else if (!m[i]->small_ln_ok) {
                 err = "batch member " + std::to_string(i) + ": learned iterations do not fit one workgroup's LDS (bddmma_fused_small_learned is 0)";
                 return BDDMMA_ERR_UNSUPPORTED;
             }
@@ -280,6 +354,10 @@ struct BatchT final : BatchBase {
         if (!ln_ready) {
             if ((rc = ln_prepare())) return rc;
             ln_ready = true;
+        }
+        if (cfi > 0 && !hs_ready) {
+            if ((rc = hs_prepare())) return rc;
+            hs_ready = true;
         }
         const bool ov = omega_vec != nullptr;
         // host inputs: checked here, before anything is copied
@@ -338,9 +416,36 @@ struct BatchT final : BatchBase {
         }
         uint64_t left = num_itr;
         const REAL omega_r = (REAL)omega;
+        // The history: the last min(num_itr, cfi) iterations are tracked (bdd_cuda_learned_mma.cu:211).  A launch whose iterations all lie
+        // in front of them is the learned launch without a history; any other runs the history form, told which of its iterations is the
+        // first tracked one and how many history steps the call has made so far.  Host outputs: their content goes to the device first —
+        // an entry the history does not reach keeps it — and comes back behind the last launch.
+        const uint64_t untracked = num_itr - std::min(num_itr, cfi);
+        const uint64_t hist_values = cfi > 0 ? ln_total + 2 * hs_bdds : 0;
+        REAL *o_sol = (REAL*)sol_avg, *o_lb1 = (REAL*)lb1_avg, *o_lb2 = (REAL*)lb2_avg;
+        if (cfi > 0) {
+            hipError_t e = hipSuccess;
+            if (!on_dev) {
+                o_sol = d_hs_stage; o_lb1 = d_hs_stage + ln_total; o_lb2 = o_lb1 + hs_bdds;
+                e = hipMemcpyAsync(o_sol, sol_avg, ln_total * sizeof(REAL), hipMemcpyHostToDevice, stream);
+                if (e == hipSuccess) e = hipMemcpyAsync(o_lb1, lb1_avg, hs_bdds * sizeof(REAL), hipMemcpyHostToDevice, stream);
+                if (e == hipSuccess) e = hipMemcpyAsync(o_lb2, lb2_avg, hs_bdds * sizeof(REAL), hipMemcpyHostToDevice, stream);
+            }
+            if (e == hipSuccess) {   // the call's outputs and beta into the items, in stream order
+                hipLaunchKernelGGL((k_hist_items_call<REAL>), dim3(cdiv(n, 256)), dim3(256), 0, stream, d_hs_items, n, o_sol, o_lb1, o_lb2, (REAL)beta_d);
+                e = hipGetLastError();
+            }
+            if (e != hipSuccess) { err = std::string("batch learned_iterations: ") + hipGetErrorString(e); (void)join_out(); return BDDMMA_ERR_DEVICE; }
+        }
+        // iterations [at, at + count) of the call
+        auto launch_range = [&](uint64_t at, uint32_t count) -> int {
+            if (at + count <= untracked) return launch_learned(omega_r, count, ov);
+            const uint64_t first = std::max(at, untracked);
+            return launch_learned_hist(omega_r, count, ov, (uint32_t)(first - at), (uint32_t)std::min<uint64_t>(first - untracked, 0xFFFFFFFFull));
+        };
         if (any) {
             if ((rc = join_in())) { (void)join_out(); return rc; }
-            rc = launch_learned(omega_r, 1, ov);
+            rc = launch_range(0, 1);
             const int rc2 = join_out();
             if (rc || rc2) return rc ? rc : rc2;
             for (uint32_t i = 0; i < n; ++i)
@@ -351,11 +456,18 @@ struct BatchT final : BatchBase {
             if ((rc = join_in())) { (void)join_out(); return rc; }
             while (left) {
                 const uint32_t chunk = (uint32_t)std::min<uint64_t>(left, 1u << 14);   // as SolverT::iterations
-                if ((rc = launch_learned(omega_r, chunk, ov))) break;
+                if ((rc = launch_range(num_itr - left, chunk))) break;
                 left -= chunk;
             }
             const int rc2 = join_out();
             if (rc || rc2) return rc ? rc : rc2;
+        }
+        if (hist_values && !on_dev) {   // behind the last launch on the batch stream: the one synchronisation of the host outputs
+            hipError_t e = hipMemcpyAsync(sol_avg, o_sol, ln_total * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(lb1_avg, o_lb1, hs_bdds * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(lb2_avg, o_lb2, hs_bdds * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) { err = std::string("batch learned_iterations: ") + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
         }
         for (uint32_t i = 0; i < n; ++i)
             if (want[i]) {

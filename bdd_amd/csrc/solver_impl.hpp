@@ -76,6 +76,7 @@ struct PullSweep {
 #endif
 template <typename REAL> struct GradSmallItem;   // kernels/gradsmall.hpp
 template <typename REAL> struct GradSmallIO;
+template <typename REAL> struct SmallHistItem;   // kernels/smallhist.hpp
 template <typename REAL>
 struct SolverT final : SolverBase {
     // device buffers
@@ -197,6 +198,7 @@ struct SolverT final : SolverBase {
     // budget) + omega per layer.  The kernels live in solver_sl_f32.hip / _f64.hip: sl_prepare() resolves this
     // solver's and raises its dynamic-LDS limit on the first call that launches it.
     bool small_ln_ok = false, small_ln_rl = false, sl_ready = false;
+    bool small_hist_ok = false;   // the learned form with its history step (kernels/small.hpp: HISTORY); no LDS beyond the learned form's
     uint32_t small_ln_lds = 0;
     SmallDev small_ln{};
     SmallLearn<REAL> small_ln_arg{};
@@ -693,6 +695,10 @@ struct SolverT final : SolverBase {
                     small_ln_lds = lbytes;
                     small_ln_ok = true;
                     fused_small_learned = true;
+                    // The history step keeps its on-path marks in the 64 dummy entries behind a pack's costs-from-root and its decisions in
+                    // the .y halves of the staging pairs, so it needs no LDS of its own; a thread per BDD holds the bounds.
+                    small_hist_ok = small_hist_fits((uint64_t)n_bdds, (uint32_t)small_nw);
+                    fused_small_history = small_hist_ok;
                 }
             }
         }
@@ -970,6 +976,10 @@ struct SolverT final : SolverBase {
     using GradSmallLoadFn = void (*)(const GradSmallItem<REAL>*, GradSmallIO<REAL>, uint32_t*);
     static GradSmallFn gs_batch_fn(int nw, bool rl);
     static GradSmallLoadFn gs_load_fn();
+    // The learned iterations with their history for a batch (kernels/smallhist.hpp; BatchT::learned_iterations_history): the kernels live in
+    // solver_sh_f32.hip / _f64.hip.
+    using SmallHistFn = void (*)(const SmallHistItem<REAL>*, REAL, uint32_t, uint32_t, uint32_t, uint32_t);
+    static SmallHistFn sh_batch_fn(int nw, bool rl);
     bool ov_ready = false;
     // One sweep: the wide and the narrow packs (one launch where `mixed`; forward only with mixed_fwd), then the huge ones.
     int launch_sweep(bool bwd, const Sweep& s, const REAL* delta_lay, REAL omega, int kclass, bool ov = false)

@@ -95,6 +95,10 @@ class bdd_hip_parallel_mma:
         """True when learned_iterations() runs whole learned iterations inside one launch too (with improvement_slope <= 0; batches of
         such solvers: bdd_hip_batch.learned_iterations)"""
         return bool(self._L.bddmma_fused_small_learned(self._h))
+    def fused_small_history(self) -> bool:
+        """True when bdd_hip_batch.learned_iterations_history can run this solver's history steps (compute_history_for_itr > 0) inside
+        its workgroup as well"""
+        return bool(self._L.bddmma_fused_small_history(self._h))
 
     def nontemporal_loads(self) -> bool:
         """the solve sweeps run in the instantiation that loads potentials and staging tables non-temporally (footprint beyond the caches' reach)"""
@@ -639,16 +643,41 @@ class bdd_hip_batch:
         """learned_iterations(w_i, num_itr, omega, improvement_slope=0.0) — with omega_vec its omega_vec form — of every member i, one
         workgroup per member.  dist_weights / omega_vec: the members' REAL[nr_layers] one behind the other in the members' order (numpy
         arrays or device tensors, both of one kind).  Every member must be fused_small_learned().  include/bdd_mma.h:
-        bddmma_learned_iterations_batch."""
+        bddmma_learned_iterations_batch.  (With a history: learned_iterations_history.)"""
+        self.learned_iterations_history(dist_weights, num_itr, omega=omega, omega_vec=omega_vec)
+
+    def learned_iterations_history(self, dist_weights, num_itr, omega=0.5, omega_vec=None, compute_history_for_itr=0, history_avg_beta=0.9,
+                                   sol_avg=None, lb_first_diff_avg=None, lb_second_diff_avg=None):
+        """learned_iterations with the history of the per-solver method: the last min(num_itr, compute_history_for_itr) iterations also
+        update, in place, sol_avg (the members' REAL[nr_layers] one behind the other) and lb_first_diff_avg / lb_second_diff_avg (the
+        members' REAL[nr_bdds] one behind the other), inside the members' workgroups; all arrays of the call on the host or all on the
+        device.  Every member must be fused_small_history().  compute_history_for_itr == 0 is learned_iterations.  include/bdd_mma.h:
+        bddmma_learned_iterations_history_batch."""
+        s0 = self.solvers[0]
         n = sum(s.nr_layers() for s in self.solvers)
-        w, w_dev = self.solvers[0]._learned_buf(dist_weights, n, "dist_weights")
+        w, w_dev = s0._learned_buf(dist_weights, n, "dist_weights")
         ov = None
         if omega_vec is not None:
-            ov, ov_dev = self.solvers[0]._learned_buf(omega_vec, n, "omega_vec")
+            ov, ov_dev = s0._learned_buf(omega_vec, n, "omega_vec")
             if ov_dev != w_dev:
                 raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: dist_weights and omega_vec must both be on the host or "
                                        "both on the device")
-        self._check(self._L.bddmma_learned_iterations_batch(self._h, w, ov, float(omega), int(num_itr), w_dev), self._h)
+        if int(compute_history_for_itr) == 0:
+            self._check(self._L.bddmma_learned_iterations_batch(self._h, w, ov, float(omega), int(num_itr), w_dev), self._h)
+            return
+        nb = sum(s.nr_bdds() for s in self.solvers)
+        outs = []
+        for x, k, what in ((sol_avg, n, "sol_avg"), (lb_first_diff_avg, nb, "lb_first_diff_avg"), (lb_second_diff_avg, nb, "lb_second_diff_avg")):
+            if x is None:   # (the library refuses it: BDDMMA_ERR_INVALID_ARGUMENT, nothing touched)
+                outs.append(None)
+                continue
+            p, dev = s0._learned_buf(x, k, what)
+            if dev != w_dev:
+                raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: the arrays of a batch call must all be on the host or all "
+                                       "on the device")
+            outs.append(p)
+        self._check(self._L.bddmma_learned_iterations_history_batch(self._h, w, ov, float(omega), int(num_itr), *outs, int(compute_history_for_itr),
+                                                                     float(history_avg_beta), w_dev), self._h)
 
     def grad_iterations(self, dist_weights, grad_lo, grad_hi, grad_mm, omega=0.5, track_grad_after_itr=0, track_grad_for_num_itr=1, num_caches=1,
                         omega_vec=None, out=None):

@@ -182,6 +182,11 @@ int bddmma_fused_small(const bddmma_solver* s);
  * holds and the learned layout — the plain one plus an omega per layer — fits the CU's LDS as well.  With improvement_slope <= 0 the iterations that compute_history_for_itr does not reach then run fused; with a stopping rule
  * (improvement_slope > 0) every iteration keeps the four launches.  variant_flags bit 19 turns it off together with bddmma_fused_small. */
 int bddmma_fused_small_learned(const bddmma_solver* s);
+/* 1 when bddmma_learned_iterations_history_batch can also run the history step of a tracked iteration (the per-BDD bounds, every BDD's
+ * arg-min path and the moving averages) inside this solver's workgroup: bddmma_fused_small_learned holds and the solver has a thread per
+ * BDD.  The step needs no LDS of its own — its marks live in entries that are dead between a backward sweep and the next exchange — so today
+ * this is 1 wherever bddmma_fused_small_learned is. */
+int bddmma_fused_small_history(const bddmma_solver* s);
 /* 1 when the narrow packs' solve sweeps run in the instantiation that loads what a sweep reads once (potentials, staging tables) non-temporally. */
 int bddmma_nontemporal_loads(const bddmma_solver* s);
 /* 1 when the solve sweeps of bddmma_iteration / _iterations / _run_solver rebuild the costs-from-root and costs-to-terminal on chip instead of
@@ -486,6 +491,29 @@ int bddmma_batch_iterations(bddmma_batch* b, double omega, uint64_t n);
  * (Named after bddmma_learned_iterations, which it is for every member; the bddmma_batch_ prefix is kept for the batch object's own calls.) */
 int bddmma_learned_iterations_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec /* or NULL */, double omega,
                                     uint64_t num_itr, int on_device);
+/* bddmma_learned_iterations_batch with the history of bddmma_learned_iterations: for every member i,
+ * bddmma_learned_iterations(member i, w_i, .., num_itr, omega, 0.0, its part of sol_avg / lb_first_diff_avg / lb_second_diff_avg,
+ * compute_history_for_itr, history_avg_beta, .., NULL) — or its omega_vec form.  The last min(num_itr, compute_history_for_itr) iterations
+ * are tracked; the history step of a tracked iteration — the per-BDD bounds, the arg-min path of every BDD and the three moving averages —
+ * runs inside the member's workgroup behind the iteration's backward sweep (csrc/kernels/small.hpp, HISTORY), where the per-member call
+ * makes about fifteen launches per tracked iteration.  The iterations in front of the tracked ones run through the launches of
+ * bddmma_learned_iterations_batch.
+ * compute_history_for_itr == 0 IS bddmma_learned_iterations_batch; the three arrays may be NULL then.
+ * Arrays: dist_weights / omega_vec as there.  sol_avg: the members' REAL[nr_layers] in the public layer order, one behind the other in
+ * the members' order; lb_first_diff_avg / lb_second_diff_avg: the members' REAL[nr_bdds] in the order of bddmma_lower_bound_per_bdd, one
+ * behind the other.  An entry the history does not reach keeps its content (compute_history_for_itr == 1 leaves both per-BDD arrays alone,
+ * == 2 the second).  on_device is one flag for all arrays.  Host outputs pass through one staging buffer the batch owns with one host
+ * synchronisation; device outputs are written in the order of the batch's stream.
+ * Results: in float every result is bit-equal to the per-member call; in double bit-equal wherever no variable sits in more than two
+ * BDDs, elsewhere within the summation order of the exchange (sol_avg holds 0 / 1 decisions: it differs only where two path costs tie to
+ * within that rounding).  Every call starts its history afresh, as the per-member call does.
+ * Everything bddmma_learned_iterations_batch promises holds: its refusals, its ordering, the checks of the weights and of omega, the
+ * members' set-once initial bound change.  Added refusals: BDDMMA_ERR_INVALID_ARGUMENT for a NULL history array with
+ * compute_history_for_itr > 0; BDDMMA_ERR_UNSUPPORTED, naming the member, where bddmma_fused_small_history is 0.  Every refusal is decided
+ * before any member or output is touched. */
+int bddmma_learned_iterations_history_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec /* or NULL */, double omega,
+                                            uint64_t num_itr, void* sol_avg, void* lb_first_diff_avg, void* lb_second_diff_avg,
+                                            uint64_t compute_history_for_itr, double history_avg_beta, int on_device);
 /* bddmma_grad_learned_iterations(member i, its part of every array, ..) for every member i, with the same two iteration counts for all
  * members: ONE workgroup per member runs the whole call in one launch per kernel instantiation present — the tracked iterations once,
  * recording what their reverse reads, then the reverse (kernels/gradsmall.hpp) — where the per-member call issues about 25 launches and
