@@ -70,6 +70,7 @@ SIGNATURES = {
     "bddmma_fused_small_history": (_I, [_V]),
     "bddmma_nontemporal_loads": (_I, [_V]),
     "bddmma_potentials_on_chip": (_I, [_V]),
+    "bddmma_onchip_hops": (_I, [_V]),
     "bddmma_precision": (_I, [_V]),
     "bddmma_device": (_I, [_V]),
     "bddmma_num_bdds_per_var": (_I, [_V, _V]),

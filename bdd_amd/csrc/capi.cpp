@@ -159,6 +159,7 @@ int bddmma_fused_small_learned(const bddmma_solver* s) { return s && s->impl ? (
 int bddmma_fused_small_history(const bddmma_solver* s) { return s && s->impl ? (s->impl->fused_small_history ? 1 : 0) : -1; }
 int bddmma_nontemporal_loads(const bddmma_solver* s) { return s && s->impl ? (s->impl->nt_loads ? 1 : 0) : -1; }
 int bddmma_potentials_on_chip(const bddmma_solver* s) { return s && s->impl ? (s->impl->pot_on_chip ? 1 : 0) : -1; }
+int bddmma_onchip_hops(const bddmma_solver* s) { return s && s->impl ? s->impl->onchip_hops : -1; }
 int bddmma_precision(const bddmma_solver* s) { return s && s->impl ? s->impl->precision : -1; }
 int bddmma_device(const bddmma_solver* s) { return s && s->impl ? s->impl->device : -1; }
 uint64_t bddmma_device_bytes(const bddmma_solver* s) { return s && s->impl ? s->impl->dev_bytes : 0; }

@@ -14,19 +14,28 @@ namespace bddmma {
 // sweep moved for them stay on chip.
 // A pack of at most HC hops keeps the {lo, hi} of the lane's layer of EVERY hop in registers (L[HC], all loads issued at once behind the
 // header reads: they do not depend on the staging tables) and walks its records twice:
-//   forward:  upward first — (ta, tb) of the lane's layer from the children's entries of the two alternating sT buffers, read back as the
-//             slots (2 lane, 2 lane + 1) into T[h], the form k_fwd_narrow3 loads from memory — then k_fwd_narrow3's hop with c = L[h] and
-//             the copy of hop h + 2's T from T[h + 2];
+//   forward:  upward first, hops hops - 1 .. 0 — the four children's entries {lo a, hi a, lo b, hi b} of the lane's layer gathered from the
+//             sT buffer of hop h + 1 and KEPT, G[h]; for h >= 1 (ta, tb) of the layer formed from them and scattered into the other sT
+//             buffer.  Hop 0 only gathers: its children are hop 1's nodes, and nothing reads a T of hop 0 in a forward sweep.  Then
+//             k_fwd_narrow3's hop with c = L[h] and the children's T from G[h]: no LDS traffic for T in the second walk (round 14; before, T
+//             was read back in slot form into T[h], copied into the buffers again hop by hop and gathered a second time);
 //   backward: downward first — pushes of f + c with lds_min into alternating frontier buffers, the lane's (fa, fb) into F[h] — then
 //             k_bwd_narrow3's hop with F[h] in place of the loaded pair.  The frontier buffers ARE the sT buffers (the phases do not overlap;
 //             the sink constants are written after the first walk, whose pushes use the same entries as dummy targets).
 // The records are read again in the second walk (shared by a family's packs: L2 hits), two hops ahead of their use as in narrow3.
 // Same arithmetic in the same order as fwd_ / bwd_narrow3_body.  Packs with resident headers only (one stage group per pack, one staging
 // round per quad), <= HC hops, so one window of hop offsets serves the pack; float (the double form spills).  REBUILD_* = false loads that
-// potential from memory as before, STORE_* = false leaves it unwritten: <1, 0> / <1, 0> is the pair iteration() runs on packs of <= 10 hops.
-// The forward form holds L and T of every hop next to the hop's working set: 108 VGPRs at 10 hops, scratch from 12 hops on within the 128
-// of four waves per SIMD; the backward form fits at 16 (118).  Packs of 11-16 hops therefore keep k_fwd_narrow3 and run k_bwd_narrow4
-// <1, 1>: F on chip, T through memory.  The other pairs exist for the decomposition of NOTES round 10 (variant_flags bits 22, 23).
+// potential from memory as before, STORE_* = false leaves it unwritten: <1, 0> / <1, 0> is the pair iteration() runs on packs of <= 10 hops (HC = 10) and of 11-12 hops (HC = 12).
+// G[h] cannot differ from what the second walk used to gather: that walk read buffer (h + 1) & 1 through the record's offsets ra[0], ra[1],
+// and the buffer had been refilled with exactly the values the upward walk had computed into buffer (h + 1) & 1 and read there through the
+// same offsets; the sink entries and the dummy entries of idle lanes hold the same constants in both walks; additions and minima are untouched.
+// The forward form holds L and G of every hop next to the hop's working set: 114 VGPRs at 10 hops (<1, 0> and <1, 1>, 4 and 8 packs; 90 with T
+// loaded, <0, 0>), no scratch.  G takes 4 registers per hop where T[] took 2, but the read-back and re-scatter registers are gone: 12 hops
+// compile to 126 VGPRs without scratch (T[]: 24 spilled) and are the second capacity of the <1, 0> pair; 14 hops (40 B of scratch) and 16 still
+// spill within the 128 of four waves per SIMD.  The backward form fits at 16 (118).  Packs of 13-16 hops therefore keep k_fwd_narrow3 and
+// run k_bwd_narrow4 <1, 1>: F on chip, T through memory.  The other pairs exist for the decomposition of NOTES round 10 (variant_flags bits 22, 23).
+// The sT buffers are dead in the forward form's second walk; sF is not aliased onto them: the registers hold the kernel at four waves per
+// SIMD whatever the LDS says, and the alias would add an ordering hazard around the roots' initialisation.
 template <typename REAL, int WPB, int HC, bool REBUILD_T, bool STORE_F>
 __device__ __forceinline__ void fwd_narrow4_body(const DevPtrs<REAL>& d, const PackDev& pk, const uint32_t* __restrict__ lrec,
                                                  const uint32_t* __restrict__ lrec_off, uint32_t lrec_words, REAL omega, uint32_t block_id)
@@ -72,13 +81,19 @@ __device__ __forceinline__ void fwd_narrow4_body(const DevPtrs<REAL>& d, const P
     uint32_t o[HC + 4];   // first slot of hops 0 .. HC + 3 of the pack (past the last hop: the pack's end)
     uint32_t lb[HC + 1];  // first layer of hops 0 .. HC
     P2 L[HC];             // {lo, hi} of the lane's layer in every hop
-    P2 T[HC + 2];         // costs-from-terminal of every hop, slots (2 lane, 2 lane + 1)
+    P2 T[HC + 2];         // !REBUILD_T: costs-from-terminal of every hop, slots (2 lane, 2 lane + 1)
+    REAL G[HC][4];        // REBUILD_T: costs-from-terminal at the four children {lo a, hi a, lo b, hi b} of the lane's layer in every hop
 #pragma unroll
     for (int i = 0; i < HC + 4; ++i) o[i] = 0;
 #pragma unroll
     for (int i = 0; i < HC + 1; ++i) lb[i] = 0;
+    if constexpr (REBUILD_T) {
 #pragma unroll
-    for (int i = 0; i < HC + 2; ++i) T[i] = P2{REAL(0), REAL(0)};
+        for (int i = 0; i < HC; ++i) G[i][0] = G[i][1] = G[i][2] = G[i][3] = REAL(0);
+    } else {
+#pragma unroll
+        for (int i = 0; i < HC + 2; ++i) T[i] = P2{REAL(0), REAL(0)};
+    }
     auto ldrec = [&](uint32_t h) { return __builtin_amdgcn_raw_buffer_load_b128(rr, (uint32_t)lane * 16u, (rbase + h * 64u) * 16u, 0); };
     const uint32_t sink = (W + 2 * (uint32_t)lane) * S;  // this lane's TOP entry; BOT follows it
     u4v rA = u4v{0u, 0u, 0u, 0u}, rB = rA;               // records of the next two hops of the walk under way
@@ -109,29 +124,32 @@ __device__ __forceinline__ void fwd_narrow4_body(const DevPtrs<REAL>& d, const P
         }
         wave_sync();
         if constexpr (REBUILD_T) {
-            // ---- upward walk: T of hops hops - 1 .. 1 (hop 0's is not read by a forward sweep)
+            // ---- upward walk: the children's T of hops hops - 1 .. 0 into G, T of hops hops - 1 .. 1 into the buffers on the way (hop 0's
+            // own T is not read by a forward sweep: its step only gathers)
             rA = ldrec(hops - 1);
             rB = ldrec(hops >= 2 ? hops - 2 : 0);
 #pragma unroll
-            for (int h = HC - 1; h >= 1; --h) {
+            for (int h = HC - 1; h >= 0; --h) {
                 if ((uint32_t)h < hops) {  // uniform
                     const u4v ra = rA;
                     rA = rB;
                     rB = ldrec(h >= 2 ? h - 2 : 0);
                     const uint32_t tc = ((h + 1) & 1) * BUF, tn = (h & 1) * BUF;
-                    const P2 c = L[h];
-                    const uint32_t flags = ra[2] >> 16;
                     const REAL tla = lds_ld<REAL>(sTw, tc + (ra[0] & 0xFFFFu)), tha = lds_ld<REAL>(sTw, tc + (ra[0] >> 16));
                     const REAL tlb = lds_ld<REAL>(sTw, tc + (ra[1] & 0xFFFFu)), thb = lds_ld<REAL>(sTw, tc + (ra[1] >> 16));
-                    const REAL ta = rmin(c.y + tha, c.x + tla);
-                    const REAL tb = rmin(c.y + thb, c.x + tlb);
-                    if (flags & LREC_REAL) lds_st<REAL>(sTw, tn + (ra[2] & 0xFFFFu), ta);
-                    if (flags & LREC_TWO) lds_st<REAL>(sTw, tn + (ra[2] & 0xFFFFu) + S, tb);
-                    wave_sync();
-                    T[h] = lds_ld<P2>(sTw, tn + 2u * (uint32_t)lane * S);
+                    G[h][0] = tla, G[h][1] = tha, G[h][2] = tlb, G[h][3] = thb;
+                    if (h >= 1) {
+                        const P2 c = L[h];
+                        const uint32_t flags = ra[2] >> 16;
+                        const REAL ta = rmin(c.y + tha, c.x + tla);
+                        const REAL tb = rmin(c.y + thb, c.x + tlb);
+                        if (flags & LREC_REAL) lds_st<REAL>(sTw, tn + (ra[2] & 0xFFFFu), ta);
+                        if (flags & LREC_TWO) lds_st<REAL>(sTw, tn + (ra[2] & 0xFFFFu) + S, tb);
+                        wave_sync();
+                    }
                 }
             }
-            // (buffer 1 now holds T of hop 1 and buffer 0 that of hop 2: what the first hop below expects)
+            BDDMMA_STAMP(p, 5);
         } else {
             if (2u * (uint32_t)lane < o[2] - o[1]) lds_st<P2>(sTw, BUF + 2u * (uint32_t)lane * S, T[1]);
         }
@@ -148,18 +166,23 @@ __device__ __forceinline__ void fwd_narrow4_body(const DevPtrs<REAL>& d, const P
             const u4v ra = rA;
             rA = rB;
             rB = ldrec(h + 2);
-            const uint32_t fc = (h & 1) * BUF, fn = ((h + 1) & 1) * BUF;  // frontier of this / the next hop; T of the next hop lies in fn, of hop h + 2 in fc
+            const uint32_t fc = (h & 1) * BUF, fn = ((h + 1) & 1) * BUF;  // frontier of this / the next hop; !REBUILD_T: T of the next hop lies in fn, of hop h + 2 in fc
             const uint32_t stg = db + (lb[h] + (uint32_t)lane) * (uint32_t)sizeof(P2);  // the lane's layer inside the wave's staging slots
             const P2 c = L[h];
             // ---- the hop's LDS reads, one batch
             const uint32_t flags = ra[2] >> 16;
             REAL fa, fb;
             lds_ld2(fa, fb, sFw, fc + (ra[2] & 0xFFFFu));
-            const REAL tla = lds_ld<REAL>(sTw, fn + (ra[0] & 0xFFFFu)), tha = lds_ld<REAL>(sTw, fn + (ra[0] >> 16));
-            const REAL tlb = lds_ld<REAL>(sTw, fn + (ra[1] & 0xFFFFu)), thb = lds_ld<REAL>(sTw, fn + (ra[1] >> 16));
+            REAL tla, tha, tlb, thb;
+            if constexpr (REBUILD_T) {
+                tla = G[h][0], tha = G[h][1], tlb = G[h][2], thb = G[h][3];  // what the upward walk read through these very offsets
+            } else {
+                tla = lds_ld<REAL>(sTw, fn + (ra[0] & 0xFFFFu)), tha = lds_ld<REAL>(sTw, fn + (ra[0] >> 16));
+                tlb = lds_ld<REAL>(sTw, fn + (ra[1] & 0xFFFFu)), thb = lds_ld<REAL>(sTw, fn + (ra[1] >> 16));
+            }
             const P2 dd = lds_ld<P2>(dyn_lds, stg);
             // ---- set-up of the next hop's buffers (nothing above depends on it)
-            if (!(REBUILD_T && h == 0))  // (the upward walk left hop 2's T where hop 0 would put it)
+            if constexpr (!REBUILD_T)
                 if (2u * (uint32_t)lane < o[h + 3] - o[h + 2]) lds_st<P2>(sTw, fc + 2u * (uint32_t)lane * S, T[h + 2]);
             lds_st<P2>(sFw, fn + 2u * (uint32_t)lane * S, P2{INF, INF});
             wave_sync();

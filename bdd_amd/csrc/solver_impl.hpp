@@ -598,13 +598,14 @@ struct SolverT final : SolverBase {
 #endif
         nt_loads = n3_nt || n12_nt;
         // The solve sweeps of iteration() with F and T rebuilt in registers (kernels/narrow4.hpp): third-generation packs that start from the
-        // resident headers and have at most 16 hops, float (the double form spills).  The smallest capacity that holds the longest pack.
+        // resident headers and have at most 16 hops, float (the double form spills).  The smallest capacity that holds the longest pack
+        // (bddmma_onchip_hops): 10 or 12 hops with both potentials on chip, 16 with F alone (the forward form spills beyond 12).
         // variant_flags bit 21: off (the tests' twin); bits 22 / 23: only T / only F on chip, where that pair is built (4 packs, 10 hops).
         if constexpr (sizeof(REAL) == 4) {
             if (use_narrow3 && res_hdr_ok && !n3_nt && !(opts && (opts->variant_flags & 0x200000u))) {
                 uint32_t max_hops = 0;
                 for (uint32_t p = 0; p < nb_.n_packs; ++p) max_hops = std::max(max_hops, L.res.pack_hdr[8 * (size_t)p + 5] & 0xFFFFu);
-                onchip_hc = max_hops <= 10 ? 10 : max_hops <= 16 ? 16 : 0;
+                onchip_hc = max_hops <= 10 ? 10 : max_hops <= 12 ? 12 : max_hops <= 16 ? 16 : 0;  // 10, 12: both on chip; 16: F only (mode 3)
                 const uint32_t part = opts ? (opts->variant_flags >> 22) & 3u : 0u;
                 if (onchip_hc == 16) onchip_mode = 3;
                 if (part == 1 || part == 2) {
@@ -612,6 +613,7 @@ struct SolverT final : SolverBase {
                     else onchip_hc = 0;
                 }
                 pot_on_chip = onchip_hc != 0;
+                onchip_hops = onchip_hc;
             }
         }
         if (wb_.n_packs) {
@@ -860,13 +862,18 @@ struct SolverT final : SolverBase {
         }
         return s;
     }
-    // k_fwd_narrow4 / k_bwd_narrow4 (float): the pair that keeps both potentials on chip for 4 / 8 packs per workgroup of <= 10 hops; the
-    // backward kernel that rebuilds F and stores T for packs of <= 16 hops (the forward form does not fit its registers there: the third
-    // generation's forward sweep stays); the pairs that keep one potential (variant_flags bits 22, 23: the decomposition of NOTES round 10)
-    // for the headline's 4 packs and 10 hops
+    // k_fwd_narrow4 / k_bwd_narrow4 (float): the pair that keeps both potentials on chip for 4 / 8 packs per workgroup of <= 10 and of <= 12
+    // hops; the backward kernel that rebuilds F and stores T for packs of <= 16 hops (the forward form, which keeps the four gathered child
+    // potentials of every hop in registers, fits 12 hops at 126 VGPRs but spills at 14 and 16: there the third generation's forward sweep
+    // stays); the pairs that keep one potential (variant_flags bits 22, 23: the decomposition of NOTES round 10) for the
+    // headline's 4 packs and 10 hops
     RecFn onchip_fn(bool bwd, bool rebuild, bool store) const
     {
         if (onchip_hc == 16) return pick<4, 8>(wpb, [&](auto W) -> RecFn { return &k_bwd_narrow4<REAL, W.value, 16, true, true>; });
+        if (onchip_hc == 12)
+            return pick<4, 8>(wpb, [&](auto W) -> RecFn {
+                return bwd ? &k_bwd_narrow4<REAL, W.value, 12, true, false> : &k_fwd_narrow4<REAL, W.value, 12, true, false>;
+            });
         if (rebuild && !store)
             return pick<4, 8>(wpb, [&](auto W) -> RecFn {
                 return bwd ? &k_bwd_narrow4<REAL, W.value, 10, true, false> : &k_fwd_narrow4<REAL, W.value, 10, true, false>;
@@ -2196,6 +2203,11 @@ struct SolverT final : SolverBase {
         if (kind >= 13 && kind <= 17) return gi_time_kernel(kind, reps, ms);
         int rc = BDDMMA_OK;
         auto once = [&]() -> int {
+#ifdef BDDMMA_STAMPS
+            // BDDMMA_STAMPS_ONCHIP: kinds 2 / 3 launch the solve sweeps iteration() runs (kernels/narrow4.hpp) instead of the third generation's
+            if ((kind == 2 || kind == 3) && onchip_hc && std::getenv("BDDMMA_STAMPS_ONCHIP"))
+                return launch_sweep(kind == 3, kern.onchip[kind - 2], d_delta_lay, REAL(0.5), BDDMMA_K_OTHER);
+#endif
             switch (kind) {
                 case 0: return launch_fwd(FWD_PLAIN, nullptr, REAL(0), BDDMMA_K_OTHER);
                 case 1: return launch_bwd(BWD_PLAIN, nullptr, REAL(0), BDDMMA_K_OTHER);
@@ -2248,7 +2260,7 @@ struct SolverT final : SolverBase {
             if (FILE* f2 = std::fopen((std::string(path) + "." + std::to_string(kind)).c_str(), "w")) {
                 for (size_t sl = 0; sl < slots; ++sl)
                     if (h[sl * 8] != 0)
-                        std::fprintf(f2, "%zu %llu %llu %llu %llu %llu\n", sl, h[sl * 8], h[sl * 8 + 1], h[sl * 8 + 2], h[sl * 8 + 3], h[sl * 8 + 4]);
+                        std::fprintf(f2, "%zu %llu %llu %llu %llu %llu %llu\n", sl, h[sl * 8], h[sl * 8 + 1], h[sl * 8 + 2], h[sl * 8 + 3], h[sl * 8 + 4], h[sl * 8 + 5]);
                 std::fclose(f2);
             }
             if (rc) return rc;

@@ -107,6 +107,10 @@ class bdd_hip_parallel_mma:
     def potentials_on_chip(self) -> bool:
         """the solve sweeps of iteration() / iterations() / run_solver rebuild F and T on chip instead of storing and reloading them"""
         return bool(self._L.bddmma_potentials_on_chip(self._h))
+
+    def onchip_hops(self) -> int:
+        """hop capacity of the kernels behind potentials_on_chip(): 0 (off), 10 or 12 (F and T on chip), 16 (F on chip, T through memory)"""
+        return int(self._L.bddmma_onchip_hops(self._h))
     def device(self) -> int:
         """index of the GPU the solver lives on"""
         return int(self._L.bddmma_device(self._h))

@@ -192,6 +192,10 @@ int bddmma_nontemporal_loads(const bddmma_solver* s);
 /* 1 when the solve sweeps of bddmma_iteration / _iterations / _run_solver rebuild the costs-from-root and costs-to-terminal on chip instead of
  * storing and reloading them (csrc/kernels/narrow4.hpp; variant_flags bit 21 turns it off).  bddmma_solve_sweep_kind stays STREAMING3. */
 int bddmma_potentials_on_chip(const bddmma_solver* s);
+/* The hop capacity of the kernels behind bddmma_potentials_on_chip, the smallest that holds the solver's longest pack: 0 (not on chip), 10 or
+ * 12 (both potentials on chip: k_fwd_narrow4 with k_bwd_narrow4), 16 (the costs-from-root on chip, the costs-to-terminal through memory:
+ * k_fwd_narrow3 with k_bwd_narrow4). */
+int bddmma_onchip_hops(const bddmma_solver* s);
 int bddmma_precision(const bddmma_solver* s);
 int bddmma_device(const bddmma_solver* s);
 /* nr_bdds(var): int32[nr_variables] (get_num_bdds_per_var, bdd_cuda_base.h:166) */
