@@ -5,8 +5,10 @@ semantics are those of the reference's torch layer (src/bdd_cuda_torch/bdd_cuda_
 mirrors); the differences are the ones include/bdd_mma.h has from the reference's solver classes and are listed here.
 
 Conventions of every function
-  solvers     a list of bdd_hip_parallel_mma of one precision on one device, or a bdd_hip_batch: its members in order.  (Only
-              DualIterations — forward and backward — does anything else with a batch than with the list of its members.)
+  solvers     a list of bdd_hip_parallel_mma of one precision on one device, or a bdd_hip_batch: its members in order.  (The chain of
+              a training step's loss — DualIterations, DistributeDeferredDelta and ComputeLowerBoundperBDD, forward and backward —
+              makes batch calls on a batch, with the results of the list form; every other function does with a batch what it does
+              with the list of its members.)
   tensors     1-D, contiguous, on the solvers' device, of the solvers' precision (torch.float32 / torch.float64 — the reference asks for
               torch's default dtype instead).  A batch tensor is the concatenation over the solvers, in list order, of each solver's array:
                 per layer     nr_layers() values in the public layer order (get_solver_costs, get_primal_variable_index) — there are
@@ -27,7 +29,8 @@ Conventions of every function
               overwritten while a handle still reads it.  Use the same current stream for a Function's forward and for what consumes
               its outputs, as with any torch operator.  DualIterations' two batched paths make batch calls only, which run on the
               batch's own stream and order themselves against every member's: there the one pair is the batch's (bdd_hip_batch.stream_wait
-              / stream_signal) instead of a pair per member.
+              / stream_signal) instead of a pair per member.  The same holds for the batched forms of DistributeDeferredDelta and
+              ComputeLowerBoundperBDD.
 Every backward is once_differentiable, takes a missing incoming gradient (None) as zeros and runs on the stream that is current
 when autograd calls it.
 """
@@ -39,6 +42,7 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
+from . import capi
 from .solver import bdd_hip_batch
 
 __all__ = ["batch_index", "BatchIndex", "DualIterations", "DistributeDeferredDelta", "ComputeAllMinMarginalsDiff", "PerturbPrimalCosts",
@@ -137,6 +141,19 @@ class _Ordered:
         for s in self.solvers:
             s.stream_signal(self.stream)
         return False
+
+
+def _batch_set_costs(batch, lo, hi, mm):
+    """the first call of a batched tail (DistributeDeferredDelta, ComputeLowerBoundperBDD): batch.set_solver_costs.  False when the batch
+    refuses it with BDDMMA_ERR_STATE — a member that has (had) an L-BFGS wrapper, for instance, with which the list form works; the
+    refusal has touched nothing, so the caller runs the list form instead."""
+    try:
+        batch.set_solver_costs(lo, hi, mm)
+    except capi.BddMmaError as e:
+        if str(e).startswith(f"bdd_mma error {capi.ERR_STATE}:"):
+            return False
+        raise
+    return True
 
 
 def _incoming(g, like):
@@ -312,6 +329,10 @@ class DualIterations(torch.autograd.Function):
 class DistributeDeferredDelta(torch.autograd.Function):
     """bdd_cuda_torch.py:184-232.  apply(solvers, lo_costs_batch, hi_costs_batch, def_mm_batch) -> (lo, hi): distribute_delta on every solver.
 
+    forward   for a bdd_hip_batch three batch calls and none on a member: ONE batch.set_solver_costs, ONE batch.distribute_delta and ONE
+              batch.get_solver_costs, with the list form's results bit for bit.  The list form runs for a list, and for a batch whose
+              first call refuses with BDDMMA_ERR_STATE.
+
     backward  grad_lo and grad_hi pass through (identity Jacobian) and grad_def_mm = where(def_mm > 0, grad_hi, -grad_lo), formed from
               the saved tensor.  That is what bddmma_grad_distribute_delta computes, but that call reads whatever distribute_delta last
               ran on the handle, and another Function may have used the solver between this forward and this backward.  No solver is
@@ -323,7 +344,16 @@ class DistributeDeferredDelta(torch.autograd.Function):
         z.check(("lo_costs_batch", lo_costs_batch, z.layers), ("hi_costs_batch", hi_costs_batch, z.layers), ("def_mm_batch", def_mm_batch, z.layers))
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(def_mm_batch)
-        lo, hi, rest = (torch.empty_like(lo_costs_batch) for _ in range(3))
+        lo, hi = (torch.empty_like(lo_costs_batch) for _ in range(2))
+        if z.batch is not None:
+            with _Ordered([z.batch]):   # batch calls only: each orders itself against the members' streams
+                batched = _batch_set_costs(z.batch, lo_costs_batch, hi_costs_batch, def_mm_batch)
+                if batched:
+                    z.batch.distribute_delta()
+                    z.batch.get_solver_costs(out=(lo, hi, None))
+            if batched:
+                return lo, hi
+        rest = torch.empty_like(lo_costs_batch)
         with _Ordered(z.solvers):
             for s, l in zip(z.solvers, z.slices(z.layers)):
                 s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], def_mm_batch[l])
@@ -418,7 +448,11 @@ class ComputeLowerBoundperBDD(torch.autograd.Function):
     """bdd_cuda_torch.py:339-401.  apply(solvers, lo_costs_batch, hi_costs_batch, smooth_gradients_temp=0.0) -> lower_bound_per_bdd, a per-BDD
     batch tensor; deferred differences zero.
 
-    backward  smooth_gradients_temp <= 0: bddmma_grad_lower_bound_per_bdd (the arg-min path of every BDD; state contract of
+    forward   for a bdd_hip_batch ONE batch.set_solver_costs and ONE batch.lower_bound_per_bdd, none on a member, with the list form's
+              results bit for bit.  The list form runs for a list, and for a batch whose first call refuses with BDDMMA_ERR_STATE.
+    backward  for a bdd_hip_batch with smooth_gradients_temp <= 0 likewise ONE batch.set_solver_costs and ONE
+              batch.grad_lower_bound_per_bdd (bddmma_grad_lower_bound_per_bdd_batch: one workgroup per member).  Otherwise, per solver,
+              smooth_gradients_temp <= 0: bddmma_grad_lower_bound_per_bdd (the arg-min path of every BDD; state contract of
               bddmma_bdds_solution).  > 0: the smooth variant on the saved costs divided by the temperature — as in the reference the
               scaling applies to the backward only, the forward value is the plain bound (state contract of bddmma_sum_marginals: both
               sweep states invalid and the cached bound dropped afterwards).  Neither changes arc costs, deferred differences or delta
@@ -432,6 +466,13 @@ class ComputeLowerBoundperBDD(torch.autograd.Function):
         ctx.save_for_backward(lo_costs_batch, hi_costs_batch)
         ctx.sizes, ctx.temp = z, float(smooth_gradients_temp)
         lb = torch.empty(z.bdds[-1], dtype=z.dtype, device=lo_costs_batch.device)
+        if z.batch is not None:
+            with _Ordered([z.batch]):
+                batched = _batch_set_costs(z.batch, lo_costs_batch, hi_costs_batch, zero)
+                if batched:
+                    z.batch.lower_bound_per_bdd(out=lb)
+            if batched:
+                return lb
         with _Ordered(z.solvers):
             for s, l, b in zip(z.solvers, z.slices(z.layers), z.slices(z.bdds)):
                 s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], zero[l])
@@ -450,6 +491,13 @@ class ComputeLowerBoundperBDD(torch.autograd.Function):
             lo_costs_batch, hi_costs_batch = lo_costs_batch / ctx.temp, hi_costs_batch / ctx.temp
         zero = torch.zeros_like(lo_costs_batch)
         g_lo, g_hi = torch.empty_like(lo_costs_batch), torch.empty_like(hi_costs_batch)
+        if z.batch is not None and not smooth:
+            with _Ordered([z.batch]):
+                batched = _batch_set_costs(z.batch, lo_costs_batch, hi_costs_batch, zero)
+                if batched:
+                    z.batch.grad_lower_bound_per_bdd(g, out=(g_lo, g_hi))
+            if batched:
+                return None, g_lo, g_hi, None
         with _Ordered(z.solvers):
             for s, l, b in zip(z.solvers, z.slices(z.layers), z.slices(z.bdds)):
                 s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], zero[l])

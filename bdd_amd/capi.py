@@ -132,6 +132,9 @@ SIGNATURES = {
     "bddmma_get_solver_costs_batch": (_I, [_V, _V, _V, _V, _I]),
     "bddmma_stream_wait_batch": (_I, [_V, _V]),
     "bddmma_stream_signal_batch": (_I, [_V, _V]),
+    "bddmma_lower_bound_per_bdd_batch": (_I, [_V, _V, _I]),
+    "bddmma_grad_lower_bound_per_bdd_batch": (_I, [_V, _V, _V, _V, _I]),
+    "bddmma_distribute_delta_batch": (_I, [_V]),
     "bddmma_batch_time_iterations": (_I, [_V, _D, _U64, C.POINTER(_D)]),
     "bddmma_batch_run_solver": (_I, [_V, _U64, _D, _D, _D, C.POINTER(RunResult)]),
     "bddmma_batch_lower_bounds": (_I, [_V, C.POINTER(_D)]),

@@ -538,6 +538,28 @@ class bdd_hip_batch {
         check(bddmma_get_solver_costs_batch(b_, std::get<0>(c).data(), std::get<1>(c).data(), std::get<2>(c).data(), 0));
         return c;
     }
+    // lower_bound_per_bdd / grad_lower_bound_per_bdd (the arg-min path's, not the smooth one) / distribute_delta of every member in one launch
+    // per kernel instantiation present: per-BDD arrays are the members' REAL[nr_bdds], layer arrays the members' REAL[nr_layers], one behind
+    // the other in the members' order.  Device pointers (the host does not wait) or host vectors.  Contract:
+    // bddmma_lower_bound_per_bdd_batch, bddmma_grad_lower_bound_per_bdd_batch, bddmma_distribute_delta_batch.
+    void lower_bound_per_bdd(REAL* dev_lb_per_bdd) { check(bddmma_lower_bound_per_bdd_batch(b_, dev_lb_per_bdd, 1)); }
+    std::vector<REAL> lower_bound_per_bdd_host(const size_t total_bdds)
+    {
+        std::vector<REAL> lb(total_bdds);
+        check(bddmma_lower_bound_per_bdd_batch(b_, lb.data(), 0));
+        return lb;
+    }
+    void grad_lower_bound_per_bdd(const REAL* dev_grad_lb_per_bdd, REAL* dev_grad_lo_out, REAL* dev_grad_hi_out)
+    {
+        check(bddmma_grad_lower_bound_per_bdd_batch(b_, dev_grad_lb_per_bdd, dev_grad_lo_out, dev_grad_hi_out, 1));
+    }
+    std::pair<std::vector<REAL>, std::vector<REAL>> grad_lower_bound_per_bdd(const std::vector<REAL>& grad_lb_per_bdd, const size_t total_layers)
+    {
+        std::vector<REAL> lo(total_layers), hi(total_layers);
+        check(bddmma_grad_lower_bound_per_bdd_batch(b_, grad_lb_per_bdd.data(), lo.data(), hi.data(), 0));
+        return {std::move(lo), std::move(hi)};
+    }
+    void distribute_delta() { check(bddmma_distribute_delta_batch(b_)); }
     // stream_wait — the batch's later calls start after everything queued on `hip_stream` so far; stream_signal — the reverse
     // (bddmma_stream_wait_batch / bddmma_stream_signal_batch)
     void stream_wait(void* hip_stream) { check(bddmma_stream_wait_batch(b_, hip_stream)); }

@@ -477,6 +477,21 @@ int bddmma_get_solver_costs_batch(bddmma_batch* b, void* lo, void* hi, void* mm,
 }
 int bddmma_stream_wait_batch(bddmma_batch* b, void* hip_stream) { return guarded_batch(b, [&](BatchBase* i) { return i->stream_wait((hipStream_t)hip_stream); }); }
 int bddmma_stream_signal_batch(bddmma_batch* b, void* hip_stream) { return guarded_batch(b, [&](BatchBase* i) { return i->stream_signal((hipStream_t)hip_stream); }); }
+int bddmma_lower_bound_per_bdd_batch(bddmma_batch* b, void* out, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!out) { i->err = "batch lower_bound_per_bdd: null output pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        return i->lower_bound_per_bdd(out, on_device);
+    });
+}
+int bddmma_grad_lower_bound_per_bdd_batch(bddmma_batch* b, const void* grad_lb_per_bdd, void* grad_lo_out, void* grad_hi_out, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!grad_lb_per_bdd || !grad_lo_out || !grad_hi_out) { i->err = "batch grad_lower_bound_per_bdd: null pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        return i->grad_lower_bound_per_bdd(grad_lb_per_bdd, grad_lo_out, grad_hi_out, on_device);
+    });
+}
+int bddmma_distribute_delta_batch(bddmma_batch* b) { return guarded_batch(b, [&](BatchBase* i) { return i->distribute_delta(); }); }
 int bddmma_batch_time_iterations(bddmma_batch* b, double omega, uint64_t n, double* ms)
 {
     return guarded_batch(b, [&](BatchBase* i) {

@@ -195,6 +195,12 @@ struct BatchBase {
     // kernel instantiation present; the arrays as in learned_iterations, each may be null (include/bdd_mma.h: bddmma_set_solver_costs_batch)
     virtual int set_solver_costs(const void* lo, const void* hi, const void* mm, int on_device) = 0;
     virtual int get_solver_costs(void* lo, void* hi, void* mm, int on_device) = 0;
+    // SolverBase::lower_bound_per_bdd / grad_lower_bound_per_bdd (smooth = 0) / distribute_delta of every member, one launch per kernel
+    // instantiation present (kernels/batchbound.hpp); per-BDD arrays: the members' REAL[nr_bdds] one behind the other, layer arrays as in
+    // learned_iterations (include/bdd_mma.h: bddmma_lower_bound_per_bdd_batch, bddmma_grad_lower_bound_per_bdd_batch, bddmma_distribute_delta_batch)
+    virtual int lower_bound_per_bdd(void* out, int on_device) = 0;
+    virtual int grad_lower_bound_per_bdd(const void* grad_lb, void* grad_lo, void* grad_hi, int on_device) = 0;
+    virtual int distribute_delta() = 0;
     // the batch stream behind everything queued on `other` so far / the reverse, by an event the batch owns; the host does not wait
     virtual int stream_wait(hipStream_t other) = 0;
     virtual int stream_signal(hipStream_t other) = 0;

@@ -8,6 +8,7 @@
 #include "solver_impl.hpp"
 #include "kernels/gradsmall.hpp"
 #include "kernels/batchcosts.hpp"
+#include "kernels/batchbound.hpp"
 #include "kernels/smallhist.hpp"
 
 namespace bddmma {
@@ -43,7 +44,7 @@ struct BatchT final : BatchBase {
         for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1, ev_order})
             if (e) (void)hipEventDestroy(e);
         if (d_items) (void)hipFree(d_items);
-        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage})
+        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad})
             if (q) (void)hipFree(q);
         if (d_ctl) (void)hipFree(d_ctl);
         if (h_ctl) (void)hipHostFree(h_ctl);
@@ -806,6 +807,175 @@ struct BatchT final : BatchBase {
         }
         const int rc2 = join_out();
         if (e != hipSuccess) { err = std::string("batch get_solver_costs: ") + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        return rc2;
+    }
+    // ---- the tail of the loss, all members at once (kernels/batchbound.hpp: k_small_bounds_batch, k_small_grad_lb_batch,
+    // k_small_distribute_batch; the kernels compile in solver_bb_f32.hip / _f64.hip).  Items sorted by the members' wave count, as the cost
+    // items are: the gradient kernel is one launch per wave count present, the other two one launch for all.  Host arrays pass through one
+    // staging buffer the batch owns (per-BDD values | lo | hi); it, the check word and a member's d_mm_consumed are allocated before any
+    // member is touched.
+    struct BbGroup {
+        BoundGradFn<REAL> fn;
+        uint32_t threads, lds, first, count;
+    };
+    std::vector<BbGroup> bb_groups;
+    std::vector<BoundItem<REAL>> bb_items;     // host copy, in launch order
+    std::vector<uint32_t> bb_ord;              // item j is member bb_ord[j]
+    BoundItem<REAL>* d_bb_items = nullptr;
+    REAL* d_bb_stage = nullptr;
+    uint32_t* d_bb_bad = nullptr;
+    uint64_t bb_layers = 0, bb_bdds = 0;       // values of all members' layers / BDDs
+    bool bb_ready = false, bb_dist_ready = false;
+
+    // dist: the call is distribute_delta, whose items need every member's d_mm_consumed; host_arrays: the call needs the staging buffer
+    int bb_prepare(bool dist, bool host_arrays)
+    {
+        const uint32_t n = (uint32_t)m.size();
+        if (!bb_ready) {
+            std::vector<uint32_t> ord(n);
+            for (uint32_t i = 0; i < n; ++i) ord[i] = i;
+            std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return m[a]->small_nw < m[b]->small_nw; });
+            std::vector<uint64_t> src(n), src_b(n);
+            uint64_t total = 0, total_b = 0;
+            for (uint32_t i = 0; i < n; ++i) {
+                src[i] = total;
+                src_b[i] = total_b;
+                total += m[i]->n_layers;
+                total_b += m[i]->n_bdds;
+            }
+            if (total > 0xFFFFFFFFull || total_b > 0xFFFFFFFFull) { err = "batch bounds: too many layers"; return BDDMMA_ERR_UNSUPPORTED; }
+            std::vector<BoundItem<REAL>> items(n);
+            std::vector<BbGroup> groups_;
+            for (uint32_t j = 0; j < n; ++j) {
+                const S* s = m[ord[j]];
+                const SmallDev& sm = s->small;
+                items[j] = BoundItem<REAL>{sm.pack_hdr, sm.rec, sm.rec_off, s->d_lpos, s->d_root_slot, s->d_bdd, s->d_T, s->d_lohi, s->d_mm_binned, s->d_mm_consumed,
+                                           s->d_delta_var, s->d_delta_lay, sm.rec_words, sm.ns, sm.nl, sm.n_packs, (uint32_t)s->n_layers, (uint32_t)s->n_bdds,
+                                           (uint32_t)s->n_vars, (uint32_t)src[ord[j]], (uint32_t)src_b[ord[j]], ord[j]};
+                if (groups_.empty() || s->small_nw != m[ord[groups_.back().first]]->small_nw)
+                    groups_.push_back(BbGroup{bound_grad_fn<REAL>(s->small_nw), 64u * (uint32_t)s->small_nw, 0u, j, 0u});
+                BbGroup& g = groups_.back();
+                g.lds = std::max(g.lds, sm.n_packs * bound_region_bytes((uint32_t)sizeof(REAL), sm.ns, sm.nl));
+                ++g.count;
+            }
+            for (const BbGroup& g : groups_) {
+                if (g.lds > m[0]->lds_cu) { err = "batch grad_lower_bound_per_bdd: the packs' state does not fit the LDS"; return BDDMMA_ERR_UNSUPPORTED; }
+                if (int rc = raise_lds_limit(reinterpret_cast<const void*>(g.fn), g.lds)) return rc;
+            }
+            if (!d_bb_items) HIPCHK(hipMalloc((void**)&d_bb_items, n * sizeof(BoundItem<REAL>)));
+            if (!d_bb_bad) HIPCHK(hipMalloc((void**)&d_bb_bad, sizeof(uint32_t)));
+            HIPCHK(hipMemcpy(d_bb_items, items.data(), n * sizeof(BoundItem<REAL>), hipMemcpyHostToDevice));
+            bb_items = std::move(items);
+            bb_ord = std::move(ord);
+            bb_groups = std::move(groups_);
+            bb_layers = total;
+            bb_bdds = total_b;
+            bb_ready = true;
+        }
+        if (dist && !bb_dist_ready) {
+            for (S* s : m)
+                if (!s->d_mm_consumed)
+                    if (int rc = s->dalloc(&s->d_mm_consumed, s->n_layers)) { err = s->err; return rc; }
+            for (uint32_t j = 0; j < n; ++j) bb_items[j].mm_consumed = m[bb_ord[j]]->d_mm_consumed;
+            HIPCHK(hipStreamSynchronize(stream));   // nothing in flight reads the items
+            HIPCHK(hipMemcpy(d_bb_items, bb_items.data(), n * sizeof(BoundItem<REAL>), hipMemcpyHostToDevice));
+            bb_dist_ready = true;
+        }
+        if (host_arrays && !d_bb_stage) HIPCHK(hipMalloc((void**)&d_bb_stage, std::max<uint64_t>(bb_bdds + 2 * bb_layers, 1) * sizeof(REAL)));
+        return BDDMMA_OK;
+    }
+    int lower_bound_per_bdd(void* out, int on_dev) override
+    {
+        int rc;
+        if (!out) { err = "batch lower_bound_per_bdd: null output pointer"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if ((rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bb_prepare(false, !on_dev))) return rc;
+        if ((rc = join_in())) { (void)join_out(); return rc; }
+        REAL* const o = on_dev ? (REAL*)out : d_bb_stage;
+        hipLaunchKernelGGL(bound_get_fn<REAL>(), dim3((uint32_t)m.size()), dim3(256), 0, stream, (const BoundItem<REAL>*)d_bb_items, o);
+        hipError_t e = hipGetLastError();
+        if (!on_dev) {
+            if (e == hipSuccess) e = hipMemcpyAsync(out, o, bb_bdds * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        }
+        const int rc2 = join_out();
+        if (e != hipSuccess) { err = std::string("batch lower_bound_per_bdd: ") + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        return rc2;
+    }
+    int grad_lower_bound_per_bdd(const void* grad_lb, void* grad_lo, void* grad_hi, int on_dev) override
+    {
+        int rc;
+        const char* const me = "batch grad_lower_bound_per_bdd";
+        const uint32_t n = (uint32_t)m.size();
+        if (!grad_lb || !grad_lo || !grad_hi) { err = std::string(me) + ": null pointer"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if ((rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bb_prepare(false, !on_dev))) return rc;
+        // the argument check, before any member or output is touched: host values here, device values by one launch for all members
+        // (the batch stream is behind whatever the caller ordered it behind: bddmma_stream_wait_batch) and the call's one read
+        uint32_t bad = 0xFFFFFFFFu;
+        if (!on_dev) {
+            const REAL* h = (const REAL*)grad_lb;
+            for (uint32_t i = 0; i < n && bad == 0xFFFFFFFFu; ++i) {
+                for (uint64_t b = 0; b < m[i]->n_bdds; ++b)
+                    if (!std::isfinite(h[b])) { bad = i; break; }
+                h += m[i]->n_bdds;
+            }
+        } else {
+            HIPCHK(hipMemsetAsync(d_bb_bad, 0xFF, sizeof(uint32_t), stream));
+            hipLaunchKernelGGL(bound_check_fn<REAL>(), dim3(n), dim3(256), 0, stream, (const BoundItem<REAL>*)d_bb_items, (const REAL*)grad_lb, d_bb_bad);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&bad, d_bb_bad, sizeof(bad), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+        if (bad != 0xFFFFFFFFu) {
+            err = "batch member " + std::to_string(bad) + ": some of its grad_lb_per_bdd are not finite";
+            return BDDMMA_ERR_INVALID_ARGUMENT;
+        }
+        if ((rc = join_in())) { (void)join_out(); return rc; }
+        const REAL* g = (const REAL*)grad_lb;
+        REAL *lo = (REAL*)grad_lo, *hi = (REAL*)grad_hi;
+        hipError_t e = hipSuccess;
+        if (!on_dev) {
+            e = hipMemcpyAsync(d_bb_stage, grad_lb, bb_bdds * sizeof(REAL), hipMemcpyHostToDevice, stream);
+            g = d_bb_stage;
+            lo = d_bb_stage + bb_bdds;
+            hi = lo + bb_layers;
+        }
+        for (size_t k = 0; k < bb_groups.size() && e == hipSuccess; ++k) {
+            const BbGroup& G = bb_groups[k];
+            hipLaunchKernelGGL(G.fn, dim3(G.count), dim3(G.threads), G.lds, stream, (const BoundItem<REAL>*)(d_bb_items + G.first), g, lo, hi);
+            e = hipGetLastError();
+        }
+        if (!on_dev) {
+            if (e == hipSuccess) e = hipMemcpyAsync(grad_lo, lo, bb_layers * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(grad_hi, hi, bb_layers * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        }
+        const int rc2 = join_out();
+        if (e != hipSuccess) { err = std::string(me) + ": " + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        return rc2;
+    }
+    int distribute_delta() override
+    {
+        int rc;
+        if ((rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bb_prepare(true, false))) return rc;
+        if ((rc = members_in())) return rc;
+        // ---- the members are touched from here on
+        hipLaunchKernelGGL(bound_dist_fn<REAL>(), dim3((uint32_t)m.size()), dim3(256), 0, stream, (const BoundItem<REAL>*)d_bb_items);
+        const hipError_t e = hipGetLastError();
+        // the host-side state after SolverT::distribute_delta
+        for (S* s : m) {
+            s->mm_consumed_valid = true;
+            s->x_layer_valid = false;
+            s->delta_var_valid = true;
+            s->costs_changed();
+        }
+        const int rc2 = join_out();
+        if (e != hipSuccess) { err = std::string("batch distribute_delta: ") + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
         return rc2;
     }
     int stream_wait(hipStream_t other) override

@@ -755,6 +755,42 @@ class bdd_hip_batch:
         self._check(self._L.bddmma_get_solver_costs_batch(self._h, _ptr(lo), _ptr(hi), _ptr(mm), 0), self._h)
         return lo, hi, mm
 
+    # ---- the tail of a training step's loss (include/bdd_mma.h: bddmma_lower_bound_per_bdd_batch and the two entries behind it)
+    def lower_bound_per_bdd(self, out=None):
+        """lower_bound_per_bdd() of every member in one launch: the members' REAL[nr_bdds] one behind the other in the members' order.
+        out: a device buffer, written in the batch stream's order (the host does not wait); without it a new NumPy array."""
+        nb = sum(s.nr_bdds() for s in self.solvers)
+        vt = self.solvers[0].value_type
+        if out is not None:
+            assert _is_dev(out), "out: a device buffer"
+            self._check(self._L.bddmma_lower_bound_per_bdd_batch(self._h, _dev_ptr(out, nb, vt), 1), self._h)
+            return out
+        out = np.zeros(nb, vt)
+        self._check(self._L.bddmma_lower_bound_per_bdd_batch(self._h, _ptr(out), 0), self._h)
+        return out
+
+    def grad_lower_bound_per_bdd(self, grad_lb, out=None):
+        """grad_lower_bound_per_bdd(grad_lb_i) of every member i, one workgroup per member: (grad_lo, grad_hi), the members' REAL[nr_layers]
+        one behind the other; grad_lb: the members' REAL[nr_bdds] one behind the other.  A device tensor needs out = (grad_lo, grad_hi)
+        device buffers, a NumPy array gives two new NumPy arrays."""
+        n = sum(s.nr_layers() for s in self.solvers)
+        nb = sum(s.nr_bdds() for s in self.solvers)
+        vt = self.solvers[0].value_type
+        call = self._L.bddmma_grad_lower_bound_per_bdd_batch
+        if _is_dev(grad_lb):
+            assert out is not None and len(out) == 2 and all(_is_dev(x) for x in out), "device gradients need device output buffers: out=(grad_lo, grad_hi)"
+            self._check(call(self._h, _dev_ptr(grad_lb, nb, vt), _dev_ptr(out[0], n, vt), _dev_ptr(out[1], n, vt), 1), self._h)
+            return out[0], out[1]
+        g = np.ascontiguousarray(grad_lb, dtype=vt)
+        assert g.size == nb, f"expected {nb} values, got {g.size}"
+        lo, hi = np.zeros(n, vt), np.zeros(n, vt)
+        self._check(call(self._h, _ptr(g), _ptr(lo), _ptr(hi), 0), self._h)
+        return lo, hi
+
+    def distribute_delta(self):
+        """distribute_delta() of every member in one launch; a member's grad_distribute_delta() afterwards refers to it"""
+        self._check(self._L.bddmma_distribute_delta_batch(self._h), self._h)
+
     # ---- ordering against other streams (include/bdd_mma.h: bddmma_stream_wait_batch / bddmma_stream_signal_batch)
     def stream_wait(self, hip_stream=0):
         """what the batch's calls queue from now on starts after everything queued so far on `hip_stream` (a raw hipStream_t as an

@@ -573,6 +573,29 @@ int bddmma_get_solver_costs_batch(bddmma_batch* b, void* lo /* or NULL */, void*
  * of a pair per member: every batch call orders itself against the members' streams. */
 int bddmma_stream_wait_batch(bddmma_batch* b, void* hip_stream);
 int bddmma_stream_signal_batch(bddmma_batch* b, void* hip_stream);
+/* The tail of a training step's loss for every member at once (kernels/batchbound.hpp); named after the per-member calls they are.
+ * Arrays: per-BDD arrays are the members' REAL[nr_bdds] in the order of bddmma_lower_bound_per_bdd, one behind the other in the members'
+ * order at bddmma_batch_create; layer arrays are the members' REAL[nr_layers] in the public layer order, concatenated the same way.  One
+ * on_device flag covers all arrays of a call.  Host arrays pass through a staging buffer the batch owns with one host synchronisation;
+ * device arrays are written in the order of the batch's stream and the host does not wait (the gradient's argument check reads one
+ * word back, once).  Results are bit-equal to the per-member calls in float and in double.
+ * Refusals, each decided before any member or output is touched: b == NULL or a null array is BDDMMA_ERR_INVALID_ARGUMENT;
+ * BDDMMA_ERR_STATE as for every batch call; whatever has to be allocated is allocated before any member is touched.
+ *
+ * bddmma_lower_bound_per_bdd_batch: bddmma_lower_bound_per_bdd(member i, its part of out, ..) for every member i in one launch.  Members
+ * whose costs-to-terminal are stale get their own backward sweep first; afterwards the backward state is valid and nothing else has changed. */
+int bddmma_lower_bound_per_bdd_batch(bddmma_batch* b, void* out, int on_device);
+/* bddmma_grad_lower_bound_per_bdd(member i, its parts, smooth = 0, ..) for every member i: one workgroup per member, a wave per pack, runs
+ * the arg-min path of every BDD out of LDS and writes grad_hi = x * g, grad_lo = (1 - x) * g per layer, g the BDD's entry of
+ * grad_lb_per_bdd; one launch per wave count present.  A value of grad_lb_per_bdd that is not finite: BDDMMA_ERR_INVALID_ARGUMENT,
+ * bddmma_batch_last_error naming the first offending member, the outputs untouched (one check launch covers all members).
+ * State: as bddmma_lower_bound_per_bdd_batch — arc costs, deferred differences and delta are unchanged, and every getter returns
+ * afterwards what it returns after the per-member call. */
+int bddmma_grad_lower_bound_per_bdd_batch(bddmma_batch* b, const void* grad_lb_per_bdd, void* grad_lo_out, void* grad_hi_out, int on_device);
+/* bddmma_distribute_delta(member i) for every member i in one launch.  Per member exactly the state that call leaves: the deferred
+ * differences applied to the arc costs and cleared, a copy of them kept for a later bddmma_grad_distribute_delta(member i, ..), delta
+ * zero, both sweep states invalid. */
+int bddmma_distribute_delta_batch(bddmma_batch* b);
 /* bddmma_run_solver(member, NULL, max_iter, tolerance, improvement_slope, time_limit, 0, &res[i]) for every member i: each member's tests
  * run inside its workgroup against its own control block and each stops on its own criterion; the host relaunches chunks of iterations
  * until every member has stopped or reached max_iter.  res (bddmma_batch_size entries, may be NULL): member i's iterations, bounds and
