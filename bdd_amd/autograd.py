@@ -372,9 +372,14 @@ class DistributeDeferredDelta(torch.autograd.Function):
 class ComputeAllMinMarginalsDiff(torch.autograd.Function):
     """bdd_cuda_torch.py:234-277.  apply(solvers, lo_costs_batch, hi_costs_batch) -> min_marginal_diff per layer, deferred differences zero.
 
-    backward  bddmma_grad_min_marginal_diff with the saved costs set again.  State contract of that call: it recomputes whichever stored
-              sweep state is invalid and leaves both valid; arc costs, deferred differences and delta are not changed; it works with an
-              L-BFGS wrapper attached; a non-finite incoming gradient is BDDMMA_ERR_INVALID_ARGUMENT (BddMmaError)."""
+    forward   for a bdd_hip_batch ONE batch.set_solver_costs and ONE batch.min_marginal_diff (bddmma_min_marginal_diff_batch: one workgroup
+              per member), none on a member, with the list form's results bit for bit.  The list form runs for a list, and for a batch
+              whose first call refuses with BDDMMA_ERR_STATE.
+    backward  bddmma_grad_min_marginal_diff with the saved costs set again; for a bdd_hip_batch likewise ONE batch.set_solver_costs and ONE
+              batch.grad_all_min_marginal_differences (bddmma_grad_min_marginal_diff_batch).  State contract of that call: it recomputes
+              whichever stored sweep state is invalid and leaves both valid; arc costs, deferred differences and delta are not changed;
+              the per-member call works with an L-BFGS wrapper attached; a non-finite incoming gradient is BDDMMA_ERR_INVALID_ARGUMENT
+              (BddMmaError)."""
 
     @staticmethod
     def forward(ctx, solvers, lo_costs_batch, hi_costs_batch):
@@ -383,6 +388,13 @@ class ComputeAllMinMarginalsDiff(torch.autograd.Function):
         ctx.save_for_backward(lo_costs_batch, hi_costs_batch)
         ctx.sizes = z
         mm_diff = torch.empty_like(lo_costs_batch)
+        if z.batch is not None:
+            with _Ordered([z.batch]):
+                batched = _batch_set_costs(z.batch, lo_costs_batch, hi_costs_batch, zero)
+                if batched:
+                    z.batch.min_marginal_diff(out=mm_diff)
+            if batched:
+                return mm_diff
         with _Ordered(z.solvers):
             for s, l in zip(z.solvers, z.slices(z.layers)):
                 s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], zero[l])
@@ -397,6 +409,13 @@ class ComputeAllMinMarginalsDiff(torch.autograd.Function):
         g = z.check(("grad_mm_diff_batch", _incoming(grad_mm_diff, lo_costs_batch), z.layers))
         zero = torch.zeros_like(lo_costs_batch)
         g_lo, g_hi = torch.empty_like(lo_costs_batch), torch.empty_like(hi_costs_batch)
+        if z.batch is not None:
+            with _Ordered([z.batch]):
+                batched = _batch_set_costs(z.batch, lo_costs_batch, hi_costs_batch, zero)
+                if batched:
+                    z.batch.grad_all_min_marginal_differences(g, out=(g_lo, g_hi))
+            if batched:
+                return None, g_lo, g_hi
         with _Ordered(z.solvers):
             for s, l in zip(z.solvers, z.slices(z.layers)):
                 s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], zero[l])

@@ -560,6 +560,26 @@ class bdd_hip_batch {
         return {std::move(lo), std::move(hi)};
     }
     void distribute_delta() { check(bddmma_distribute_delta_batch(b_)); }
+    // min_marginal_diff / grad_mm_diff_all_hops of every member, one workgroup per member: every array is the members' REAL[nr_layers], one
+    // behind the other in the members' order.  Device pointers (the host does not wait) or host vectors.  Contract:
+    // bddmma_min_marginal_diff_batch, bddmma_grad_min_marginal_diff_batch.
+    void min_marginal_diff(REAL* dev_mm_diff) { check(bddmma_min_marginal_diff_batch(b_, dev_mm_diff, 1)); }
+    std::vector<REAL> min_marginal_diff_host(const size_t total_layers)
+    {
+        std::vector<REAL> mm(total_layers);
+        check(bddmma_min_marginal_diff_batch(b_, mm.data(), 0));
+        return mm;
+    }
+    void grad_mm_diff_all_hops(const REAL* dev_grad_mm, REAL* dev_grad_lo_out, REAL* dev_grad_hi_out)
+    {
+        check(bddmma_grad_min_marginal_diff_batch(b_, dev_grad_mm, dev_grad_lo_out, dev_grad_hi_out, 1));
+    }
+    std::pair<std::vector<REAL>, std::vector<REAL>> grad_mm_diff_all_hops(const std::vector<REAL>& grad_mm)
+    {
+        std::vector<REAL> lo(grad_mm.size()), hi(grad_mm.size());
+        check(bddmma_grad_min_marginal_diff_batch(b_, grad_mm.data(), lo.data(), hi.data(), 0));
+        return {std::move(lo), std::move(hi)};
+    }
     // stream_wait — the batch's later calls start after everything queued on `hip_stream` so far; stream_signal — the reverse
     // (bddmma_stream_wait_batch / bddmma_stream_signal_batch)
     void stream_wait(void* hip_stream) { check(bddmma_stream_wait_batch(b_, hip_stream)); }

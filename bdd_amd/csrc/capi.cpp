@@ -492,6 +492,20 @@ int bddmma_grad_lower_bound_per_bdd_batch(bddmma_batch* b, const void* grad_lb_p
     });
 }
 int bddmma_distribute_delta_batch(bddmma_batch* b) { return guarded_batch(b, [&](BatchBase* i) { return i->distribute_delta(); }); }
+int bddmma_min_marginal_diff_batch(bddmma_batch* b, void* out, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!out) { i->err = "batch min_marginal_diff: null output pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        return i->min_marginal_diff(out, on_device);
+    });
+}
+int bddmma_grad_min_marginal_diff_batch(bddmma_batch* b, const void* grad_mm, void* grad_lo_out, void* grad_hi_out, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!grad_mm || !grad_lo_out || !grad_hi_out) { i->err = "batch grad_min_marginal_diff: null pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        return i->grad_min_marginal_diff(grad_mm, grad_lo_out, grad_hi_out, on_device);
+    });
+}
 int bddmma_batch_time_iterations(bddmma_batch* b, double omega, uint64_t n, double* ms)
 {
     return guarded_batch(b, [&](BatchBase* i) {

@@ -1,7 +1,7 @@
 // kernels/gradmm.hpp — the backward operator of the min-marginal differences (bdd_cuda_learned_mma.cu:623-1023, grad_mm_diff_all_hops):
 // the transpose-Jacobian product of mm_diff[l] = m_hi[l] - m_lo[l], m_a[l] = min over the nodes u of l of F[u] + c_a[l] + T[child_a(u)],
-// with respect to the lo / hi arc costs.  Included by solver_gr.hpp only (translation units solver_gr_f32.hip / solver_gr_f64.hip), behind
-// kernels.hpp.
+// with respect to the lo / hi arc costs.  The two kernels are instantiated by solver_gr.hpp only (translation units solver_gr_f32.hip /
+// solver_gr_f64.hip); their bodies also run inside k_small_grad_mm_batch (kernels/batchmm.hpp).  Behind kernels.hpp.
 //
 // F and T are the stored potentials of the plain sweeps.  With g the incoming gradient:
 //   seeds      per layer l and arc a, at the arg-min node u*_a(l) (sign s = +1 for hi, -1 for lo):  dc_a[l] += s g[l],  dF[u*_a] += s g[l],
@@ -75,13 +75,13 @@ __device__ __forceinline__ Pull2<REAL> gr_take_up(const PullNode& nd, uint32_t j
     return {(nd.lo < nn && AP[nd.lo] == (j << 1)) ? Dn[nd.lo] : REAL(0), (nd.hi < nn && AP[nd.hi] == ((j << 1) | 1u)) ? Dn[nd.hi] : REAL(0)};
 }
 
-template <typename REAL, bool NARROW, bool GLOBAL>
-__global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gr_down(DevPtrs<REAL> d, PackDev pk, const uint32_t* par_ptr, const uint32_t* par, uint32_t ww,
-                                                                        unsigned char* scratch, const REAL* __restrict__ g, REAL* __restrict__ out_lo,
-                                                                        REAL* __restrict__ out_hi, uint32_t* __restrict__ arg)
+// The sweeps' bodies for the pack `pc`: k_gr_down / k_gr_up run them with the workgroup's pack and PullBlockBar (__syncthreads()) as BAR,
+// k_small_grad_mm_batch (kernels/batchmm.hpp) with a wave's pack and a wave-level ordering point.
+template <typename REAL, bool NARROW, typename BAR>
+__device__ __forceinline__ void gr_down_body(const DevPtrs<REAL>& d, const PackDev& pk, const PullPack<REAL>& pc, const uint32_t* par_ptr, const uint32_t* par,
+                                             uint32_t ww, const REAL* __restrict__ g, REAL* __restrict__ out_lo, REAL* __restrict__ out_hi,
+                                             uint32_t* __restrict__ arg)
 {
-    if (blockIdx.x >= pk.n_packs) return;
-    const PullPack<REAL> pc = pull_pack<REAL, NARROW, GLOBAL>(d, pk, ww, scratch, gr_lds_bytes(sizeof(REAL), ww));
     REAL* const S = pc.base;                    // [hop parity][arc][slot]: what the node sends along the arc
     REAL* const P0 = pc.base + 4 * (size_t)ww;  // path value through the lo arc per slot; after the arg-min: the runs' sums of S
     REAL* const P1 = pc.base + 5 * (size_t)ww;  // ... the hi arc
@@ -104,9 +104,9 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gr_down(DevPtrs<
             P1[j] = f + b;
             gr_send_down(par_ptr, par, wi, !(q == pc.q0 || j == rt), Sp, Sc, ww, j, REAL(0), a, b);
         });
-        __syncthreads();
+        BAR::sync();
         // ---- arg-min per layer and arc (strictly smaller replaces, in the runs and among them: the lowest slot wins a tie)
-        pull_layer_fold(
+        pull_layer_fold_bar<BAR>(
             pc, Lid, n, [](uint32_t j) { return Pull2<uint32_t>{j, j}; },
             [&](Pull2<uint32_t> v, Pull2<uint32_t> w) { return Pull2<uint32_t>{P0[w.lo] < P0[v.lo] ? w.lo : v.lo, P1[w.hi] < P1[v.hi] ? w.hi : v.hi}; },
             [&](uint32_t j, Pull2<uint32_t> v) { I0[j] = v.lo; I1[j] = v.hi; }, [&](uint32_t j) { return Pull2<uint32_t>{I0[j], I1[j]}; },
@@ -119,23 +119,31 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gr_down(DevPtrs<
                 arg[2 * (size_t)(lbase + l)] = f0 ? i.lo : GR_NONE;
                 arg[2 * (size_t)(lbase + l) + 1] = f1 ? i.hi : GR_NONE;
             });
-        __syncthreads();
+        BAR::sync();
         // ---- dc of the layer = the sum of S over its slots (the runs' sums into P0 / P1, dead by now)
-        pull_layer_fold(
+        pull_layer_fold_bar<BAR>(
             pc, Lid, n, [&](uint32_t j) { return Pull2<REAL>{Sc[j], Sc[ww + j]}; },
             pull_add<REAL>, [&](uint32_t j, Pull2<REAL> v) { P0[j] = v.lo; P1[j] = v.hi; },
             [&](uint32_t j) { return Pull2<REAL>{P0[j], P1[j]}; }, [&](uint32_t l, Pull2<REAL> s) { out_lo[lbase + l] = s.lo; out_hi[lbase + l] = s.hi; });
-        __syncthreads();  // the next hop overwrites P, I and Lid and pulls from this hop's S
+        BAR::sync();  // the next hop overwrites P, I and Lid and pulls from this hop's S
     }
 }
 
 template <typename REAL, bool NARROW, bool GLOBAL>
-__global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gr_up(DevPtrs<REAL> d, PackDev pk, const uint32_t* par_ptr, const uint32_t* par, uint32_t ww,
-                                                                      unsigned char* scratch, const REAL* __restrict__ g, REAL* __restrict__ out_lo,
-                                                                      REAL* __restrict__ out_hi, const uint32_t* __restrict__ arg)
+__global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gr_down(DevPtrs<REAL> d, PackDev pk, const uint32_t* par_ptr, const uint32_t* par, uint32_t ww,
+                                                                        unsigned char* scratch, const REAL* __restrict__ g, REAL* __restrict__ out_lo,
+                                                                        REAL* __restrict__ out_hi, uint32_t* __restrict__ arg)
 {
     if (blockIdx.x >= pk.n_packs) return;
     const PullPack<REAL> pc = pull_pack<REAL, NARROW, GLOBAL>(d, pk, ww, scratch, gr_lds_bytes(sizeof(REAL), ww));
+    gr_down_body<REAL, NARROW, PullBlockBar>(d, pk, pc, par_ptr, par, ww, g, out_lo, out_hi, arg);
+}
+
+template <typename REAL, bool NARROW, typename BAR>
+__device__ __forceinline__ void gr_up_body(const DevPtrs<REAL>& d, const PackDev& pk, const PullPack<REAL>& pc, const uint32_t* par_ptr, const uint32_t* par,
+                                           uint32_t ww, const REAL* __restrict__ g, REAL* __restrict__ out_lo, REAL* __restrict__ out_hi,
+                                           const uint32_t* __restrict__ arg)
+{
     REAL* const D = pc.base;                    // [hop parity][slot]: dF
     REAL* const V0 = pc.base + 2 * (size_t)ww;  // F + lo cost per slot of this hop; after the children's arg-min: what the node took over its lo arc
     REAL* const V1 = pc.base + 3 * (size_t)ww;  // ... hi
@@ -155,10 +163,10 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gr_up(DevPtrs<RE
             V0[j] = f + d.lohi[2 * (size_t)nd.layer];
             V1[j] = f + d.lohi[2 * (size_t)nd.layer + 1];
         });
-        __syncthreads();
+        BAR::sync();
         // ---- the children's arg-min (parent, arc): first in parent table order wins a tie; a root or an unreachable node names nobody
         gr_name_parents(pc, par_ptr, par, nb + n + pc.wdelta, nn, V0, V1, AP);
-        __syncthreads();
+        BAR::sync();
         // ---- dF = seeds + dF of the children that name this node
         pull_slots<REAL, NARROW, false>(d, pc, nb, n, lbase, nullptr, [&](uint32_t j, uint32_t, const PullNode& nd) {
             const Pull2<REAL> t = gr_take_up(nd, j, nn, AP, Dn);
@@ -174,9 +182,9 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gr_up(DevPtrs<RE
             V0[j] = t0;
             V1[j] = t1;
         });
-        __syncthreads();
+        BAR::sync();
         // ---- dc of the layer grows by the sum of what its nodes took
-        pull_layer_fold(
+        pull_layer_fold_bar<BAR>(
             pc, Lid, n, [&](uint32_t j) { return Pull2<REAL>{V0[j], V1[j]}; },
             pull_add<REAL>, [&](uint32_t j, Pull2<REAL> v) { Q0[j] = v.lo; Q1[j] = v.hi; },
             [&](uint32_t j) { return Pull2<REAL>{Q0[j], Q1[j]}; },
@@ -184,8 +192,18 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gr_up(DevPtrs<RE
                 out_lo[lbase + l] += s.lo;  // behind k_gr_down's value; one writer per layer
                 out_hi[lbase + l] += s.hi;
             });
-        __syncthreads();  // the next hop overwrites every array but this hop's dF
+        BAR::sync();  // the next hop overwrites every array but this hop's dF
     }
+}
+
+template <typename REAL, bool NARROW, bool GLOBAL>
+__global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_gr_up(DevPtrs<REAL> d, PackDev pk, const uint32_t* par_ptr, const uint32_t* par, uint32_t ww,
+                                                                      unsigned char* scratch, const REAL* __restrict__ g, REAL* __restrict__ out_lo,
+                                                                      REAL* __restrict__ out_hi, const uint32_t* __restrict__ arg)
+{
+    if (blockIdx.x >= pk.n_packs) return;
+    const PullPack<REAL> pc = pull_pack<REAL, NARROW, GLOBAL>(d, pk, ww, scratch, gr_lds_bytes(sizeof(REAL), ww));
+    gr_up_body<REAL, NARROW, PullBlockBar>(d, pk, pc, par_ptr, par, ww, g, out_lo, out_hi, arg);
 }
 
 }  // namespace bddmma

@@ -201,6 +201,10 @@ struct BatchBase {
     virtual int lower_bound_per_bdd(void* out, int on_device) = 0;
     virtual int grad_lower_bound_per_bdd(const void* grad_lb, void* grad_lo, void* grad_hi, int on_device) = 0;
     virtual int distribute_delta() = 0;
+    // SolverBase::min_marginal_diff / grad_min_marginal_diff of every member, one launch per kernel instantiation present
+    // (kernels/batchmm.hpp; include/bdd_mma.h: bddmma_min_marginal_diff_batch, bddmma_grad_min_marginal_diff_batch)
+    virtual int min_marginal_diff(void* out, int on_device) = 0;
+    virtual int grad_min_marginal_diff(const void* grad_mm, void* grad_lo, void* grad_hi, int on_device) = 0;
     // the batch stream behind everything queued on `other` so far / the reverse, by an event the batch owns; the host does not wait
     virtual int stream_wait(hipStream_t other) = 0;
     virtual int stream_signal(hipStream_t other) = 0;

@@ -9,6 +9,7 @@
 #include "kernels/gradsmall.hpp"
 #include "kernels/batchcosts.hpp"
 #include "kernels/batchbound.hpp"
+#include "kernels/batchmm.hpp"
 #include "kernels/smallhist.hpp"
 
 namespace bddmma {
@@ -44,7 +45,7 @@ struct BatchT final : BatchBase {
         for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1, ev_order})
             if (e) (void)hipEventDestroy(e);
         if (d_items) (void)hipFree(d_items);
-        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad})
+        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad, (void*)d_bm_items, (void*)d_bm_stage, (void*)d_bm_bad})
             if (q) (void)hipFree(q);
         if (d_ctl) (void)hipFree(d_ctl);
         if (h_ctl) (void)hipHostFree(h_ctl);
@@ -976,6 +977,172 @@ struct BatchT final : BatchBase {
         }
         const int rc2 = join_out();
         if (e != hipSuccess) { err = std::string("batch distribute_delta: ") + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        return rc2;
+    }
+    // ---- the min-marginal differences and their gradient, all members at once (kernels/batchmm.hpp: k_small_mmdiff_batch,
+    // k_small_grad_mm_batch; the kernels compile in solver_bm_f32.hip / _f64.hip).  Items sorted by the members' wave count, as the bound
+    // items are: one launch per wave count present.  Host arrays pass through one staging buffer the batch owns (grad_mm or the
+    // differences | lo | hi); it, the check word and what a member's gr_prepare() allocates exist before any member is touched.
+    struct BmGroup {
+        MmDiffFn<REAL> diff;
+        MmGradFn<REAL> grad;
+        uint32_t threads, lds_diff, lds_grad, first, count;
+    };
+    std::vector<BmGroup> bm_groups;
+    std::vector<MmItem<REAL>> bm_items;        // host copy, in launch order
+    std::vector<uint32_t> bm_ord;              // item j is member bm_ord[j]
+    MmItem<REAL>* d_bm_items = nullptr;
+    REAL* d_bm_stage = nullptr;
+    uint32_t* d_bm_bad = nullptr;
+    uint64_t bm_layers = 0;                    // values of all members' layers
+    bool bm_ready = false, bm_grad_ready = false;
+
+    // grad: the call is the gradient, whose items need every member's parent tables and d_gr_arg; host_arrays: the call needs the staging buffer
+    int bm_prepare(bool grad, bool host_arrays)
+    {
+        const uint32_t n = (uint32_t)m.size();
+        constexpr uint32_t RS = (uint32_t)sizeof(REAL);
+        if (!bm_ready) {
+            std::vector<uint32_t> ord(n);
+            for (uint32_t i = 0; i < n; ++i) ord[i] = i;
+            std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return m[a]->small_nw < m[b]->small_nw; });
+            std::vector<uint64_t> src(n);
+            uint64_t total = 0;
+            for (uint32_t i = 0; i < n; ++i) {
+                src[i] = total;
+                total += m[i]->n_layers;
+            }
+            if (total > 0xFFFFFFFFull) { err = "batch min_marginal_diff: too many layers"; return BDDMMA_ERR_UNSUPPORTED; }
+            std::vector<MmItem<REAL>> items(n);
+            std::vector<BmGroup> groups_;
+            for (uint32_t j = 0; j < n; ++j) {
+                const S* s = m[ord[j]];
+                const SmallDev& sm = s->small;
+                items[j] = MmItem<REAL>{sm.pack_hdr, sm.rec, sm.rec_off, sm.rec_words, sm.ns, sm.nl, sm.n_packs, (uint32_t)s->n_layers, (uint32_t)src[ord[j]], ord[j],
+                                        s->pack_width, s->ptrs(nullptr), s->pdev(s->nb_, 0, 0), nullptr, nullptr, nullptr};
+                if (groups_.empty() || s->small_nw != m[ord[groups_.back().first]]->small_nw)
+                    groups_.push_back(BmGroup{mm_diff_fn<REAL>(s->small_nw), mm_grad_fn<REAL>(s->small_nw), 64u * (uint32_t)s->small_nw, 0u, 0u, j, 0u});
+                BmGroup& g = groups_.back();
+                g.lds_diff = std::max(g.lds_diff, sm.n_packs * mmdiff_region_bytes(RS, sm.ns, sm.nl));
+                g.lds_grad = std::max(g.lds_grad, sm.n_packs * mmgrad_region_bytes(RS, sm.ns, sm.nl));
+                ++g.count;
+            }
+            for (const BmGroup& g : groups_) {
+                // (never taken for a fused_small member: both regions are smaller than a pack's share of small_lds, kernels/batchmm.hpp)
+                if (std::max(g.lds_diff, g.lds_grad) > m[0]->lds_cu) { err = "batch min_marginal_diff: the packs' state does not fit the LDS"; return BDDMMA_ERR_UNSUPPORTED; }
+                if (int rc = raise_lds_limit(reinterpret_cast<const void*>(g.diff), g.lds_diff)) return rc;
+                if (int rc = raise_lds_limit(reinterpret_cast<const void*>(g.grad), g.lds_grad)) return rc;
+            }
+            if (!d_bm_items) HIPCHK(hipMalloc((void**)&d_bm_items, n * sizeof(MmItem<REAL>)));
+            if (!d_bm_bad) HIPCHK(hipMalloc((void**)&d_bm_bad, sizeof(uint32_t)));
+            HIPCHK(hipMemcpy(d_bm_items, items.data(), n * sizeof(MmItem<REAL>), hipMemcpyHostToDevice));
+            bm_items = std::move(items);
+            bm_ord = std::move(ord);
+            bm_groups = std::move(groups_);
+            bm_layers = total;
+            bm_ready = true;
+        }
+        if (grad && !bm_grad_ready) {
+            for (S* s : m)
+                if (int rc = s->gr_prepare()) { err = s->err; return rc; }
+            for (uint32_t j = 0; j < n; ++j) {
+                const S* s = m[bm_ord[j]];
+                bm_items[j].par_ptr = s->d_sm_nptr;
+                bm_items[j].par = s->d_sm_npar;
+                bm_items[j].arg = s->d_gr_arg;
+            }
+            HIPCHK(hipStreamSynchronize(stream));   // nothing in flight reads the items
+            HIPCHK(hipMemcpy(d_bm_items, bm_items.data(), n * sizeof(MmItem<REAL>), hipMemcpyHostToDevice));
+            bm_grad_ready = true;
+        }
+        if (host_arrays && !d_bm_stage) HIPCHK(hipMalloc((void**)&d_bm_stage, std::max<uint64_t>(3 * bm_layers, 1) * sizeof(REAL)));
+        return BDDMMA_OK;
+    }
+    // the host-side state after SolverT::min_marginal_diff / gr_min_marginal_diff: the costs-from-root are the plain sweep's (the launch has
+    // stored them), the costs-to-terminal join_in's.  Behind a failed launch the costs-from-root are not known to be valid.
+    void bm_launched(bool ok)
+    {
+        for (S* s : m) s->fwd_valid = ok;
+    }
+    int min_marginal_diff(void* out, int on_dev) override
+    {
+        int rc;
+        if (!out) { err = "batch min_marginal_diff: null output pointer"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if ((rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bm_prepare(false, !on_dev))) return rc;
+        if ((rc = join_in())) { (void)join_out(); return rc; }
+        // ---- the members are touched from here on (their costs-from-root)
+        REAL* const o = on_dev ? (REAL*)out : d_bm_stage;
+        hipError_t e = hipSuccess;
+        for (size_t k = 0; k < bm_groups.size() && e == hipSuccess; ++k) {
+            const BmGroup& G = bm_groups[k];
+            hipLaunchKernelGGL(G.diff, dim3(G.count), dim3(G.threads), G.lds_diff, stream, (const MmItem<REAL>*)(d_bm_items + G.first), o);
+            e = hipGetLastError();
+        }
+        bm_launched(e == hipSuccess);
+        if (!on_dev) {
+            if (e == hipSuccess) e = hipMemcpyAsync(out, o, bm_layers * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        }
+        const int rc2 = join_out();
+        if (e != hipSuccess) { err = std::string("batch min_marginal_diff: ") + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        return rc2;
+    }
+    int grad_min_marginal_diff(const void* grad_mm, void* grad_lo, void* grad_hi, int on_dev) override
+    {
+        int rc;
+        const char* const me = "batch grad_min_marginal_diff";
+        const uint32_t n = (uint32_t)m.size();
+        if (!grad_mm || !grad_lo || !grad_hi) { err = std::string(me) + ": null pointer"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if ((rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bm_prepare(true, !on_dev))) return rc;
+        // the argument check, before any member or output is touched: host values here, device values by one launch for all members
+        // (the batch stream is behind whatever the caller ordered it behind: bddmma_stream_wait_batch) and the call's one read
+        uint32_t bad = 0xFFFFFFFFu;
+        if (!on_dev) {
+            const REAL* h = (const REAL*)grad_mm;
+            for (uint32_t i = 0; i < n && bad == 0xFFFFFFFFu; ++i) {
+                for (uint64_t l = 0; l < m[i]->n_layers; ++l)
+                    if (!std::isfinite(h[l])) { bad = i; break; }
+                h += m[i]->n_layers;
+            }
+        } else {
+            HIPCHK(hipMemsetAsync(d_bm_bad, 0xFF, sizeof(uint32_t), stream));
+            hipLaunchKernelGGL(mm_check_fn<REAL>(), dim3(n), dim3(256), 0, stream, (const MmItem<REAL>*)d_bm_items, (const REAL*)grad_mm, d_bm_bad);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&bad, d_bm_bad, sizeof(bad), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+        if (bad != 0xFFFFFFFFu) {
+            err = "batch member " + std::to_string(bad) + ": some of its grad_mm are not finite";
+            return BDDMMA_ERR_INVALID_ARGUMENT;
+        }
+        if ((rc = join_in())) { (void)join_out(); return rc; }
+        // ---- the members are touched from here on (their costs-from-root and d_gr_arg)
+        const REAL* g = (const REAL*)grad_mm;
+        REAL *lo = (REAL*)grad_lo, *hi = (REAL*)grad_hi;
+        hipError_t e = hipSuccess;
+        if (!on_dev) {
+            e = hipMemcpyAsync(d_bm_stage, grad_mm, bm_layers * sizeof(REAL), hipMemcpyHostToDevice, stream);
+            g = d_bm_stage;
+            lo = d_bm_stage + bm_layers;
+            hi = lo + bm_layers;
+        }
+        for (size_t k = 0; k < bm_groups.size() && e == hipSuccess; ++k) {
+            const BmGroup& G = bm_groups[k];
+            hipLaunchKernelGGL(G.grad, dim3(G.count), dim3(G.threads), G.lds_grad, stream, (const MmItem<REAL>*)(d_bm_items + G.first), g, lo, hi);
+            e = hipGetLastError();
+        }
+        bm_launched(e == hipSuccess);
+        if (!on_dev) {
+            if (e == hipSuccess) e = hipMemcpyAsync(grad_lo, lo, bm_layers * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(grad_hi, hi, bm_layers * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        }
+        const int rc2 = join_out();
+        if (e != hipSuccess) { err = std::string(me) + ": " + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
         return rc2;
     }
     int stream_wait(hipStream_t other) override

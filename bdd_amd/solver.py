@@ -791,6 +791,37 @@ class bdd_hip_batch:
         """distribute_delta() of every member in one launch; a member's grad_distribute_delta() afterwards refers to it"""
         self._check(self._L.bddmma_distribute_delta_batch(self._h), self._h)
 
+    # ---- the min-marginal differences and their gradient (include/bdd_mma.h: bddmma_min_marginal_diff_batch and the entry behind it)
+    def min_marginal_diff(self, out=None):
+        """min_marginal_diff() of every member, one workgroup per member: the members' REAL[nr_layers] one behind the other in the
+        members' order.  out: a device buffer, written in the batch stream's order (the host does not wait); without it a new NumPy array."""
+        n = sum(s.nr_layers() for s in self.solvers)
+        vt = self.solvers[0].value_type
+        if out is not None:
+            assert _is_dev(out), "out: a device buffer"
+            self._check(self._L.bddmma_min_marginal_diff_batch(self._h, _dev_ptr(out, n, vt), 1), self._h)
+            return out
+        out = np.zeros(n, vt)
+        self._check(self._L.bddmma_min_marginal_diff_batch(self._h, _ptr(out), 0), self._h)
+        return out
+
+    def grad_all_min_marginal_differences(self, grad_mm, out=None):
+        """grad_all_min_marginal_differences(grad_mm_i) of every member i, one workgroup per member: (grad_lo, grad_hi); all three are the
+        members' REAL[nr_layers] one behind the other.  A device tensor needs out = (grad_lo, grad_hi) device buffers, a NumPy array gives
+        two new NumPy arrays."""
+        n = sum(s.nr_layers() for s in self.solvers)
+        vt = self.solvers[0].value_type
+        call = self._L.bddmma_grad_min_marginal_diff_batch
+        if _is_dev(grad_mm):
+            assert out is not None and len(out) == 2 and all(_is_dev(x) for x in out), "device gradients need device output buffers: out=(grad_lo, grad_hi)"
+            self._check(call(self._h, _dev_ptr(grad_mm, n, vt), _dev_ptr(out[0], n, vt), _dev_ptr(out[1], n, vt), 1), self._h)
+            return out[0], out[1]
+        g = np.ascontiguousarray(grad_mm, dtype=vt)
+        assert g.size == n, f"expected {n} values, got {g.size}"
+        lo, hi = np.zeros(n, vt), np.zeros(n, vt)
+        self._check(call(self._h, _ptr(g), _ptr(lo), _ptr(hi), 0), self._h)
+        return lo, hi
+
     # ---- ordering against other streams (include/bdd_mma.h: bddmma_stream_wait_batch / bddmma_stream_signal_batch)
     def stream_wait(self, hip_stream=0):
         """what the batch's calls queue from now on starts after everything queued so far on `hip_stream` (a raw hipStream_t as an

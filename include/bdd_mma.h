@@ -596,6 +596,20 @@ int bddmma_grad_lower_bound_per_bdd_batch(bddmma_batch* b, const void* grad_lb_p
  * differences applied to the arc costs and cleared, a copy of them kept for a later bddmma_grad_distribute_delta(member i, ..), delta
  * zero, both sweep states invalid. */
 int bddmma_distribute_delta_batch(bddmma_batch* b);
+/* The min-marginal differences of every member and their gradient (kernels/batchmm.hpp), one launch per wave count present each: one
+ * workgroup per member, a wave per pack.  Arrays, the on_device flag, host staging, device ordering and the refusals are those of the
+ * three entry points above; results are bit-equal to the per-member calls in float and in double.
+ *
+ * bddmma_min_marginal_diff_batch: bddmma_min_marginal_diff(member i, its part of out, ..) for every member i.  Deferred differences are
+ * not applied.  Members whose costs-to-terminal are stale get their own backward sweep first; the launch recomputes every member's
+ * costs-from-root by a plain forward pass and stores them, so both sweep states are valid afterwards, as after the per-member call;
+ * arc costs, deferred differences and delta are unchanged. */
+int bddmma_min_marginal_diff_batch(bddmma_batch* b, void* out, int on_device);
+/* bddmma_grad_min_marginal_diff(member i, its parts, ..) for every member i: the forward pass, then the two sweeps of that call on the
+ * wave's pack (the same routing steps and layer folds, so the same tie rule and the same bits).  A value of grad_mm that is not finite:
+ * BDDMMA_ERR_INVALID_ARGUMENT, bddmma_batch_last_error naming the first offending member and grad_mm, the outputs untouched (host
+ * values are checked on the host, device values by one check launch for all members).  State: as bddmma_min_marginal_diff_batch. */
+int bddmma_grad_min_marginal_diff_batch(bddmma_batch* b, const void* grad_mm, void* grad_lo_out, void* grad_hi_out, int on_device);
 /* bddmma_run_solver(member, NULL, max_iter, tolerance, improvement_slope, time_limit, 0, &res[i]) for every member i: each member's tests
  * run inside its workgroup against its own control block and each stops on its own criterion; the host relaunches chunks of iterations
  * until every member has stopped or reached max_iter.  res (bddmma_batch_size entries, may be NULL): member i's iterations, bounds and
