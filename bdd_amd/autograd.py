@@ -7,8 +7,9 @@ mirrors); the differences are the ones include/bdd_mma.h has from the reference'
 Conventions of every function
   solvers     a list of bdd_hip_parallel_mma of one precision on one device, or a bdd_hip_batch: its members in order.  (The chain of
               a training step's loss — DualIterations, DistributeDeferredDelta and ComputeLowerBoundperBDD, forward and backward —
-              makes batch calls on a batch, with the results of the list form; every other function does with a batch what it does
-              with the list of its members.)
+              makes batch calls on a batch, with the results of the list form, and so do ComputeAllMinMarginalsDiff, GetSumMarginals
+              and GetMarginalProbability; the backward of ComputeLowerBoundperBDD with smooth_gradients_temp > 0 and every other
+              function do with a batch what they do with the list of its members.)
   tensors     1-D, contiguous, on the solvers' device, of the solvers' precision (torch.float32 / torch.float64 — the reference asks for
               torch's default dtype instead).  A batch tensor is the concatenation over the solvers, in list order, of each solver's array:
                 per layer     nr_layers() values in the public layer order (get_solver_costs, get_primal_variable_index) — there are
@@ -29,8 +30,8 @@ Conventions of every function
               overwritten while a handle still reads it.  Use the same current stream for a Function's forward and for what consumes
               its outputs, as with any torch operator.  DualIterations' two batched paths make batch calls only, which run on the
               batch's own stream and order themselves against every member's: there the one pair is the batch's (bdd_hip_batch.stream_wait
-              / stream_signal) instead of a pair per member.  The same holds for the batched forms of DistributeDeferredDelta and
-              ComputeLowerBoundperBDD.
+              / stream_signal) instead of a pair per member.  The same holds for the batched forms of DistributeDeferredDelta,
+              ComputeLowerBoundperBDD, ComputeAllMinMarginalsDiff, GetSumMarginals and GetMarginalProbability.
 Every backward is once_differentiable, takes a missing incoming gradient (None) as zeros and runs on the stream that is current
 when autograd calls it.
 """
@@ -184,9 +185,19 @@ def _with_costs(solvers, lo_costs_batch, hi_costs_batch):
 
 
 def GetMarginalProbability(solvers, lo_costs_batch, hi_costs_batch):
-    """bdd_cuda_torch.py:22-30: the smooth solution (smooth_solution_per_bdd) per layer, deferred differences zero"""
+    """bdd_cuda_torch.py:22-30: the smooth solution (smooth_solution_per_bdd) per layer, deferred differences zero.  For a bdd_hip_batch
+    ONE batch.set_solver_costs and ONE batch.smooth_solution_per_bdd (bddmma_smooth_solution_batch: one workgroup per member), none on a
+    member, with the list form's results bit for bit.  The list form runs for a list, and for a batch whose first call refuses with
+    BDDMMA_ERR_STATE."""
     z, zero = _with_costs(solvers, lo_costs_batch, hi_costs_batch)
     prob_hi = torch.empty_like(lo_costs_batch)
+    if z.batch is not None:
+        with _Ordered([z.batch]):
+            batched = _batch_set_costs(z.batch, lo_costs_batch, hi_costs_batch, zero)
+            if batched:
+                z.batch.smooth_solution_per_bdd(out=prob_hi)
+        if batched:
+            return prob_hi
     with _Ordered(z.solvers):
         for s, l in zip(z.solvers, z.slices(z.layers)):
             s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], zero[l])
@@ -195,9 +206,19 @@ def GetMarginalProbability(solvers, lo_costs_batch, hi_costs_batch):
 
 
 def GetSumMarginals(solvers, lo_costs_batch, hi_costs_batch, get_logits):
-    """bdd_cuda_torch.py:32-41: (sum_marginal_lo, sum_marginal_hi) per layer in the public layer order, logs when get_logits"""
+    """bdd_cuda_torch.py:32-41: (sum_marginal_lo, sum_marginal_hi) per layer in the public layer order, logs when get_logits.  For a
+    bdd_hip_batch ONE batch.set_solver_costs and ONE batch.sum_marginals_cuda (bddmma_sum_marginals_batch: one workgroup per member),
+    none on a member, with the list form's results bit for bit.  The list form runs for a list, and for a batch whose first call refuses
+    with BDDMMA_ERR_STATE."""
     z, zero = _with_costs(solvers, lo_costs_batch, hi_costs_batch)
     sm_lo, sm_hi = torch.empty_like(lo_costs_batch), torch.empty_like(hi_costs_batch)
+    if z.batch is not None:
+        with _Ordered([z.batch]):
+            batched = _batch_set_costs(z.batch, lo_costs_batch, hi_costs_batch, zero)
+            if batched:
+                z.batch.sum_marginals_cuda(bool(get_logits), out=(sm_lo, sm_hi))
+        if batched:
+            return sm_lo, sm_hi
     var = torch.empty(max(b - a for a, b in zip(z.layers[:-1], z.layers[1:])), dtype=torch.int32, device=lo_costs_batch.device)
     with _Ordered(z.solvers):
         for s, l in zip(z.solvers, z.slices(z.layers)):

@@ -137,6 +137,9 @@ SIGNATURES = {
     "bddmma_distribute_delta_batch": (_I, [_V]),
     "bddmma_min_marginal_diff_batch": (_I, [_V, _V, _I]),
     "bddmma_grad_min_marginal_diff_batch": (_I, [_V, _V, _V, _V, _I]),
+    "bddmma_sum_marginals_batch": (_I, [_V, _I, _V, _V, _I]),
+    "bddmma_smooth_solution_batch": (_I, [_V, _V, _I]),
+    "bddmma_grad_smooth_lower_bound_per_bdd_batch": (_I, [_V, _V, _V, _V, _I]),
     "bddmma_batch_time_iterations": (_I, [_V, _D, _U64, C.POINTER(_D)]),
     "bddmma_batch_run_solver": (_I, [_V, _U64, _D, _D, _D, C.POINTER(RunResult)]),
     "bddmma_batch_lower_bounds": (_I, [_V, C.POINTER(_D)]),

@@ -580,6 +580,37 @@ class bdd_hip_batch {
         check(bddmma_grad_min_marginal_diff_batch(b_, grad_mm.data(), lo.data(), hi.data(), 0));
         return {std::move(lo), std::move(hi)};
     }
+    // sum_marginals_cuda (unsorted layer order, no variable output) / smooth_solution_per_bdd / grad_lower_bound_per_bdd(.., smooth = true)
+    // of every member, one workgroup per member: layer arrays are the members' REAL[nr_layers], grad_lb_per_bdd the members' REAL[nr_bdds],
+    // one behind the other in the members' order.  Device pointers (the host does not wait) or host vectors.  Contract:
+    // bddmma_sum_marginals_batch, bddmma_smooth_solution_batch, bddmma_grad_smooth_lower_bound_per_bdd_batch.
+    void sum_marginals_cuda(const bool get_log_probs, REAL* dev_sm_lo, REAL* dev_sm_hi)
+    {
+        check(bddmma_sum_marginals_batch(b_, get_log_probs ? 1 : 0, dev_sm_lo, dev_sm_hi, 1));
+    }
+    std::pair<std::vector<REAL>, std::vector<REAL>> sum_marginals_host(const bool get_log_probs, const size_t total_layers)
+    {
+        std::vector<REAL> lo(total_layers), hi(total_layers);
+        check(bddmma_sum_marginals_batch(b_, get_log_probs ? 1 : 0, lo.data(), hi.data(), 0));
+        return {std::move(lo), std::move(hi)};
+    }
+    void smooth_solution_per_bdd(REAL* dev_out) { check(bddmma_smooth_solution_batch(b_, dev_out, 1)); }
+    std::vector<REAL> smooth_solution_per_bdd_host(const size_t total_layers)
+    {
+        std::vector<REAL> x(total_layers);
+        check(bddmma_smooth_solution_batch(b_, x.data(), 0));
+        return x;
+    }
+    void grad_smooth_lower_bound_per_bdd(const REAL* dev_grad_lb_per_bdd, REAL* dev_grad_lo_out, REAL* dev_grad_hi_out)
+    {
+        check(bddmma_grad_smooth_lower_bound_per_bdd_batch(b_, dev_grad_lb_per_bdd, dev_grad_lo_out, dev_grad_hi_out, 1));
+    }
+    std::pair<std::vector<REAL>, std::vector<REAL>> grad_smooth_lower_bound_per_bdd(const std::vector<REAL>& grad_lb_per_bdd, const size_t total_layers)
+    {
+        std::vector<REAL> lo(total_layers), hi(total_layers);
+        check(bddmma_grad_smooth_lower_bound_per_bdd_batch(b_, grad_lb_per_bdd.data(), lo.data(), hi.data(), 0));
+        return {std::move(lo), std::move(hi)};
+    }
     // stream_wait — the batch's later calls start after everything queued on `hip_stream` so far; stream_signal — the reverse
     // (bddmma_stream_wait_batch / bddmma_stream_signal_batch)
     void stream_wait(void* hip_stream) { check(bddmma_stream_wait_batch(b_, hip_stream)); }

@@ -506,6 +506,27 @@ int bddmma_grad_min_marginal_diff_batch(bddmma_batch* b, const void* grad_mm, vo
         return i->grad_min_marginal_diff(grad_mm, grad_lo_out, grad_hi_out, on_device);
     });
 }
+int bddmma_sum_marginals_batch(bddmma_batch* b, int log_probs, void* sm0, void* sm1, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!sm0 || !sm1) { i->err = "batch sum_marginals: null output pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        return i->sum_marginals(log_probs, sm0, sm1, on_device);
+    });
+}
+int bddmma_smooth_solution_batch(bddmma_batch* b, void* out, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!out) { i->err = "batch smooth_solution: null output pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        return i->smooth_solution(out, on_device);
+    });
+}
+int bddmma_grad_smooth_lower_bound_per_bdd_batch(bddmma_batch* b, const void* grad_lb_per_bdd, void* grad_lo_out, void* grad_hi_out, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!grad_lb_per_bdd || !grad_lo_out || !grad_hi_out) { i->err = "batch grad_smooth_lower_bound_per_bdd: null pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        return i->grad_smooth_lower_bound_per_bdd(grad_lb_per_bdd, grad_lo_out, grad_hi_out, on_device);
+    });
+}
 int bddmma_batch_time_iterations(bddmma_batch* b, double omega, uint64_t n, double* ms)
 {
     return guarded_batch(b, [&](BatchBase* i) {

@@ -671,28 +671,39 @@ __global__ void k_ema(REAL* __restrict__ avg, const REAL* __restrict__ cur, REAL
 
 // ---- sum-marginals (SolverT::sum_marginals; the sweeps: kernels/summarg.hpp)
 // log sum-marginals -> probabilities (ProcessSumMarginals with get_log_probs = false, bdd_cuda_base.cu:1001-1006); exp(-inf) = 0.  Full-accuracy exp.
+// (the per-layer expressions of k_exp_pair, k_smooth_solution and k_grad_lb are written once, as ew_*: the epilogue of
+// k_small_summarg_batch, kernels/batchsm.hpp, evaluates the same ones)
+template <typename REAL>
+__device__ __forceinline__ REAL ew_exp(REAL a)
+{
+    return sizeof(REAL) == 4 ? (REAL)expf((float)a) : (REAL)exp((double)a);
+}
 template <typename REAL>
 __global__ void k_exp_pair(REAL* __restrict__ a, REAL* __restrict__ b, uint32_t n)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
-        a[i] = sizeof(REAL) == 4 ? (REAL)expf((float)a[i]) : (REAL)exp((double)a[i]);
-        b[i] = sizeof(REAL) == 4 ? (REAL)expf((float)b[i]) : (REAL)exp((double)b[i]);
+        a[i] = ew_exp(a[i]);
+        b[i] = ew_exp(b[i]);
     }
 }
 // ComputeSmoothSolution (bdd_cuda_base.cu:1027-1048): exp(hi - c) / (exp(lo - c) + exp(hi - c)), c = max(lo, hi), of the log sum-marginals.
 // A layer no root-to-top path crosses (both -inf; the reference's -1e30 sentinels give 0.5 there) gives 0.5 here too.
 template <typename REAL>
+__device__ __forceinline__ REAL ew_smooth_solution(REAL lo, REAL hi)
+{
+    const REAL c = lo > hi ? lo : hi;
+    if (!(c > REAL(-__builtin_huge_val()))) return REAL(0.5);
+    const REAL e_lo = sizeof(REAL) == 4 ? (REAL)expf((float)(lo - c)) : (REAL)exp((double)(lo - c));
+    const REAL e_hi = sizeof(REAL) == 4 ? (REAL)expf((float)(hi - c)) : (REAL)exp((double)(hi - c));
+    return e_hi / (e_lo + e_hi);
+}
+template <typename REAL>
 __global__ void k_smooth_solution(const REAL* __restrict__ sm_lo, const REAL* __restrict__ sm_hi, REAL* __restrict__ out, uint32_t n)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const REAL lo = sm_lo[i], hi = sm_hi[i];
-    const REAL c = lo > hi ? lo : hi;
-    if (!(c > REAL(-__builtin_huge_val()))) { out[i] = REAL(0.5); return; }
-    const REAL e_lo = sizeof(REAL) == 4 ? (REAL)expf((float)(lo - c)) : (REAL)exp((double)(lo - c));
-    const REAL e_hi = sizeof(REAL) == 4 ? (REAL)expf((float)(hi - c)) : (REAL)exp((double)(hi - c));
-    out[i] = e_hi / (e_lo + e_hi);
+    out[i] = ew_smooth_solution(sm_lo[i], sm_hi[i]);
 }
 
 // ---- the single-shot backward operators (SolverT::gr_*; bdd_cuda_learned_mma.cu:387-416, 1025-1187)
@@ -746,14 +757,18 @@ __global__ void __launch_bounds__(256) k_load_checked(LoadArrays<REAL> a, uint32
 }
 // grad_lower_bound_per_bdd (:387-416): the bound of a BDD is the cost of its solution x, so grad_hi = x * glb[bdd], grad_lo = (1 - x) * glb[bdd];
 // x is the arg-min path (char 0 / 1) or the smooth solution.  out_hi may be x itself (every thread reads its x first).
+template <typename REAL>
+__device__ __forceinline__ REAL ew_grad_lb_hi(REAL xl, REAL gb) { return xl * gb; }
+template <typename REAL>
+__device__ __forceinline__ REAL ew_grad_lb_lo(REAL xl, REAL gb) { return (REAL(1) - xl) * gb; }
 template <typename REAL, typename XT>
 __global__ void k_grad_lb(const XT* x, const REAL* __restrict__ glb, const int32_t* __restrict__ layer_bdd, REAL* out_lo, REAL* out_hi, uint32_t n)
 {
     const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
     if (l >= n) return;
     const REAL xl = REAL(x[l]), gb = glb[layer_bdd[l]];
-    out_hi[l] = xl * gb;
-    out_lo[l] = (REAL(1) - xl) * gb;
+    out_hi[l] = ew_grad_lb_hi(xl, gb);
+    out_lo[l] = ew_grad_lb_lo(xl, gb);
 }
 // grad_distribute_delta (:1025-1065): distribute_delta added the deferred difference m to hi where m > 0 and -m to lo otherwise
 template <typename REAL>

@@ -1,5 +1,6 @@
 // kernels/summarg.hpp — the sweeps in the (log-sum-exp, +) semiring: sum-marginals (bdd_cuda_base.cu:788-1025, sum_marginals_cuda).
-// Included by solver_sm.hpp only (translation units solver_sm_f32.hip / solver_sm_f64.hip), behind kernels.hpp.
+// The two kernels are instantiated by solver_sm.hpp only (translation units solver_sm_f32.hip / solver_sm_f64.hip); their bodies also run
+// inside k_small_summarg_batch (kernels/batchsm.hpp).  Behind kernels.hpp.
 //
 // Two pull sweeps (kernels/pull.hpp: one launch per pack family, one workgroup per pack; the skeleton of a hop and the fixed orders of
 // its folds are written there):
@@ -43,13 +44,13 @@ __device__ __forceinline__ REAL sm_finish(REAL m, REAL s)
 __host__ __device__ inline size_t sm_lds_bytes(size_t real_size, uint32_t ww) { return (7 * real_size + 4) * (size_t)ww; }
 
 
+// The sweeps' bodies for the pack `pc`: k_sm_fwd / k_sm_bwd run them with the workgroup's pack and PullBlockBar (__syncthreads()) as BAR,
+// k_small_summarg_batch (kernels/batchsm.hpp) with a wave's pack and a wave-level ordering point.
 // (par_ptr / par: kernels/pull.hpp, pull_parents)
-template <typename REAL, bool NARROW, bool GLOBAL>
-__global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_sm_fwd(DevPtrs<REAL> d, PackDev pk, const uint32_t* par_ptr, const uint32_t* par, uint32_t ww,
-                                                                       unsigned char* scratch)
+template <typename REAL, bool NARROW, typename BAR>
+__device__ __forceinline__ void sm_fwd_body(const DevPtrs<REAL>& d, const PackDev& pk, const PullPack<REAL>& pc, const uint32_t* par_ptr, const uint32_t* par,
+                                            uint32_t ww)
 {
-    if (blockIdx.x >= pk.n_packs) return;
-    const PullPack<REAL> pc = pull_pack<REAL, NARROW, GLOBAL>(d, pk, ww, scratch, sm_lds_bytes(sizeof(REAL), ww));
     REAL* const A = pc.base;  // [hop parity][arc][slot]
     const REAL NINF = -inf_v<REAL>();
     uint32_t cur = 0;
@@ -71,16 +72,23 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_sm_fwd(DevPtrs<R
             Ac[ww + j] = f - d.lohi[2 * (size_t)nd.layer + 1];
             d.F[nb + j] = f;
         });
-        __syncthreads();  // this hop's values before the next hop's pulls; the next hop writes the other parity
+        BAR::sync();  // this hop's values before the next hop's pulls; the next hop writes the other parity
     }
 }
 
-// (the parent tables are not read: the leading arguments are those of every pull kernel, SolverT::launch_pull)
 template <typename REAL, bool NARROW, bool GLOBAL>
-__global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_sm_bwd(DevPtrs<REAL> d, PackDev pk, const uint32_t*, const uint32_t*, uint32_t ww, unsigned char* scratch)
+__global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_sm_fwd(DevPtrs<REAL> d, PackDev pk, const uint32_t* par_ptr, const uint32_t* par, uint32_t ww,
+                                                                       unsigned char* scratch)
 {
     if (blockIdx.x >= pk.n_packs) return;
     const PullPack<REAL> pc = pull_pack<REAL, NARROW, GLOBAL>(d, pk, ww, scratch, sm_lds_bytes(sizeof(REAL), ww));
+    sm_fwd_body<REAL, NARROW, PullBlockBar>(d, pk, pc, par_ptr, par, ww);
+}
+
+// (the parent tables are not read: the leading arguments are those of every pull sweep)
+template <typename REAL, bool NARROW, typename BAR>
+__device__ __forceinline__ void sm_bwd_body(const DevPtrs<REAL>& d, const PackDev& pk, const PullPack<REAL>& pc, const uint32_t*, const uint32_t*, uint32_t ww)
+{
     REAL* const Tb = pc.base;                   // [hop parity][slot]: T~
     REAL* const P0 = pc.base + 2 * (size_t)ww;  // path values through the lo arc per slot, then exp(value - the layer's maximum)
     REAL* const P1 = pc.base + 3 * (size_t)ww;  // ... the hi arc
@@ -110,11 +118,11 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_sm_bwd(DevPtrs<R
             P0[j] = f + a;
             P1[j] = f + b;
         });
-        __syncthreads();
+        BAR::sync();
         // ---- maxima
-        pull_layer_fold(pc, Lid, n, path, [](Pull2<REAL> v, Pull2<REAL> w) { return Pull2<REAL>{rmax(v.lo, w.lo), rmax(v.hi, w.hi)}; }, keep, run,
-                        [&](uint32_t l, Pull2<REAL> m) { M0[l] = m.lo; M1[l] = m.hi; });
-        __syncthreads();
+        pull_layer_fold_bar<BAR>(pc, Lid, n, path, [](Pull2<REAL> v, Pull2<REAL> w) { return Pull2<REAL>{rmax(v.lo, w.lo), rmax(v.hi, w.hi)}; }, keep, run,
+                                 [&](uint32_t l, Pull2<REAL> m) { M0[l] = m.lo; M1[l] = m.hi; });
+        BAR::sync();
         // ---- exp(value - maximum), every node its own; then the sums
         for (uint32_t j = pc.tid; j < n; j += pc.T) {
             const uint32_t l = Lid[j];
@@ -124,14 +132,24 @@ __global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_sm_bwd(DevPtrs<R
                 P1[j] = m1 > NINF ? sm_exp(P1[j] - m1) : REAL(0);
             }
         }
-        __syncthreads();
-        pull_layer_fold(pc, Lid, n, path, pull_add<REAL>, keep, run,
-                        [&](uint32_t l, Pull2<REAL> s) {
-                            d.mm0_out[lbase + l] = sm_finish(M0[l], s.lo);
-                            d.mm1_out[lbase + l] = sm_finish(M1[l], s.hi);
-                        });
-        __syncthreads();  // the next hop overwrites every array (M0 is its T~ buffer)
+        BAR::sync();
+        pull_layer_fold_bar<BAR>(pc, Lid, n, path, pull_add<REAL>, keep, run,
+                                 [&](uint32_t l, Pull2<REAL> s) {
+                                     d.mm0_out[lbase + l] = sm_finish(M0[l], s.lo);
+                                     d.mm1_out[lbase + l] = sm_finish(M1[l], s.hi);
+                                 });
+        BAR::sync();  // the next hop overwrites every array (M0 is its T~ buffer)
     }
+}
+
+// (the leading arguments are those of every pull kernel, SolverT::launch_pull)
+template <typename REAL, bool NARROW, bool GLOBAL>
+__global__ void __launch_bounds__(NARROW ? 64 : WIDE_THREADS) k_sm_bwd(DevPtrs<REAL> d, PackDev pk, const uint32_t* par_ptr, const uint32_t* par, uint32_t ww,
+                                                                       unsigned char* scratch)
+{
+    if (blockIdx.x >= pk.n_packs) return;
+    const PullPack<REAL> pc = pull_pack<REAL, NARROW, GLOBAL>(d, pk, ww, scratch, sm_lds_bytes(sizeof(REAL), ww));
+    sm_bwd_body<REAL, NARROW, PullBlockBar>(d, pk, pc, par_ptr, par, ww);
 }
 
 }  // namespace bddmma

@@ -205,6 +205,12 @@ struct BatchBase {
     // (kernels/batchmm.hpp; include/bdd_mma.h: bddmma_min_marginal_diff_batch, bddmma_grad_min_marginal_diff_batch)
     virtual int min_marginal_diff(void* out, int on_device) = 0;
     virtual int grad_min_marginal_diff(const void* grad_mm, void* grad_lo, void* grad_hi, int on_device) = 0;
+    // SolverBase::sum_marginals (unsorted, no var) / smooth_solution / grad_lower_bound_per_bdd (smooth = 1) of every member, one launch
+    // per kernel instantiation present (kernels/batchsm.hpp; include/bdd_mma.h: bddmma_sum_marginals_batch, bddmma_smooth_solution_batch,
+    // bddmma_grad_smooth_lower_bound_per_bdd_batch)
+    virtual int sum_marginals(int log_probs, void* sm0, void* sm1, int on_device) = 0;
+    virtual int smooth_solution(void* out, int on_device) = 0;
+    virtual int grad_smooth_lower_bound_per_bdd(const void* grad_lb, void* grad_lo, void* grad_hi, int on_device) = 0;
     // the batch stream behind everything queued on `other` so far / the reverse, by an event the batch owns; the host does not wait
     virtual int stream_wait(hipStream_t other) = 0;
     virtual int stream_signal(hipStream_t other) = 0;

@@ -10,6 +10,7 @@
 #include "kernels/batchcosts.hpp"
 #include "kernels/batchbound.hpp"
 #include "kernels/batchmm.hpp"
+#include "kernels/batchsm.hpp"
 #include "kernels/smallhist.hpp"
 
 namespace bddmma {
@@ -45,7 +46,7 @@ struct BatchT final : BatchBase {
         for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1, ev_order})
             if (e) (void)hipEventDestroy(e);
         if (d_items) (void)hipFree(d_items);
-        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad, (void*)d_bm_items, (void*)d_bm_stage, (void*)d_bm_bad})
+        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad, (void*)d_bm_items, (void*)d_bm_stage, (void*)d_bm_bad, (void*)d_bsm_items, (void*)d_bsm_stage})
             if (q) (void)hipFree(q);
         if (d_ctl) (void)hipFree(d_ctl);
         if (h_ctl) (void)hipHostFree(h_ctl);
@@ -1144,6 +1145,161 @@ struct BatchT final : BatchBase {
         const int rc2 = join_out();
         if (e != hipSuccess) { err = std::string(me) + ": " + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
         return rc2;
+    }
+    // ---- the log-sum-exp family, all members at once (kernels/batchsm.hpp: k_small_summarg_batch; the kernel compiles in
+    // solver_bsm_f32.hip / _f64.hip): sum-marginals, smooth solutions and the gradient of the smooth per-BDD bounds are one kernel with
+    // three epilogues.  Items sorted by the members' wave count, as the min-marginal items are: one launch per wave count present.  Host
+    // arrays pass through one staging buffer the batch owns (per-BDD values | first output | second output); it, the parent tables of
+    // every member's sm_prepare() and the bound items of the argument check exist before any member is touched.
+    struct BsmGroup {
+        SmBatchFn<REAL> fn;
+        uint32_t threads, lds, first, count;
+    };
+    std::vector<BsmGroup> bsm_groups;
+    SmItem<REAL>* d_bsm_items = nullptr;
+    REAL* d_bsm_stage = nullptr;
+    uint64_t bsm_layers = 0, bsm_bdds = 0;     // values of all members' layers / BDDs
+    bool bsm_ready = false;
+
+    // grad: the call is the gradient, whose argument check reads the bound items; host_arrays: the call needs the staging buffer
+    int bsm_prepare(bool grad, bool host_arrays)
+    {
+        const uint32_t n = (uint32_t)m.size();
+        constexpr uint32_t RS = (uint32_t)sizeof(REAL);
+        if (!bsm_ready) {
+            for (S* s : m)
+                if (int rc = s->sm_prepare()) { err = s->err; return rc; }
+            std::vector<uint32_t> ord(n);
+            for (uint32_t i = 0; i < n; ++i) ord[i] = i;
+            std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return m[a]->small_nw < m[b]->small_nw; });
+            std::vector<uint64_t> src(n), src_b(n);
+            uint64_t total = 0, total_b = 0;
+            for (uint32_t i = 0; i < n; ++i) {
+                src[i] = total;
+                src_b[i] = total_b;
+                total += m[i]->n_layers;
+                total_b += m[i]->n_bdds;
+            }
+            if (total > 0xFFFFFFFFull || total_b > 0xFFFFFFFFull) { err = "batch sum_marginals: too many layers"; return BDDMMA_ERR_UNSUPPORTED; }
+            std::vector<SmItem<REAL>> items(n);
+            std::vector<BsmGroup> groups_;
+            for (uint32_t j = 0; j < n; ++j) {
+                const S* s = m[ord[j]];
+                items[j] = SmItem<REAL>{s->ptrs(nullptr), s->pdev(s->nb_, 0, 0), s->d_sm_nptr, s->d_sm_npar, s->d_bdd, s->pack_width, s->small.n_packs,
+                                        (uint32_t)src[ord[j]], (uint32_t)src_b[ord[j]], ord[j]};
+                if (groups_.empty() || s->small_nw != m[ord[groups_.back().first]]->small_nw)
+                    groups_.push_back(BsmGroup{sm_batch_fn<REAL>(s->small_nw), 64u * (uint32_t)s->small_nw, 0u, j, 0u});
+                BsmGroup& g = groups_.back();
+                g.lds = std::max(g.lds, s->small.n_packs * bsm_region_bytes(RS, s->pack_width));
+                ++g.count;
+            }
+            for (const BsmGroup& g : groups_) {
+                // (never taken for a fused_small member: it has at most SMALL_MAX_PACKS = 16 packs of 64 slots, the condition of the
+                // second-generation resident records, so at most 16 x 3 840 B = 60 KiB in double, below every lds_cu the layout accepts)
+                if (g.lds > m[0]->lds_cu) { err = "batch sum_marginals: the packs' arrays do not fit the LDS"; return BDDMMA_ERR_STATE; }
+                if (int rc = raise_lds_limit(reinterpret_cast<const void*>(g.fn), g.lds)) return rc;
+            }
+            if (!d_bsm_items) HIPCHK(hipMalloc((void**)&d_bsm_items, n * sizeof(SmItem<REAL>)));
+            HIPCHK(hipMemcpy(d_bsm_items, items.data(), n * sizeof(SmItem<REAL>), hipMemcpyHostToDevice));
+            bsm_groups = std::move(groups_);
+            bsm_layers = total;
+            bsm_bdds = total_b;
+            bsm_ready = true;
+        }
+        if (grad)
+            if (int rc = bb_prepare(false, false)) return rc;
+        if (host_arrays && !d_bsm_stage) HIPCHK(hipMalloc((void**)&d_bsm_stage, std::max<uint64_t>(bsm_bdds + 2 * bsm_layers, 1) * sizeof(REAL)));
+        return BDDMMA_OK;
+    }
+    // One call of the family: `mode` the epilogue (kernels/batchsm.hpp: BSM_*), g the per-BDD gradient (BSM_GRAD only), o1 null for
+    // BSM_SMOOTH.  The arguments are checked and bsm_prepare() has run.
+    int bsm_run(const char* me, uint32_t mode, const void* g_in, void* out0, void* out1, int on_dev)
+    {
+        int rc;
+        if ((rc = members_in())) return rc;   // (no costs-to-terminal are needed: the sweeps compute their own potentials)
+        // ---- the members are touched from here on (F, T, d_tmp0 / d_tmp1)
+        const REAL* g = (const REAL*)g_in;
+        REAL *o0 = (REAL*)out0, *o1 = (REAL*)out1;
+        hipError_t e = hipSuccess;
+        if (!on_dev) {
+            if (g) {
+                e = hipMemcpyAsync(d_bsm_stage, g_in, bsm_bdds * sizeof(REAL), hipMemcpyHostToDevice, stream);
+                g = d_bsm_stage;
+            }
+            o0 = d_bsm_stage + bsm_bdds;
+            if (out1) o1 = o0 + bsm_layers;
+        }
+        for (size_t k = 0; k < bsm_groups.size() && e == hipSuccess; ++k) {
+            const BsmGroup& G = bsm_groups[k];
+            hipLaunchKernelGGL(G.fn, dim3(G.count), dim3(G.threads), G.lds, stream, (const SmItem<REAL>*)(d_bsm_items + G.first), mode, g, o0, o1);
+            e = hipGetLastError();
+        }
+        // the host-side state after SolverT::sm_launch_fwd and sm_launch_bwd: the stored potentials are log-partition values
+        for (S* s : m) {
+            s->fwd_valid = s->bwd_valid = s->lb_valid = false;
+            s->lb_cached = false;
+            ++s->lb_gen;
+        }
+        if (!on_dev) {
+            if (e == hipSuccess) e = hipMemcpyAsync(out0, o0, bsm_layers * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess && out1) e = hipMemcpyAsync(out1, o1, bsm_layers * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        }
+        const int rc2 = join_out();
+        if (e != hipSuccess) { err = std::string(me) + ": " + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        return rc2;
+    }
+    int sum_marginals(int log_probs, void* sm0, void* sm1, int on_dev) override
+    {
+        int rc;
+        const char* const me = "batch sum_marginals";
+        if (!sm0 || !sm1) { err = std::string(me) + ": null output pointer"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if ((rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bsm_prepare(false, !on_dev))) return rc;
+        return bsm_run(me, log_probs ? BSM_LOG : BSM_PROB, nullptr, sm0, sm1, on_dev);
+    }
+    int smooth_solution(void* out, int on_dev) override
+    {
+        int rc;
+        const char* const me = "batch smooth_solution";
+        if (!out) { err = std::string(me) + ": null output pointer"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if ((rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bsm_prepare(false, !on_dev))) return rc;
+        return bsm_run(me, BSM_SMOOTH, nullptr, out, nullptr, on_dev);
+    }
+    int grad_smooth_lower_bound_per_bdd(const void* grad_lb, void* grad_lo, void* grad_hi, int on_dev) override
+    {
+        int rc;
+        const char* const me = "batch grad_smooth_lower_bound_per_bdd";
+        const uint32_t n = (uint32_t)m.size();
+        if (!grad_lb || !grad_lo || !grad_hi) { err = std::string(me) + ": null pointer"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if ((rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bsm_prepare(true, !on_dev))) return rc;
+        // the argument check, before any member or output is touched: host values here, device values by one launch for all members
+        // (k_small_grad_lb_check over the bound items: the same per-BDD offsets) and the call's one read
+        uint32_t bad = 0xFFFFFFFFu;
+        if (!on_dev) {
+            const REAL* h = (const REAL*)grad_lb;
+            for (uint32_t i = 0; i < n && bad == 0xFFFFFFFFu; ++i) {
+                for (uint64_t b = 0; b < m[i]->n_bdds; ++b)
+                    if (!std::isfinite(h[b])) { bad = i; break; }
+                h += m[i]->n_bdds;
+            }
+        } else {
+            HIPCHK(hipMemsetAsync(d_bb_bad, 0xFF, sizeof(uint32_t), stream));
+            hipLaunchKernelGGL(bound_check_fn<REAL>(), dim3(n), dim3(256), 0, stream, (const BoundItem<REAL>*)d_bb_items, (const REAL*)grad_lb, d_bb_bad);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&bad, d_bb_bad, sizeof(bad), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+        if (bad != 0xFFFFFFFFu) {
+            err = "batch member " + std::to_string(bad) + ": some of its grad_lb_per_bdd are not finite";
+            return BDDMMA_ERR_INVALID_ARGUMENT;
+        }
+        return bsm_run(me, BSM_GRAD, grad_lb, grad_lo, grad_hi, on_dev);
     }
     int stream_wait(hipStream_t other) override
     {

@@ -822,6 +822,54 @@ class bdd_hip_batch:
         self._check(call(self._h, _ptr(g), _ptr(lo), _ptr(hi), 0), self._h)
         return lo, hi
 
+    # ---- sum-marginals, smooth solutions and the smooth bound gradient (include/bdd_mma.h: bddmma_sum_marginals_batch and the two entries behind it)
+    def sum_marginals_cuda(self, get_log_probs=True, out=None):
+        """sum_marginals_cuda(get_sorted=False, get_log_probs) of every member, one workgroup per member: (sm_lo, sm_hi), the members'
+        REAL[nr_layers] one behind the other in the members' order, each in the unsorted layer order (a member's
+        get_primal_variable_index() names the variables).  out: (sm_lo, sm_hi) device buffers, written in the batch stream's order (the
+        host does not wait); without it two new NumPy arrays."""
+        n = sum(s.nr_layers() for s in self.solvers)
+        vt = self.solvers[0].value_type
+        call = self._L.bddmma_sum_marginals_batch
+        if out is not None:
+            assert len(out) == 2 and all(_is_dev(x) for x in out), "out: (sm_lo, sm_hi) device buffers"
+            self._check(call(self._h, 1 if get_log_probs else 0, _dev_ptr(out[0], n, vt), _dev_ptr(out[1], n, vt), 1), self._h)
+            return out[0], out[1]
+        lo, hi = np.zeros(n, vt), np.zeros(n, vt)
+        self._check(call(self._h, 1 if get_log_probs else 0, _ptr(lo), _ptr(hi), 0), self._h)
+        return lo, hi
+
+    def smooth_solution_per_bdd(self, out=None):
+        """smooth_solution_per_bdd() of every member, one workgroup per member: the members' REAL[nr_layers] one behind the other.
+        out: a device buffer, written in the batch stream's order (the host does not wait); without it a new NumPy array."""
+        n = sum(s.nr_layers() for s in self.solvers)
+        vt = self.solvers[0].value_type
+        if out is not None:
+            assert _is_dev(out), "out: a device buffer"
+            self._check(self._L.bddmma_smooth_solution_batch(self._h, _dev_ptr(out, n, vt), 1), self._h)
+            return out
+        out = np.zeros(n, vt)
+        self._check(self._L.bddmma_smooth_solution_batch(self._h, _ptr(out), 0), self._h)
+        return out
+
+    def grad_smooth_lower_bound_per_bdd(self, grad_lb, out=None):
+        """grad_smooth_lower_bound_per_bdd(grad_lb_i) of every member i, one workgroup per member: (grad_lo, grad_hi), the members'
+        REAL[nr_layers] one behind the other; grad_lb: the members' REAL[nr_bdds] one behind the other.  A device tensor needs
+        out = (grad_lo, grad_hi) device buffers, a NumPy array gives two new NumPy arrays."""
+        n = sum(s.nr_layers() for s in self.solvers)
+        nb = sum(s.nr_bdds() for s in self.solvers)
+        vt = self.solvers[0].value_type
+        call = self._L.bddmma_grad_smooth_lower_bound_per_bdd_batch
+        if _is_dev(grad_lb):
+            assert out is not None and len(out) == 2 and all(_is_dev(x) for x in out), "device gradients need device output buffers: out=(grad_lo, grad_hi)"
+            self._check(call(self._h, _dev_ptr(grad_lb, nb, vt), _dev_ptr(out[0], n, vt), _dev_ptr(out[1], n, vt), 1), self._h)
+            return out[0], out[1]
+        g = np.ascontiguousarray(grad_lb, dtype=vt)
+        assert g.size == nb, f"expected {nb} values, got {g.size}"
+        lo, hi = np.zeros(n, vt), np.zeros(n, vt)
+        self._check(call(self._h, _ptr(g), _ptr(lo), _ptr(hi), 0), self._h)
+        return lo, hi
+
     # ---- ordering against other streams (include/bdd_mma.h: bddmma_stream_wait_batch / bddmma_stream_signal_batch)
     def stream_wait(self, hip_stream=0):
         """what the batch's calls queue from now on starts after everything queued so far on `hip_stream` (a raw hipStream_t as an

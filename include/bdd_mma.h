@@ -610,6 +610,24 @@ int bddmma_min_marginal_diff_batch(bddmma_batch* b, void* out, int on_device);
  * BDDMMA_ERR_INVALID_ARGUMENT, bddmma_batch_last_error naming the first offending member and grad_mm, the outputs untouched (host
  * values are checked on the host, device values by one check launch for all members).  State: as bddmma_min_marginal_diff_batch. */
 int bddmma_grad_min_marginal_diff_batch(bddmma_batch* b, const void* grad_mm, void* grad_lo_out, void* grad_hi_out, int on_device);
+/* The log-sum-exp family of every member (kernels/batchsm.hpp), one launch per wave count present each: one workgroup per member, a wave
+ * per pack, running the two sweeps of bddmma_sum_marginals on the wave's pack and the call's per-layer expression behind them.  Arrays,
+ * the on_device flag, host staging, device ordering and the refusals are those of the entry points above; every output pointer is
+ * required.  Layer arrays are in the unsorted layer order only (bddmma_get_primal_variable_index gives the variables); results are
+ * bit-equal to the per-member calls in float and in double.  No costs-to-terminal are needed, so no member runs a sweep of its own first.
+ * State of every member afterwards, as after the per-member calls: the stored costs-from-root and costs-to-terminal hold log-partition
+ * values and both sweep states and the cached bound are invalid (the next call that needs them recomputes them); arc costs, deferred
+ * differences and delta are unchanged.
+ *
+ * bddmma_sum_marginals_batch: bddmma_sum_marginals(member i, sorted 0, log_probs, NULL, its parts of sm0 and sm1, ..) for every member i. */
+int bddmma_sum_marginals_batch(bddmma_batch* b, int log_probs, void* sm0, void* sm1, int on_device);
+/* bddmma_smooth_solution(member i, its part of out, ..) for every member i: 0.5 on a layer no root-to-top path crosses. */
+int bddmma_smooth_solution_batch(bddmma_batch* b, void* out, int on_device);
+/* bddmma_grad_lower_bound_per_bdd(member i, its parts, smooth 1, ..) for every member i; grad_lb_per_bdd: the members' REAL[nr_bdds] one
+ * behind the other.  A value of it that is not finite: BDDMMA_ERR_INVALID_ARGUMENT, bddmma_batch_last_error naming the first offending
+ * member and grad_lb_per_bdd, members and outputs untouched (host values are checked on the host, device values by one check launch for
+ * all members). */
+int bddmma_grad_smooth_lower_bound_per_bdd_batch(bddmma_batch* b, const void* grad_lb_per_bdd, void* grad_lo_out, void* grad_hi_out, int on_device);
 /* bddmma_run_solver(member, NULL, max_iter, tolerance, improvement_slope, time_limit, 0, &res[i]) for every member i: each member's tests
  * run inside its workgroup against its own control block and each stops on its own criterion; the host relaunches chunks of iterations
  * until every member has stopped or reached max_iter.  res (bddmma_batch_size entries, may be NULL): member i's iterations, bounds and
