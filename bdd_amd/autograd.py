@@ -167,9 +167,19 @@ def _incoming(g, like):
 def ComputePrimalSolution(solvers, lo_costs_batch, hi_costs_batch, def_mm_batch, init_delta, delta_growth_rate, num_itr_lb, verbose=False):
     """bdd_cuda_torch.py:12-20: sets every solver's costs and rounds with the incremental min-marginal agreement rounding
     (bddmma_incremental_mm_agreement_rounding); a list with one solution (a list of 0.0 / 1.0 per variable, empty when none was found)
-    per solver.  The solvers' costs stay perturbed, as in the reference."""
+    per solver.  The solvers' costs stay perturbed, as in the reference.  For a bdd_hip_batch ONE batch.set_solver_costs and ONE
+    batch.primal_rounding_incremental (bddmma_incremental_mm_agreement_rounding_batch: every round one workgroup per member), none on a
+    member, with the list form's results bit for bit.  The list form runs for a list, with verbose, and for a batch whose first call
+    refuses with BDDMMA_ERR_STATE."""
     z = _Sizes(solvers)
     z.check(("lo_costs_batch", lo_costs_batch, z.layers), ("hi_costs_batch", hi_costs_batch, z.layers), ("def_mm_batch", def_mm_batch, z.layers))
+    if z.batch is not None and not verbose:
+        with _Ordered([z.batch]):
+            batched = _batch_set_costs(z.batch, lo_costs_batch, hi_costs_batch, def_mm_batch)
+            if batched:
+                out = z.batch.primal_rounding_incremental(init_delta, delta_growth_rate, num_itr_lb)
+        if batched:
+            return out
     out = []
     with _Ordered(z.solvers):
         for s, l in zip(z.solvers, z.slices(z.layers)):

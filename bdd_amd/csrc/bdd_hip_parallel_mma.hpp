@@ -466,7 +466,10 @@ class bdd_hip_batch {
     explicit bdd_hip_batch(const std::vector<std::reference_wrapper<bdd_hip_parallel_mma<REAL>>>& solvers)
     {
         std::vector<bddmma_solver*> h;
-        for (bdd_hip_parallel_mma<REAL>& s : solvers) h.push_back(s.handle());
+        for (bdd_hip_parallel_mma<REAL>& s : solvers) {
+            h.push_back(s.handle());
+            nv_.push_back(bddmma_nr_variables(s.handle()));
+        }
         if (bddmma_batch_create(&b_, h.data(), h.size()) != BDDMMA_OK) throw std::runtime_error(std::string("bdd_hip_batch: ") + bddmma_batch_last_error(nullptr));
     }
     ~bdd_hip_batch() { bddmma_batch_destroy(b_); }
@@ -611,6 +614,27 @@ class bdd_hip_batch {
         check(bddmma_grad_smooth_lower_bound_per_bdd_batch(b_, grad_lb_per_bdd.data(), lo.data(), hi.data(), 0));
         return {std::move(lo), std::move(hi)};
     }
+    // incremental_mm_agreement_rounding(...) of every member (not verbose), every round one workgroup per member: member i's solution, empty
+    // where none was found.  rounds (may be null): the index of the round in which each member's agreement was seen, num_rounds where none
+    // was.  Contract: bddmma_incremental_mm_agreement_rounding_batch.
+    std::vector<std::vector<char>> incremental_mm_agreement_rounding(const double init_delta, const double delta_growth_rate, const size_t num_itr_lb,
+                                                                      const size_t num_rounds = 500, const uint32_t seed = 0, std::vector<uint64_t>* rounds = nullptr)
+    {
+        size_t total = 0;
+        for (const size_t v : nv_) total += v;
+        std::vector<char> sol(total > 0 ? total : 1);
+        std::vector<int> found(size());
+        if (rounds) rounds->assign(size(), 0);
+        check(bddmma_incremental_mm_agreement_rounding_batch(b_, init_delta, delta_growth_rate, num_itr_lb, num_rounds, seed, sol.data(), found.data(),
+                                                             rounds ? rounds->data() : nullptr));
+        std::vector<std::vector<char>> out(size());
+        size_t at = 0;
+        for (size_t i = 0; i < out.size(); ++i) {
+            if (found[i]) out[i].assign(sol.begin() + at, sol.begin() + at + nv_[i]);
+            at += nv_[i];
+        }
+        return out;
+    }
     // stream_wait — the batch's later calls start after everything queued on `hip_stream` so far; stream_signal — the reverse
     // (bddmma_stream_wait_batch / bddmma_stream_signal_batch)
     void stream_wait(void* hip_stream) { check(bddmma_stream_wait_batch(b_, hip_stream)); }
@@ -636,6 +660,7 @@ class bdd_hip_batch {
         if (rc != BDDMMA_OK) throw std::runtime_error(std::string("bdd_hip_batch: ") + bddmma_batch_last_error(b_));
     }
     bddmma_batch* b_ = nullptr;
+    std::vector<size_t> nv_;   // the members' nr_variables()
 };
 
 // lbfgs<bdd_cuda_parallel_mma<REAL>, ...> (include/bdd_solver/lbfgs.h:35-111) over the HIP solver.

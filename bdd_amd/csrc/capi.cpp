@@ -606,6 +606,29 @@ int bddmma_incremental_mm_agreement_rounding(bddmma_solver* s, bddmma_lbfgs* lbf
     });
 }
 
+// ... and both for a batch: bddmma_perturb_primal_costs(member i, NULL, ...) / bddmma_incremental_mm_agreement_rounding(member i, NULL,
+// ..., seed, 0, ...) of every member, one launch per round and wave count present (solver_bt.hpp: BatchT::rounding_round, rounding)
+int bddmma_perturb_primal_costs_batch(bddmma_batch* b, double cur_delta, uint32_t round_index, uint32_t seed, uint32_t* counts, char* sol,
+                                      void* cost_delta_0, void* cost_delta_1)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!counts || !sol) { i->err = "batch perturb_primal_costs: null output pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        return i->perturb_primal_costs(cur_delta, round_index, seed, counts, sol, cost_delta_0, cost_delta_1);
+    });
+}
+int bddmma_incremental_mm_agreement_rounding_batch(bddmma_batch* b, double init_delta, double delta_growth_rate, uint64_t num_itr_lb,
+                                                   uint64_t num_rounds, uint32_t seed, char* sol, int* found, uint64_t* rounds)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!sol || !found) { i->err = "batch rounding: null output pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        if (!(delta_growth_rate > 0) || !(init_delta > 0)) {
+            i->err = "batch rounding: init_delta and delta_growth_rate must be positive";
+            return (int)BDDMMA_ERR_INVALID_ARGUMENT;
+        }
+        return i->rounding(init_delta, delta_growth_rate, num_itr_lb, num_rounds, seed, sol, found, rounds);
+    });
+}
+
 // ---- checkpoint (bdd_cuda_base.cu:1486-1550: every index array of the layout + the costs are archived) -------------------------
 // File: magic, header {precision, #arrays, sizeof(LayoutScalars), sizeof(bddmma_options)}, LayoutScalars, options, the layout arrays
 // as {id, element size, count, data} records (layout.hpp: visit_layout_arrays), then lo / hi / deferred mm / delta.  Loading

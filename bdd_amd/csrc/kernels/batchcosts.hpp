@@ -28,6 +28,48 @@ struct CostsItem {
 // sinks at ns and ns + 1) and of the layer pairs are those of res2_wave_bytes' region without its costs-from-root.
 __host__ __device__ inline uint32_t costs_region_bytes(uint32_t real_size, uint32_t ns, uint32_t nl) { return ((ns + 4u) * real_size + nl * 2u * real_size + 15u) & ~15u; }
 
+// (b) of k_small_set_batch for one pack, by its wave: the region's costs-to-terminal at byte `wb` of the dynamic LDS (the two sinks
+// filled), its layer pairs at `wbC`; T goes to LDS and to `Tg` (the pack's first slot in the member's array).  Returns the pack's bound
+// on lane 0.  Shared with the round kernel of a batch (kernels/batchround.hpp).
+template <typename REAL>
+__device__ __forceinline__ double costs_backward(unsigned char* dyn_lds, uint32_t wb, uint32_t wbC, const rsrc_t& rr, uint32_t rbase, uint32_t nh, uint32_t lane,
+                                                 unsigned char* Tg)
+{
+    using P2 = typename Pair<REAL>::type;
+    auto hop = [&](const u4v& r) {
+        const bool real = r[3] != RES2_PAD;   // padding lanes: both children the bot sink, layer 0 of the pack; their result goes nowhere
+        const uint32_t ll = r[2] & 0xFFFFu, fs = r[2] >> 16;
+        const REAL tl = lds_ld<REAL>(dyn_lds, wb + (r[0] & 0xFFFFu)), th = lds_ld<REAL>(dyn_lds, wb + (r[0] >> 16));
+        const P2 cc = lds_ld<P2>(dyn_lds, wbC + ll);
+        const REAL t = rmin(th + cc.y, tl + cc.x);
+        if (real) {
+            lds_st<REAL>(dyn_lds, wb + fs, t);
+            *reinterpret_cast<REAL*>(Tg + fs) = t;
+        }
+        wave_sync();
+    };
+    // k-th hop processed = hop nh - 1 - k of the pack, its record requested eight hops ahead; past the first hop: any record (never used)
+    const uint32_t nhm1 = nh - 1u;
+    auto ldrec = [&](uint32_t k) -> u4v {
+        const uint32_t h = k < nhm1 ? nhm1 - k : 0u;
+        return __builtin_amdgcn_raw_buffer_load_b128(rr, lane * 16u, (rbase + h * 64u) * 16u, 0);
+    };
+    u4v r0 = ldrec(0), r1 = ldrec(1), r2 = ldrec(2), r3 = ldrec(3), r4 = ldrec(4), r5 = ldrec(5), r6 = ldrec(6), r7 = ldrec(7);
+#define COSTS_HOP(RK, HK)           \
+    hop(RK);                        \
+    RK = ldrec(k + (HK) + 8);       \
+    if (k + (HK) + 1 >= nh) break;
+    for (uint32_t k = 0; k < nh; k += 8) {
+        COSTS_HOP(r0, 0) COSTS_HOP(r1, 1) COSTS_HOP(r2, 2) COSTS_HOP(r3, 3) COSTS_HOP(r4, 4) COSTS_HOP(r5, 5) COSTS_HOP(r6, 6) COSTS_HOP(r7, 7)
+    }
+#undef COSTS_HOP
+    // lower bound contribution of this pack: the double sum of the first hop's roots, small_iterate's tree
+    const u4v rroot = __builtin_amdgcn_raw_buffer_load_b128(rr, lane * 16u, rbase * 16u, 0);
+    double lb = rroot[3] != RES2_PAD ? (double)lds_ld<REAL>(dyn_lds, wb + (rroot[2] >> 16)) : 0.0;
+    for (int off2 = 32; off2 > 0; off2 >>= 1) lb += __shfl_down(lb, off2);
+    return lb;
+}
+
 // (a) the member's part of lo / hi / mm -> lohi (stride 2) and mm_binned (through lpos): k_strided_copy and k_layers_to_entries for every
 //     member at once; a null array is skipped.  No value is checked, as the per-member call checks none.
 // (b) a plain backward sweep of the member, wave p on pack p (n_packs <= NW): the pack's costs-to-terminal and its arc costs in LDS, the
@@ -84,38 +126,7 @@ __global__ void __launch_bounds__(64 * NW) k_small_set_batch(const CostsItem<REA
     }
     if (lane < 2) lds_st<REAL>(dyn_lds, wb + (it.ns + (uint32_t)lane) * S, lane == 0 ? REAL(0) : inf_v<REAL>());  // sinks: cost to terminal 0 (top) / +inf (bot)
     wave_sync();
-    unsigned char* const Tg = reinterpret_cast<unsigned char*>(it.T + slot0);
-    auto hop = [&](const u4v& r) {
-        const bool real = r[3] != RES2_PAD;   // padding lanes: both children the bot sink, layer 0 of the pack; their result goes nowhere
-        const uint32_t ll = r[2] & 0xFFFFu, fs = r[2] >> 16;
-        const REAL tl = lds_ld<REAL>(dyn_lds, wb + (r[0] & 0xFFFFu)), th = lds_ld<REAL>(dyn_lds, wb + (r[0] >> 16));
-        const P2 cc = lds_ld<P2>(dyn_lds, wbC + ll);
-        const REAL t = rmin(th + cc.y, tl + cc.x);
-        if (real) {
-            lds_st<REAL>(dyn_lds, wb + fs, t);
-            *reinterpret_cast<REAL*>(Tg + fs) = t;
-        }
-        wave_sync();
-    };
-    // k-th hop processed = hop nh - 1 - k of the pack, its record requested eight hops ahead; past the first hop: any record (never used)
-    const uint32_t nhm1 = nh - 1u;
-    auto ldrec = [&](uint32_t k) -> u4v {
-        const uint32_t h = k < nhm1 ? nhm1 - k : 0u;
-        return __builtin_amdgcn_raw_buffer_load_b128(rr, (uint32_t)lane * 16u, (rbase + h * 64u) * 16u, 0);
-    };
-    u4v r0 = ldrec(0), r1 = ldrec(1), r2 = ldrec(2), r3 = ldrec(3), r4 = ldrec(4), r5 = ldrec(5), r6 = ldrec(6), r7 = ldrec(7);
-#define COSTS_HOP(RK, HK)           \
-    hop(RK);                        \
-    RK = ldrec(k + (HK) + 8);       \
-    if (k + (HK) + 1 >= nh) break;
-    for (uint32_t k = 0; k < nh; k += 8) {
-        COSTS_HOP(r0, 0) COSTS_HOP(r1, 1) COSTS_HOP(r2, 2) COSTS_HOP(r3, 3) COSTS_HOP(r4, 4) COSTS_HOP(r5, 5) COSTS_HOP(r6, 6) COSTS_HOP(r7, 7)
-    }
-#undef COSTS_HOP
-    // lower bound contribution of this pack: the double sum of the first hop's roots, small_iterate's tree
-    const u4v rroot = __builtin_amdgcn_raw_buffer_load_b128(rr, (uint32_t)lane * 16u, rbase * 16u, 0);
-    double lb = rroot[3] != RES2_PAD ? (double)lds_ld<REAL>(dyn_lds, wb + (rroot[2] >> 16)) : 0.0;
-    for (int off2 = 32; off2 > 0; off2 >>= 1) lb += __shfl_down(lb, off2);
+    const double lb = costs_backward<REAL>(dyn_lds, wb, wbC, rr, rbase, nh, (uint32_t)lane, reinterpret_cast<unsigned char*>(it.T + slot0));
     if (lane == 0) it.lb_partial[it.lb_base + p] = lb;
 }
 

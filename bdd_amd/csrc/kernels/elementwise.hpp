@@ -13,6 +13,17 @@ namespace bddmma {
 struct CostQuot {
     double lo, hi;
 };
+// The two expressions, shared with the round kernel of a batch (kernels/batchround.hpp), which applies a full-length update per member
+// inside its own launch: a variable's share per BDD, and a layer's new arc cost.
+template <typename TIN>
+__device__ __forceinline__ double ew_cost_quotient(TIN c, double nb) { return (double)c / nb; }
+// (f: the record's flags; do_lo / do_hi: the side is given at all)
+template <typename REAL>
+__device__ __forceinline__ void ew_cost_add(typename Pair<REAL>::type& c, const CostQuot& d, uint32_t f, uint32_t do_lo, uint32_t do_hi)
+{
+    if (do_lo) c.x = (f & 1u) ? REAL(0) : REAL((double)c.x + d.lo);
+    if (do_hi) c.y = (f & 2u) ? REAL(0) : REAL((double)c.y + d.hi);
+}
 template <typename TIN>
 __global__ void k_cost_quotients(CostQuot* __restrict__ q, uint8_t* __restrict__ flags, const int32_t* __restrict__ nbdds, const TIN* __restrict__ c_lo, uint64_t n_lo,
                                  const TIN* __restrict__ c_hi, uint64_t n_hi, uint32_t n_vars)
@@ -21,8 +32,8 @@ __global__ void k_cost_quotients(CostQuot* __restrict__ q, uint8_t* __restrict__
     if (v >= n_vars) return;
     const double nb = (double)nbdds[v];
     CostQuot r;
-    r.lo = (n_lo && v < n_lo) ? (double)c_lo[v] / nb : 0.0;
-    r.hi = (n_hi && v < n_hi) ? (double)c_hi[v] / nb : 0.0;
+    r.lo = (n_lo && v < n_lo) ? ew_cost_quotient(c_lo[v], nb) : 0.0;
+    r.hi = (n_hi && v < n_hi) ? ew_cost_quotient(c_hi[v], nb) : 0.0;
     q[v] = r;
     flags[v] = (uint8_t)(((n_lo && v >= n_lo) ? 1 : 0) | ((n_hi && v >= n_hi) ? 2 : 0));
 }
@@ -37,8 +48,7 @@ __global__ void k_update_costs(REAL* __restrict__ lohi, const int32_t* __restric
     const CostQuot d = q[v];
     const uint32_t f = flags[v];
     P2 c = reinterpret_cast<P2*>(lohi)[l];
-    if (do_lo) c.x = (f & 1u) ? REAL(0) : REAL((double)c.x + d.lo);
-    if (do_hi) c.y = (f & 2u) ? REAL(0) : REAL((double)c.y + d.hi);
+    ew_cost_add<REAL>(c, d, f, do_lo, do_hi);
     reinterpret_cast<P2*>(lohi)[l] = c;
 }
 
@@ -509,14 +519,13 @@ __device__ __forceinline__ float hash_uniform(uint32_t a, uint32_t b, uint32_t c
     return (float)(x >> 8) * (1.0f / 16777216.0f);  // [0, 1)
 }
 
-template <typename REAL>
-__global__ void k_round_perturb(const REAL* __restrict__ mm0, const REAL* __restrict__ mm1, const uint32_t* __restrict__ var_ptr,
-                                const uint32_t* __restrict__ var_layers, REAL* __restrict__ cost_delta_0, REAL* __restrict__ cost_delta_1,
-                                char* __restrict__ sol, uint32_t* __restrict__ counts, uint32_t n_vars, double delta, uint32_t round,
-                                uint32_t seed)
+// Variable v's part: its type (0 one, 1 zero, 2 equal, 3 inconsistent) and its two cost differences.  Shared by k_round_perturb and the
+// round kernel of a batch (kernels/batchround.hpp), where v is the member's own variable index.
+template <typename REAL, typename EMIT>
+__device__ __forceinline__ void ew_round_perturb(const REAL* __restrict__ mm0, const REAL* __restrict__ mm1, const uint32_t* __restrict__ var_ptr,
+                                                const uint32_t* __restrict__ var_layers, uint32_t v, double delta, uint32_t round, uint32_t seed, REAL& c0, REAL& c1,
+                                                EMIT&& emit)
 {
-    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= n_vars) return;
     int dmin = 2, dmax = -2;
     REAL s0 = 0, s1 = 0;
     for (uint32_t k = var_ptr[v]; k < var_ptr[v + 1]; ++k) {
@@ -534,9 +543,9 @@ __global__ void k_round_perturb(const REAL* __restrict__ mm0, const REAL* __rest
     else if (dmax < 0) type = 1;
     else if (dmin == 0 && dmax == 0) type = 2;
     else type = 3;
-    atomicAdd(&counts[type], 1u);
-    sol[v] = type == 0 ? 1 : 0;
-    REAL c0 = 0, c1 = 0;
+    emit(type);   // the caller's counter and its entry of the solution
+    c0 = 0;
+    c1 = 0;
     if (type == 0) c0 = REAL(delta);
     else if (type == 1) c1 = REAL(delta);
     else {
@@ -548,6 +557,20 @@ __global__ void k_round_perturb(const REAL* __restrict__ mm0, const REAL* __rest
             if (s0 < s1) c1 = mag; else c0 = mag;
         }
     }
+}
+template <typename REAL>
+__global__ void k_round_perturb(const REAL* __restrict__ mm0, const REAL* __restrict__ mm1, const uint32_t* __restrict__ var_ptr,
+                                const uint32_t* __restrict__ var_layers, REAL* __restrict__ cost_delta_0, REAL* __restrict__ cost_delta_1,
+                                char* __restrict__ sol, uint32_t* __restrict__ counts, uint32_t n_vars, double delta, uint32_t round,
+                                uint32_t seed)
+{
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_vars) return;
+    REAL c0, c1;
+    ew_round_perturb(mm0, mm1, var_ptr, var_layers, v, delta, round, seed, c0, c1, [&](int type) {
+        atomicAdd(&counts[type], 1u);
+        sol[v] = type == 0 ? 1 : 0;
+    });
     cost_delta_0[v] = c0;
     cost_delta_1[v] = c1;
 }

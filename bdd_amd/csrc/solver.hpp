@@ -175,7 +175,8 @@ struct BatchBase {
     virtual uint64_t size() const = 0;
     virtual int iterations(double omega, uint64_t n) = 0;   // SolverBase::iterations(omega, n) of every member
     // run_plain of every member (tests in its workgroup, its own control block; one clock and one time limit for the batch); res[size()]
-    virtual int run_plain(uint64_t max_iter, double tolerance, double slope, double time_limit, bddmma_run_result* res) = 0;
+    // mask (may be null): size() entries in member order; a member whose entry is non-zero takes no part and keeps its state
+    virtual int run_plain(uint64_t max_iter, double tolerance, double slope, double time_limit, bddmma_run_result* res, const char* mask = nullptr) = 0;
     virtual int time_iterations(double omega, uint64_t n, double* ms) = 0;   // iterations() between hipEvents on the batch stream; waits
     virtual int lower_bounds(double* out) = 0;              // SolverBase::lower_bound of every member, the reductions in flight together
     // SolverBase::learned_iterations(w_i, num_itr, omega, slope 0, no history) of every member, or its omega_vec form; dist_weights /
@@ -211,6 +212,12 @@ struct BatchBase {
     virtual int sum_marginals(int log_probs, void* sm0, void* sm1, int on_device) = 0;
     virtual int smooth_solution(void* out, int on_device) = 0;
     virtual int grad_smooth_lower_bound_per_bdd(const void* grad_lb, void* grad_lo, void* grad_hi, int on_device) = 0;
+    // SolverBase::rounding_round (apply_update) of every member in one launch per kernel instantiation present, and the loop of
+    // bddmma_incremental_mm_agreement_rounding over all members at once (kernels/batchround.hpp; include/bdd_mma.h:
+    // bddmma_perturb_primal_costs_batch, bddmma_incremental_mm_agreement_rounding_batch); host arrays, per-variable ones the members'
+    // nr_variables entries one behind the other
+    virtual int perturb_primal_costs(double delta, uint32_t round, uint32_t seed, uint32_t* counts, char* sol, void* c0, void* c1) = 0;
+    virtual int rounding(double init_delta, double growth, uint64_t num_itr_lb, uint64_t num_rounds, uint32_t seed, char* sol, int* found, uint64_t* rounds) = 0;
     // the batch stream behind everything queued on `other` so far / the reverse, by an event the batch owns; the host does not wait
     virtual int stream_wait(hipStream_t other) = 0;
     virtual int stream_signal(hipStream_t other) = 0;

@@ -11,6 +11,7 @@
 #include "kernels/batchbound.hpp"
 #include "kernels/batchmm.hpp"
 #include "kernels/batchsm.hpp"
+#include "kernels/batchround.hpp"
 #include "kernels/smallhist.hpp"
 
 namespace bddmma {
@@ -46,11 +47,12 @@ struct BatchT final : BatchBase {
         for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1, ev_order})
             if (e) (void)hipEventDestroy(e);
         if (d_items) (void)hipFree(d_items);
-        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad, (void*)d_bm_items, (void*)d_bm_stage, (void*)d_bm_bad, (void*)d_bsm_items, (void*)d_bsm_stage})
+        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad, (void*)d_bm_items, (void*)d_bm_stage, (void*)d_bm_bad, (void*)d_bsm_items, (void*)d_bsm_stage, (void*)d_br_items, (void*)d_br_words})
             if (q) (void)hipFree(q);
         if (d_ctl) (void)hipFree(d_ctl);
         if (h_ctl) (void)hipHostFree(h_ctl);
         if (h_run) (void)hipHostFree(h_run);
+        if (h_br_words) (void)hipHostFree(h_br_words);
         if (stream) (void)hipStreamDestroy(stream);
     }
     uint64_t size() const override { return m.size(); }
@@ -132,14 +134,19 @@ struct BatchT final : BatchBase {
     // for everything queued on every member's stream
     int join_in()
     {
-        for (S* s : m)
-            if (int rc = s->backward_run()) { err = s->err; return rc; }
+        for (size_t i = 0; i < m.size(); ++i)
+            if (!masked(i))
+                if (int rc = m[i]->backward_run()) { err = m[i]->err; return rc; }
         for (size_t i = 0; i < m.size(); ++i) {
             HIPCHK(hipEventRecord(ev_in[i], m[i]->stream));
             HIPCHK(hipStreamWaitEvent(stream, ev_in[i], 0));
         }
         return BDDMMA_OK;
     }
+    // run_plain's optional mask (member order), set for the duration of that call only: a masked member runs no iteration and keeps its
+    // host-side state
+    const char* run_mask = nullptr;
+    bool masked(size_t i) const { return run_mask != nullptr && run_mask[i] != 0; }
     // exit: every member's stream waits for what the batch stream holds now
     int join_out()
     {
@@ -161,7 +168,8 @@ struct BatchT final : BatchBase {
             hipLaunchKernelGGL(g.fn, dim3(g.count), dim3(g.threads), g.lds, stream, (const SmallItem<REAL>*)(d_items + g.first), omega, n_iters);
             HIPCHK(hipGetLastError());
         }
-        for (S* s : m) s->small_launched();
+        for (size_t i = 0; i < m.size(); ++i)
+            if (!masked(i)) m[i]->small_launched();
         return BDDMMA_OK;
     }
 
@@ -1301,6 +1309,166 @@ struct BatchT final : BatchBase {
         }
         return bsm_run(me, BSM_GRAD, grad_lb, grad_lo, grad_hi, on_dev);
     }
+    // ---- primal rounding, all members at once (kernels/batchround.hpp: k_small_round_batch; the kernel compiles in solver_br_f32.hip /
+    // _f64.hip).  Items sorted by the members' wave count, as the min-marginal items are: one launch per wave count present.  The batch
+    // owns one `done` word and four counters per member (br_words: n done words in item order, then 4 n counters) and their pinned
+    // host copy; they, the items and every member's d_mm_consumed exist before any member is touched.
+    struct BrGroup {
+        RoundFn<REAL> fn;
+        uint32_t threads, lds, first, count;
+    };
+    std::vector<BrGroup> br_groups;
+    std::vector<uint32_t> br_ord;              // item j is member br_ord[j]
+    RoundItem<REAL>* d_br_items = nullptr;
+    uint32_t *d_br_words = nullptr, *h_br_words = nullptr;
+    bool br_ready = false;
+
+    int br_prepare()
+    {
+        if (br_ready) return BDDMMA_OK;
+        const uint32_t n = (uint32_t)m.size();
+        constexpr uint32_t RS = (uint32_t)sizeof(REAL);
+        if (int rc = bb_prepare(true, false)) return rc;   // every member's d_mm_consumed; the items of distribute_delta
+        std::vector<uint32_t> ord(n);
+        for (uint32_t i = 0; i < n; ++i) ord[i] = i;
+        std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return m[a]->small_nw < m[b]->small_nw; });
+        if (!d_br_words) HIPCHK(hipMalloc((void**)&d_br_words, 5 * (size_t)n * sizeof(uint32_t)));
+        if (!h_br_words) HIPCHK(hipHostMalloc((void**)&h_br_words, 5 * (size_t)n * sizeof(uint32_t), hipHostMallocDefault));
+        std::vector<RoundItem<REAL>> items(n);
+        std::vector<BrGroup> groups_;
+        for (uint32_t j = 0; j < n; ++j) {
+            const S* s = m[ord[j]];
+            const SmallDev& sm = s->small;
+            RoundItem<REAL>& it = items[j];
+            it.mm = MmItem<REAL>{sm.pack_hdr, sm.rec, sm.rec_off, sm.rec_words, sm.ns, sm.nl, sm.n_packs, (uint32_t)s->n_layers, 0u, ord[j],
+                                 s->pack_width, s->ptrs(nullptr), s->pdev(s->nb_, 0, 0), nullptr, nullptr, nullptr};
+            it.mm_consumed = s->d_mm_consumed;
+            it.delta_var = s->d_delta_var; it.delta_lay = s->d_delta_lay; it.delta_c = s->d_delta_c;
+            it.var_ptr = s->d_var_ptr; it.var_layers = s->d_var_layers; it.layer_var = s->d_var; it.nbdds = s->d_nbdds;
+            it.done = d_br_words + j;
+            it.counts = d_br_words + n + 4 * (size_t)j;
+            it.n_vars = (uint32_t)s->n_vars;
+            if (groups_.empty() || s->small_nw != m[ord[groups_.back().first]]->small_nw)
+                groups_.push_back(BrGroup{round_fn<REAL>(s->small_nw), 64u * (uint32_t)s->small_nw, 0u, j, 0u});
+            BrGroup& g = groups_.back();
+            // the largest phase: a region of k_small_mmdiff_batch per pack (kernels/batchround.hpp: round_lds_bytes)
+            g.lds = std::max(g.lds, round_lds_bytes(RS, sm.ns, sm.nl, sm.n_packs));
+            ++g.count;
+        }
+        for (const BrGroup& g : groups_) {
+            // (never taken for a fused_small member: the region is smaller than a pack's share of small_lds, kernels/batchmm.hpp)
+            if (g.lds > m[0]->lds_cu) { err = "batch rounding: the packs' state does not fit the LDS"; return BDDMMA_ERR_STATE; }
+            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(g.fn), g.lds)) return rc;
+        }
+        if (!d_br_items) HIPCHK(hipMalloc((void**)&d_br_items, n * sizeof(RoundItem<REAL>)));
+        HIPCHK(hipMemcpy(d_br_items, items.data(), n * sizeof(RoundItem<REAL>), hipMemcpyHostToDevice));
+        br_ord = std::move(ord);
+        br_groups = std::move(groups_);
+        br_ready = true;
+        return BDDMMA_OK;
+    }
+    // SolverT::rounding_round(delta, round, seed, apply_update = true) of every member whose entry of `active` is non-zero (null: every
+    // member; the device's done words are then cleared first, else they are what the earlier rounds of the loop left: !active).
+    // counts: 4 per member; sol / c0 / c1: the members' n_vars values one behind the other, c0 / c1 may be null; all in member order, on
+    // the host.  A member's part of sol is written only if its min-marginals agree; an inactive member's outputs are left alone.
+    // agreed (may be null): 1 where they did.
+    int rounding_round(double delta, uint32_t round, uint32_t seed, const char* active, uint32_t* counts, char* sol, void* c0, void* c1, char* agreed = nullptr)
+    {
+        int rc;
+        const char* const me = "batch perturb_primal_costs";
+        const uint32_t n = (uint32_t)m.size();
+        if (!counts || !sol) { err = std::string(me) + ": null output pointer"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if ((rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = br_prepare())) return rc;
+        if ((rc = members_in())) return rc;   // (no costs-to-terminal are needed: the kernel runs its own backward sweep)
+        // ---- the members are touched from here on
+        hipError_t e = hipSuccess;
+        if (!active) e = hipMemsetAsync(d_br_words, 0, n * sizeof(uint32_t), stream);
+        for (size_t k = 0; k < br_groups.size() && e == hipSuccess; ++k) {
+            const BrGroup& G = br_groups[k];
+            hipLaunchKernelGGL(G.fn, dim3(G.count), dim3(G.threads), G.lds, stream, (const RoundItem<REAL>*)(d_br_items + G.first), delta, round, seed);
+            e = hipGetLastError();
+        }
+        // one copy of all done words and counters, one host synchronisation
+        if (e == hipSuccess) e = hipMemcpyAsync(h_br_words, d_br_words, 5 * (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        std::vector<uint64_t> voff(n + 1, 0);
+        for (uint32_t i = 0; i < n; ++i) voff[i + 1] = voff[i] + m[i]->n_vars;
+        // the host-side state after SolverT::rounding_round: distribute_delta, forward_run, the BWD_MARGINALS launch, and update_costs
+        // where the member did not agree.  Behind a failure nothing is known to be valid.
+        const bool ok = e == hipSuccess;
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t i = br_ord[j];
+            if (active && !active[i]) continue;
+            S* s = m[i];
+            const bool done = ok && h_br_words[j] != 0;
+            s->mm_consumed_valid = true;
+            s->delta_var_valid = true;
+            s->costs_changed();
+            s->lb_cached = false;
+            ++s->lb_gen;
+            if (done) s->fwd_valid = s->bwd_valid = s->lb_valid = true;
+            else s->costs_changed();
+            if (!ok) continue;
+            for (int k = 0; k < 4; ++k) counts[4 * (size_t)i + k] = h_br_words[n + 4 * (size_t)j + k];
+            if (agreed) agreed[i] = done ? 1 : 0;
+            // the outputs the per-member call copies: both differences where asked for, the solution where the member agreed
+            const size_t vb = s->n_vars * sizeof(REAL);
+            if (c0 && e == hipSuccess) e = hipMemcpyAsync((REAL*)c0 + voff[i], s->d_delta_c, vb, hipMemcpyDeviceToHost, stream);
+            if (c1 && e == hipSuccess) e = hipMemcpyAsync((REAL*)c1 + voff[i], s->d_delta_c + s->n_vars, vb, hipMemcpyDeviceToHost, stream);
+            if (done && e == hipSuccess) e = hipMemcpyAsync(sol + voff[i], s->d_sol, s->n_vars, hipMemcpyDeviceToHost, stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        const int rc2 = join_out();
+        if (e != hipSuccess) { err = std::string(me) + ": " + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        return rc2;
+    }
+    int perturb_primal_costs(double delta, uint32_t round, uint32_t seed, uint32_t* counts, char* sol, void* c0, void* c1) override
+    {
+        return rounding_round(delta, round, seed, nullptr, counts, sol, c0, c1);
+    }
+    // bddmma_incremental_mm_agreement_rounding (no L-BFGS wrapper, not verbose) of every member: its call sequence with every per-member
+    // call replaced by the batch's — distribute_delta, lower_bound, then per round rounding_round over the members still looking and
+    // run_plain(num_itr_lb, 1e-7, 0.0001, DBL_MAX) over the same.  A member whose min-marginals agree leaves both from then on.  (The
+    // round's own distribute_delta is part of the kernel, so round 0 applies already-cleared differences as the per-member call does.)
+    int rounding(double init_delta, double growth, uint64_t num_itr_lb, uint64_t num_rounds, uint32_t seed, char* sol, int* found, uint64_t* rounds) override
+    {
+        int rc;
+        const uint32_t n = (uint32_t)m.size();
+        if (!sol || !found) { err = "batch rounding: null output pointer"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if (!(growth > 0) || !(init_delta > 0)) { err = "batch rounding: init_delta and delta_growth_rate must be positive"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if ((rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = br_prepare())) return rc;
+        // ---- the members and the outputs are touched from here on
+        for (uint32_t i = 0; i < n; ++i) {
+            found[i] = 0;
+            if (rounds) rounds[i] = num_rounds;
+        }
+        if ((rc = distribute_delta())) return rc;
+        std::vector<double> lb(n);
+        if ((rc = lower_bounds(lb.data()))) return rc;
+        std::vector<char> active(n, 1), agreed(n, 0), mask(n, 0);
+        std::vector<uint32_t> counts(4 * (size_t)n);
+        double cur_delta = init_delta / growth;
+        uint32_t left = n;
+        for (uint64_t round = 0; round < num_rounds && left; ++round) {
+            cur_delta = std::min(cur_delta * growth, 1e6);
+            if ((rc = rounding_round(cur_delta, (uint32_t)round, seed, round == 0 ? nullptr : active.data(), counts.data(), sol, nullptr, nullptr, agreed.data()))) return rc;
+            for (uint32_t i = 0; i < n; ++i)
+                if (active[i] && agreed[i]) {
+                    active[i] = 0;
+                    mask[i] = 1;
+                    found[i] = 1;
+                    if (rounds) rounds[i] = round;
+                    --left;
+                }
+            if (!left) break;
+            if ((rc = run_plain(num_itr_lb, 1e-7, 0.0001, std::numeric_limits<double>::max(), nullptr, mask.data()))) return rc;
+        }
+        return BDDMMA_OK;
+    }
     int stream_wait(hipStream_t other) override
     {
         HIPCHK(hipSetDevice(device));
@@ -1323,6 +1491,7 @@ struct BatchT final : BatchBase {
         HIPCHK(hipSetDevice(device));
         std::vector<char> pending(m.size(), 0);
         for (size_t i = 0; i < m.size(); ++i) {
+            if (masked(i)) continue;
             S* s = m[i];
             int rc = s->backward_run();
             if (!rc && !s->lb_cached) {
@@ -1333,6 +1502,7 @@ struct BatchT final : BatchBase {
         }
         // the reductions run side by side on the members' streams; the host then collects them in order
         for (size_t i = 0; i < m.size(); ++i) {
+            if (masked(i)) continue;   // (its entry of `out` stays)
             S* s = m[i];
             if (pending[i]) {
                 if (int rc = s->wait_bound(0)) { err = s->err; return rc; }
@@ -1347,8 +1517,15 @@ struct BatchT final : BatchBase {
     // SolverT::run_plain for every member at once.  Chunks of SMALL_CHUNK iterations, the tests in each member's workgroup after every
     // iteration against its own control block; a member that has stopped returns at once in later chunks (DevPtrs::stop).  At most two
     // chunks are outstanding; the host waits for the older one and reads what the members have published.
-    int run_plain(uint64_t max_iter, double tolerance, double slope, double time_limit, bddmma_run_result* res) override
+    // mask (member order, may be null): a member whose entry is non-zero takes no part — its control block starts as stopped at iteration
+    // 0, so its workgroup returns at once; its sweep states, run_stop, cached bound and entry of `res` are left alone.
+    int run_plain(uint64_t max_iter, double tolerance, double slope, double time_limit, bddmma_run_result* res, const char* mask = nullptr) override
     {
+        struct MaskScope {
+            BatchT* b;
+            ~MaskScope() { b->run_mask = nullptr; }
+        } scope{this};
+        run_mask = mask;
         if (slope < 0.0 || slope >= 1.0 || time_limit < 0.0 || tolerance < 0.0) {
             err = "run_solver: invalid termination criteria";
             return BDDMMA_ERR_INVALID_ARGUMENT;
@@ -1365,7 +1542,7 @@ struct BatchT final : BatchBase {
         if (max_iter > 0) {
             for (uint32_t j = 0; j < n; ++j) {
                 RunCtl c{};
-                c.stop = RUN_NOT_STOPPED;
+                c.stop = masked(order[j]) ? 0u : RUN_NOT_STOPPED;
                 c.lb_initial = lb_initial[order[j]];
                 c.lb_first = std::numeric_limits<double>::max();
                 c.lb_post = c.lb_initial;
@@ -1381,7 +1558,8 @@ struct BatchT final : BatchBase {
             HIPCHK(hipGetLastError());
             constexpr uint64_t SMALL_CHUNK = 64;
             static_assert(2 * SMALL_CHUNK < RUN_RING, "published bounds must not wrap before the host has read them");
-            for (uint32_t j = 0; j < n; ++j) m[order[j]]->run_stop = &d_ctl[j].stop;   // "run_solver in progress", as run_plain marks it
+            for (uint32_t j = 0; j < n; ++j)
+                if (!masked(order[j])) m[order[j]]->run_stop = &d_ctl[j].stop;   // "run_solver in progress", as run_plain marks it
             volatile RunHost* hr = h_run;
             uint64_t queued = 0, chunks = 0, waited = 0;
             while (!rc) {
@@ -1400,18 +1578,19 @@ struct BatchT final : BatchBase {
                 bool all_done = true;
                 for (uint32_t j = 0; j < n && all_done; ++j) {
                     const uint64_t st = hr[j].state;
-                    all_done = (st >> 56) != 0 || (st & MASK) >= max_iter;
+                    all_done = masked(order[j]) || (st >> 56) != 0 || (st & MASK) >= max_iter;
                 }
                 if (all_done) break;
             }
             const hipError_t e = hipStreamSynchronize(stream);   // launches behind the last stop return at once
-            for (S* s : m) s->run_stop = nullptr;
+            for (size_t i = 0; i < m.size(); ++i)
+                if (!masked(i)) m[i]->run_stop = nullptr;
             if (!rc && e != hipSuccess) { err = std::string("run_solver: ") + hipGetErrorString(e); rc = BDDMMA_ERR_DEVICE; }
             const int rc2 = join_out();
             if (rc || rc2) return rc ? rc : rc2;
             for (uint32_t j = 0; j < n; ++j) {
                 const uint64_t st = hr[j].state;
-                if ((st >> 56) == 0 && (st & MASK) < queued) {
+                if (!masked(order[j]) && (st >> 56) == 0 && (st & MASK) < queued) {
                     err = "run_solver: queued iterations of batch member " + std::to_string(order[j]) + " did not complete";
                     return BDDMMA_ERR_DEVICE;
                 }
@@ -1419,6 +1598,7 @@ struct BatchT final : BatchBase {
         }
         const double seconds = elapsed();
         for (uint32_t j = 0; j < n; ++j) {
+            if (masked(order[j])) continue;
             S* s = m[order[j]];
             const uint64_t st = max_iter > 0 ? ((volatile RunHost*)h_run)[j].state : 0;
             const uint64_t done = st & MASK;

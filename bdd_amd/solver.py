@@ -870,6 +870,37 @@ class bdd_hip_batch:
         self._check(call(self._h, _ptr(g), _ptr(lo), _ptr(hi), 0), self._h)
         return lo, hi
 
+    # ---- primal rounding (include/bdd_mma.h: bddmma_perturb_primal_costs_batch, bddmma_incremental_mm_agreement_rounding_batch)
+    def perturb_primal_costs(self, delta, round_index=0, seed=0):
+        """perturb_primal_costs(delta, round_index, seed) of every member, one workgroup per member in one launch per wave count
+        present: a list of the per-member dicts of bdd_hip_parallel_mma.perturb_primal_costs (sol is zero where the member's
+        min-marginals did not agree)"""
+        nv = [s.nr_variables() for s in self.solvers]
+        off = np.cumsum([0] + nv)
+        vt = self.solvers[0].value_type
+        counts = np.zeros(4 * len(nv), np.uint32)
+        sol = np.zeros(int(off[-1]), np.int8)
+        c0, c1 = np.zeros(int(off[-1]), vt), np.zeros(int(off[-1]), vt)
+        self._check(self._L.bddmma_perturb_primal_costs_batch(self._h, float(delta), int(round_index), int(seed),
+                                                              counts.ctypes.data_as(C.POINTER(C.c_uint32)), _ptr(sol), _ptr(c0), _ptr(c1)), self._h)
+        return [dict(counts=tuple(int(c) for c in counts[4 * i:4 * i + 4]), sol=sol[off[i]:off[i + 1]].copy(),
+                     cost_delta_0=c0[off[i]:off[i + 1]].copy(), cost_delta_1=c1[off[i]:off[i + 1]].copy()) for i in range(len(nv))]
+
+    def primal_rounding_incremental(self, init_delta, delta_growth_rate, num_itr_lb, num_rounds=500, seed=0, return_rounds=False):
+        """primal_rounding_incremental(...) of every member (not verbose), every round one launch per wave count present and the
+        iterations in between those of run_solver on the members still looking: a list of per-member solutions, each a list of
+        0.0 / 1.0 per variable, empty where none was found.  The costs stay perturbed.  return_rounds: also the round index in which
+        each member's agreement was seen (num_rounds where none was)."""
+        nv = [s.nr_variables() for s in self.solvers]
+        off = np.cumsum([0] + nv)
+        sol = np.zeros(int(off[-1]), np.int8)
+        found = (C.c_int * len(nv))()
+        rounds = (C.c_uint64 * len(nv))()
+        self._check(self._L.bddmma_incremental_mm_agreement_rounding_batch(self._h, float(init_delta), float(delta_growth_rate), int(num_itr_lb),
+                                                                           int(num_rounds), int(seed), _ptr(sol), found, rounds), self._h)
+        sols = [[float(x) for x in sol[off[i]:off[i + 1]]] if found[i] else [] for i in range(len(nv))]
+        return (sols, [int(r) for r in rounds]) if return_rounds else sols
+
     # ---- ordering against other streams (include/bdd_mma.h: bddmma_stream_wait_batch / bddmma_stream_signal_batch)
     def stream_wait(self, hip_stream=0):
         """what the batch's calls queue from now on starts after everything queued so far on `hip_stream` (a raw hipStream_t as an

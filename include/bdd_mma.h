@@ -659,6 +659,26 @@ int bddmma_incremental_mm_agreement_rounding(bddmma_solver* s, bddmma_lbfgs* lbf
 int bddmma_perturb_primal_costs(bddmma_solver* s, bddmma_lbfgs* lbfgs_or_null, double cur_delta, uint32_t round_index, uint32_t seed,
                                 uint32_t counts[4], char* sol, void* cost_delta_0, void* cost_delta_1);
 
+/* Both for a batch (kernels/batchround.hpp: one workgroup per member, one launch per round and wave count present).  All arrays are on
+ * the host.  sol, cost_delta_0 and cost_delta_1 are the members' nr_variables entries one behind the other in the members' order, counts
+ * four per member, found / rounds one per member.  A call equals the per-member call — bddmma_perturb_primal_costs(member i, NULL, ..)
+ * resp. bddmma_incremental_mm_agreement_rounding(member i, NULL, .., seed, 0, ..) — on every member, bit for bit in float and in
+ * double: the outputs and every member's state afterwards.  A member's part of sol is written only where its min-marginals agreed, as
+ * the per-member call writes it.  There is no L-BFGS form and no `verbose`.
+ * Refusals, all decided before any member or output is touched: a null batch or a required null array (counts, sol; sol, found):
+ * BDDMMA_ERR_INVALID_ARGUMENT; init_delta <= 0 or delta_growth_rate <= 0: BDDMMA_ERR_INVALID_ARGUMENT; BDDMMA_ERR_STATE as for every
+ * batch call (an L-BFGS wrapper, profiling, a member inside run_solver; bddmma_batch_last_error names the member).
+ *
+ * bddmma_perturb_primal_costs_batch: one round on every member; cost_delta_0 / cost_delta_1 may be NULL. */
+int bddmma_perturb_primal_costs_batch(bddmma_batch* b, double cur_delta, uint32_t round_index, uint32_t seed, uint32_t* counts, char* sol, void* cost_delta_0,
+                                      void* cost_delta_1);
+/* The loop for all members at once: the initial distribute_delta, then per round cur_delta = min(cur_delta * delta_growth_rate, 1e6), the
+ * round over the members still looking and bddmma_batch_run_solver(num_itr_lb, 1e-7, 0.0001, no time limit) over the same.  A member
+ * whose min-marginals agree is not touched again: its state is what its own call returns with.  found[i]: 0 or 1; rounds (may be NULL):
+ * rounds[i] = the index of the round in which member i's agreement was seen, num_rounds where none was. */
+int bddmma_incremental_mm_agreement_rounding_batch(bddmma_batch* b, double init_delta, double delta_growth_rate, uint64_t num_itr_lb, uint64_t num_rounds,
+                                                   uint32_t seed, char* sol, int* found, uint64_t* rounds);
+
 /* ---- checkpoint (bdd_cuda_base.cu:1486-1550) ------------------------------ */
 int bddmma_save(const bddmma_solver* s, const char* path);
 int bddmma_load(bddmma_solver** out, int device, const char* path);
