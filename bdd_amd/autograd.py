@@ -7,9 +7,9 @@ mirrors); the differences are the ones include/bdd_mma.h has from the reference'
 Conventions of every function
   solvers     a list of bdd_hip_parallel_mma of one precision on one device, or a bdd_hip_batch: its members in order.  (The chain of
               a training step's loss — DualIterations, DistributeDeferredDelta and ComputeLowerBoundperBDD, forward and backward —
-              makes batch calls on a batch, with the results of the list form, and so do ComputeAllMinMarginalsDiff, GetSumMarginals
-              and GetMarginalProbability; the backward of ComputeLowerBoundperBDD with smooth_gradients_temp > 0 and every other
-              function do with a batch what they do with the list of its members.)
+              makes batch calls on a batch, with the results of the list form, and so do ComputeAllMinMarginalsDiff, GetSumMarginals,
+              GetMarginalProbability, ComputePrimalSolution, ComputePerBDDSolutions and PerturbPrimalCosts; only the backward of
+              ComputeLowerBoundperBDD with smooth_gradients_temp > 0 does with a batch what it does with the list of its members.)
   tensors     1-D, contiguous, on the solvers' device, of the solvers' precision (torch.float32 / torch.float64 — the reference asks for
               torch's default dtype instead).  A batch tensor is the concatenation over the solvers, in list order, of each solver's array:
                 per layer     nr_layers() values in the public layer order (get_solver_costs, get_primal_variable_index) — there are
@@ -31,7 +31,8 @@ Conventions of every function
               its outputs, as with any torch operator.  DualIterations' two batched paths make batch calls only, which run on the
               batch's own stream and order themselves against every member's: there the one pair is the batch's (bdd_hip_batch.stream_wait
               / stream_signal) instead of a pair per member.  The same holds for the batched forms of DistributeDeferredDelta,
-              ComputeLowerBoundperBDD, ComputeAllMinMarginalsDiff, GetSumMarginals and GetMarginalProbability.
+              ComputeLowerBoundperBDD, ComputeAllMinMarginalsDiff, GetSumMarginals, GetMarginalProbability,
+              ComputePerBDDSolutions and PerturbPrimalCosts.
 Every backward is once_differentiable, takes a missing incoming gradient (None) as zeros and runs on the stream that is current
 when autograd calls it.
 """
@@ -144,17 +145,21 @@ class _Ordered:
         return False
 
 
-def _batch_set_costs(batch, lo, hi, mm):
-    """the first call of a batched tail (DistributeDeferredDelta, ComputeLowerBoundperBDD): batch.set_solver_costs.  False when the batch
-    refuses it with BDDMMA_ERR_STATE — a member that has (had) an L-BFGS wrapper, for instance, with which the list form works; the
-    refusal has touched nothing, so the caller runs the list form instead."""
+def _batch_first(call, *args, **kwargs):
+    """the first call of a batched path: False when the batch refuses it with BDDMMA_ERR_STATE — a member that has (had) an L-BFGS
+    wrapper, for instance, with which the list form works; the refusal has touched nothing, so the caller runs the list form instead."""
     try:
-        batch.set_solver_costs(lo, hi, mm)
+        call(*args, **kwargs)
     except capi.BddMmaError as e:
         if str(e).startswith(f"bdd_mma error {capi.ERR_STATE}:"):
             return False
         raise
     return True
+
+
+def _batch_set_costs(batch, lo, hi, mm):
+    """the first call of a batched tail (DistributeDeferredDelta, ComputeLowerBoundperBDD, ...): batch.set_solver_costs"""
+    return _batch_first(batch.set_solver_costs, lo, hi, mm)
 
 
 def _incoming(g, like):
@@ -238,9 +243,19 @@ def GetSumMarginals(solvers, lo_costs_batch, hi_costs_batch, get_logits):
 
 
 def ComputePerBDDSolutions(solvers, lo_costs_batch, hi_costs_batch):
-    """bdd_cuda_torch.py:43-59: the arg-min path of every BDD (bdds_solution_vec) as 0 / 1 in the solvers' precision, per layer"""
+    """bdd_cuda_torch.py:43-59: the arg-min path of every BDD (bdds_solution_vec) as 0 / 1 in the solvers' precision, per layer.  For a
+    bdd_hip_batch ONE batch.set_solver_costs and ONE batch.bdds_solution_vec (bddmma_bdds_solution_batch: one workgroup per member), none
+    on a member, with the list form's results bit for bit.  The list form runs for a list, and for a batch whose first call refuses with
+    BDDMMA_ERR_STATE."""
     z, zero = _with_costs(solvers, lo_costs_batch, hi_costs_batch)
     sol = torch.empty(z.layers[-1], dtype=torch.int8, device=lo_costs_batch.device)
+    if z.batch is not None:
+        with _Ordered([z.batch]):
+            batched = _batch_set_costs(z.batch, lo_costs_batch, hi_costs_batch, zero)
+            if batched:
+                z.batch.bdds_solution_vec(out=sol)
+        if batched:
+            return sol.to(z.dtype)
     with _Ordered(z.solvers):
         for s, l in zip(z.solvers, z.slices(z.layers)):
             s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], zero[l])
@@ -459,8 +474,13 @@ class PerturbPrimalCosts(torch.autograd.Function):
     costs after update_costs(lo_pert, hi_pert) — every layer of a variable gets pert[variable] / nr_bdds(variable).  The perturbations
     are per-variable batch tensors; deferred differences zero.
 
-    backward  the identity for lo and hi, bddmma_grad_cost_perturbation for the two perturbations.  That call reads nothing of the solver
-              but its layout and changes nothing; a non-finite incoming gradient is BDDMMA_ERR_INVALID_ARGUMENT (BddMmaError)."""
+    forward   for a bdd_hip_batch three batch calls and none on a member: ONE batch.set_solver_costs, ONE batch.update_costs
+              (bddmma_update_costs_batch) and ONE batch.get_solver_costs, with the list form's results bit for bit.  The list form runs
+              for a list, and for a batch whose first call refuses with BDDMMA_ERR_STATE.
+    backward  the identity for lo and hi, bddmma_grad_cost_perturbation for the two perturbations; for a bdd_hip_batch ONE
+              batch.grad_cost_perturbation (bddmma_grad_cost_perturbation_batch) instead of a call per member, the list form after a
+              BDDMMA_ERR_STATE refusal.  That call reads nothing of the solver but its layout and changes nothing; a non-finite incoming
+              gradient is BDDMMA_ERR_INVALID_ARGUMENT (BddMmaError)."""
 
     @staticmethod
     def forward(ctx, solvers, lo_costs_pert_batch, hi_costs_pert_batch, lo_costs_batch, hi_costs_batch):
@@ -472,6 +492,14 @@ class PerturbPrimalCosts(torch.autograd.Function):
         ctx.like = (lo_costs_batch.new_empty(0), lo_costs_pert_batch.shape, lo_costs_batch.shape)
         zero = torch.zeros_like(lo_costs_batch)
         lo, hi, rest = (torch.empty_like(lo_costs_batch) for _ in range(3))
+        if z.batch is not None:
+            with _Ordered([z.batch]):   # batch calls only: each orders itself against the members' streams
+                batched = _batch_set_costs(z.batch, lo_costs_batch, hi_costs_batch, zero)
+                if batched:
+                    z.batch.update_costs(lo_costs_pert_batch, hi_costs_pert_batch)
+                    z.batch.get_solver_costs(out=(lo, hi, None))
+            if batched:
+                return lo, hi
         with _Ordered(z.solvers):
             for s, l, v in zip(z.solvers, z.slices(z.layers), z.slices(z.variables)):
                 s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], zero[l])
@@ -488,6 +516,11 @@ class PerturbPrimalCosts(torch.autograd.Function):
         g_hi = proto.new_zeros(layer_shape) if grad_hi is None else grad_hi.contiguous()
         z.check(("grad_lo_costs_out", g_lo, z.layers), ("grad_hi_costs_out", g_hi, z.layers))
         p_lo, p_hi = proto.new_empty(pert_shape), proto.new_empty(pert_shape)
+        if z.batch is not None:
+            with _Ordered([z.batch]):
+                batched = _batch_first(z.batch.grad_cost_perturbation, g_lo, g_hi, out=(p_lo, p_hi))
+            if batched:
+                return None, p_lo, p_hi, g_lo, g_hi
         with _Ordered(z.solvers):
             for s, l, v in zip(z.solvers, z.slices(z.layers), z.slices(z.variables)):
                 s.grad_cost_perturbation(g_lo[l], g_hi[l], out=(p_lo[v], p_hi[v]))

@@ -146,6 +146,9 @@ SIGNATURES = {
     "bddmma_incremental_mm_agreement_rounding": (_I, [_V, _V, _D, _D, _U64, _U64, C.c_uint32, _I, _V, C.POINTER(_I)]),
     "bddmma_perturb_primal_costs_batch": (_I, [_V, _D, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), _V, _V, _V]),
     "bddmma_incremental_mm_agreement_rounding_batch": (_I, [_V, _D, _D, _U64, _U64, C.c_uint32, _V, C.POINTER(_I), C.POINTER(_U64)]),
+    "bddmma_bdds_solution_batch": (_I, [_V, _V, _I]),
+    "bddmma_update_costs_batch": (_I, [_V, _V, _V, _I, _I]),
+    "bddmma_grad_cost_perturbation_batch": (_I, [_V, _V, _V, _V, _V, _I]),
     "bddmma_save": (_I, [_V, C.c_char_p]),
     "bddmma_load": (_I, [C.POINTER(_V), _I, C.c_char_p]),
     "bddmma_synchronize": (_I, [_V]),

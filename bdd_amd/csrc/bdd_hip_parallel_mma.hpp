@@ -635,6 +635,48 @@ class bdd_hip_batch {
         }
         return out;
     }
+    // bdds_solution_vec / update_costs / grad_cost_perturbation of every member in one launch each: layer arrays are the members'
+    // [nr_layers], per-variable arrays the members' [nr_variables], one behind the other in the members' order.  Device pointers (the host
+    // does not wait) or host vectors; a null (device) or empty (host) cost vector leaves that side of every member's costs as it is.
+    // Contract: bddmma_bdds_solution_batch, bddmma_update_costs_batch, bddmma_grad_cost_perturbation_batch.
+    void bdds_solution_vec(char* dev_out) { check(bddmma_bdds_solution_batch(b_, dev_out, 1)); }
+    std::vector<char> bdds_solution_vec_host(const size_t total_layers)
+    {
+        std::vector<char> sol(total_layers > 0 ? total_layers : 1);
+        check(bddmma_bdds_solution_batch(b_, sol.data(), 0));
+        sol.resize(total_layers);
+        return sol;
+    }
+    void update_costs(const REAL* dev_cost_delta_0, const REAL* dev_cost_delta_1)
+    {
+        check(bddmma_update_costs_batch(b_, dev_cost_delta_0, dev_cost_delta_1, sizeof(REAL) == 8 ? BDDMMA_F64 : BDDMMA_F32, 1));
+    }
+    template <typename COST>
+    void update_costs(const std::vector<COST>& cost_delta_0, const std::vector<COST>& cost_delta_1)
+    {
+        static_assert(std::is_same<COST, float>::value || std::is_same<COST, double>::value, "update_costs: float or double vectors");
+        size_t total = 0;
+        for (const size_t v : nv_) total += v;
+        if ((!cost_delta_0.empty() && cost_delta_0.size() != total) || (!cost_delta_1.empty() && cost_delta_1.size() != total))
+            throw std::invalid_argument("bdd_hip_batch::update_costs: a vector holds the members' nr_variables() entries, or none");
+        check(bddmma_update_costs_batch(b_, cost_delta_0.empty() ? nullptr : cost_delta_0.data(), cost_delta_1.empty() ? nullptr : cost_delta_1.data(),
+                                        sizeof(COST) == 8 ? BDDMMA_F64 : BDDMMA_F32, 0));
+    }
+    void grad_cost_perturbation(const REAL* dev_grad_lo, const REAL* dev_grad_hi, REAL* dev_grad_lo_pert_out, REAL* dev_grad_hi_pert_out)
+    {
+        check(bddmma_grad_cost_perturbation_batch(b_, dev_grad_lo, dev_grad_hi, dev_grad_lo_pert_out, dev_grad_hi_pert_out, 1));
+    }
+    std::pair<std::vector<REAL>, std::vector<REAL>> grad_cost_perturbation(const std::vector<REAL>& grad_lo, const std::vector<REAL>& grad_hi)
+    {
+        if (grad_lo.size() != grad_hi.size()) throw std::invalid_argument("bdd_hip_batch::grad_cost_perturbation: the members' nr_layers() entries each");
+        size_t total = 0;
+        for (const size_t v : nv_) total += v;
+        std::vector<REAL> lo(total > 0 ? total : 1), hi(total > 0 ? total : 1);
+        check(bddmma_grad_cost_perturbation_batch(b_, grad_lo.data(), grad_hi.data(), lo.data(), hi.data(), 0));
+        lo.resize(total);
+        hi.resize(total);
+        return {std::move(lo), std::move(hi)};
+    }
     // stream_wait — the batch's later calls start after everything queued on `hip_stream` so far; stream_signal — the reverse
     // (bddmma_stream_wait_batch / bddmma_stream_signal_batch)
     void stream_wait(void* hip_stream) { check(bddmma_stream_wait_batch(b_, hip_stream)); }

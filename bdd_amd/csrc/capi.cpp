@@ -629,6 +629,28 @@ int bddmma_incremental_mm_agreement_rounding_batch(bddmma_batch* b, double init_
     });
 }
 
+// bddmma_bdds_solution(member i, 0, ..) / bddmma_update_costs(member i, .., nr_variables(i), .., nr_variables(i), ..) /
+// bddmma_grad_cost_perturbation(member i, ..) of every member, one launch per kernel instantiation present (solver_bt.hpp:
+// BatchT::bdds_solution, update_costs, grad_cost_perturbation)
+int bddmma_bdds_solution_batch(bddmma_batch* b, char* sol, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!sol) { i->err = "batch bdds_solution: null output pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        return i->bdds_solution(sol, on_device);
+    });
+}
+int bddmma_update_costs_batch(bddmma_batch* b, const void* lo, const void* hi, int elem_precision, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) { return i->update_costs(lo, hi, elem_precision, on_device); });
+}
+int bddmma_grad_cost_perturbation_batch(bddmma_batch* b, const void* grad_lo, const void* grad_hi, void* grad_lo_pert_out, void* grad_hi_pert_out, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!grad_lo || !grad_hi || !grad_lo_pert_out || !grad_hi_pert_out) { i->err = "batch grad_cost_perturbation: null pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        return i->grad_cost_perturbation(grad_lo, grad_hi, grad_lo_pert_out, grad_hi_pert_out, on_device);
+    });
+}
+
 // ---- checkpoint (bdd_cuda_base.cu:1486-1550: every index array of the layout + the costs are archived) -------------------------
 // File: magic, header {precision, #arrays, sizeof(LayoutScalars), sizeof(bddmma_options)}, LayoutScalars, options, the layout arrays
 // as {id, element size, count, data} records (layout.hpp: visit_layout_arrays), then lo / hi / deferred mm / delta.  Loading

@@ -2,7 +2,8 @@
 // grad_lower_bound_per_bdd, distribute_delta).  k_small_bounds_batch: lower_bound_per_bdd of every member; k_small_grad_lb_batch:
 // grad_lower_bound_per_bdd (smooth = 0) of every member, one workgroup per member; k_small_distribute_batch: distribute_delta of every
 // member.  Not part of kernels.hpp: the kernels are instantiated in solver_bb_f32.hip / solver_bb_f64.hip only (solver_bb.hpp);
-// solver_bt.hpp includes this file for the item and the getters.
+// solver_bt.hpp includes this file for the item and the getters.  bound_path_pass, the arg-min path pass of a pack, is shared with
+// k_small_solution_batch (kernels/batchsol.hpp).
 #pragma once
 
 namespace bddmma {
@@ -55,38 +56,38 @@ __global__ void __launch_bounds__(256) k_small_grad_lb_check(const BoundItem<REA
     if (b) atomicMin(bad, it.member);
 }
 
-// The arg-min path of every BDD of the member, wave p on pack p (n_packs <= NW), and k_grad_lb's two products per layer.  The pass is the
-// history step's of small_iterate (kernels/small.hpp), which is FWD_SOLUTION's (kernels/narrow.hpp) out of LDS: a plain forward pass over
-// the pack's hops from the costs-to-terminal in memory (valid: BatchT::join_in) and the arc costs, the second-generation resident
+// The arg-min path of every BDD of one pack, by its wave (lane `lane` of wave p on pack p < n_packs): the path pass of
+// k_small_grad_lb_batch and of k_small_solution_batch (kernels/batchsol.hpp), written once, so that both decide ties alike.  The pass is
+// the history step's of small_iterate (kernels/small.hpp), which is FWD_SOLUTION's (kernels/narrow.hpp) out of LDS: a plain forward pass
+// over the pack's hops from the costs-to-terminal in memory (valid: BatchT::join_in) and the arc costs, the second-generation resident
 // records from the pack's first hop downwards.  Roots start with cost-from-root 0 and on the path; a node on the path decides
 // take_lo = ((f + (th + hi)) - (f + (tl + lo))) > 0, writes the decision of its layer and marks the child taken; every node pushes
 // f + cost into its children (a push into a sink or from a padding lane goes as +inf into the lane's own entry).  The on-path marks of a
 // hop's nodes are 64 entries indexed by the node's slot modulo 64: a hop's slots are consecutive and at most 64.
-// A wave reads and writes its own pack's layers only and fetches grad_lb per layer: the kernel has no workgroup barrier.
-template <typename REAL, int NW>
-__global__ void __launch_bounds__(64 * NW) k_small_grad_lb_batch(const BoundItem<REAL>* __restrict__ items, const REAL* __restrict__ grad_lb, REAL* __restrict__ grad_lo,
-                                                                 REAL* __restrict__ grad_hi)
+// The pack's region of the dynamic LDS is bound_region_bytes; a wave reads and writes its own pack's region only: no workgroup barrier.
+// Out: the pack's first layer and its number of layers, and `dc`, the LDS byte offset of the pack's decisions — REAL 0 / 1 per layer, 0
+// where no node of the layer is on the path, as the memset of the solution buffer leaves it.  Returns false, with nothing in LDS, for a
+// pack without a hop.
+template <typename REAL>
+__device__ __forceinline__ bool bound_path_pass(unsigned char* dyn_lds, const BoundItem<REAL>& it, uint32_t p, uint32_t lane, uint32_t& layer0, uint32_t& nlayers,
+                                                uint32_t& dc)
 {
     constexpr uint32_t S = sizeof(REAL);
     using P2 = typename Pair<REAL>::type;
     constexpr uint32_t P2S = (uint32_t)sizeof(P2);
-    extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
-    const BoundItem<REAL>& it = items[blockIdx.x];
-    const uint32_t tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
-    const uint32_t lane = tid & 63u;
-    const uint32_t p = (uint32_t)wave;
-    if (p >= it.n_packs) return;
     const uint32_t* const hp = it.pack_hdr + 8 * (size_t)p;
-    const uint32_t slot0 = hp[0], nslots = hp[1], layer0 = hp[2], nlayers = hp[3];
+    const uint32_t slot0 = hp[0], nslots = hp[1];
+    layer0 = hp[2];
+    nlayers = hp[3];
     // (wave-uniform by construction; said so, or every record load's scalar offset is wrapped in a loop over its distinct values)
     const uint32_t nh = __builtin_amdgcn_readfirstlane(hp[5] & 0xFFFFu);
-    if (nh == 0u) return;
+    if (nh == 0u) return false;
     const uint32_t rbase = __builtin_amdgcn_readfirstlane(it.rec_off[p]);
     const REAL INF = inf_v<REAL>();
     const uint32_t ns = it.ns;
     const uint32_t wb = p * bound_region_bytes(S, ns, it.nl), wbF = wb + res2_f_off(S, ns), wbC = wb + res2_c_off(S, ns);
-    const uint32_t mk = wb + res2_wave_bytes(S, ns, it.nl), dc = mk + 64u * S;
+    const uint32_t mk = wb + res2_wave_bytes(S, ns, it.nl);
+    dc = mk + 64u * S;
     const uint32_t f_end = res2_f_off(S, ns) + ns * S;
     const rsrc_t rr = make_rsrc(it.rec, it.rec_words);
     // ---- the pack's state -> LDS
@@ -140,6 +141,26 @@ __global__ void __launch_bounds__(64 * NW) k_small_grad_lb_batch(const BoundItem
         BOUND_HOP(r0, 0) BOUND_HOP(r1, 1) BOUND_HOP(r2, 2) BOUND_HOP(r3, 3) BOUND_HOP(r4, 4) BOUND_HOP(r5, 5) BOUND_HOP(r6, 6) BOUND_HOP(r7, 7)
     }
 #undef BOUND_HOP
+    return true;
+}
+
+// grad_lower_bound_per_bdd (smooth = 0) of every member, wave p on pack p (n_packs <= NW): the path pass above and k_grad_lb's two
+// products per layer.  A wave reads and writes its own pack's layers only and fetches grad_lb per layer: the kernel has no workgroup
+// barrier.
+template <typename REAL, int NW>
+__global__ void __launch_bounds__(64 * NW) k_small_grad_lb_batch(const BoundItem<REAL>* __restrict__ items, const REAL* __restrict__ grad_lb, REAL* __restrict__ grad_lo,
+                                                                 REAL* __restrict__ grad_hi)
+{
+    constexpr uint32_t S = sizeof(REAL);
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
+    const BoundItem<REAL>& it = items[blockIdx.x];
+    const uint32_t tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const uint32_t lane = tid & 63u;
+    const uint32_t p = (uint32_t)wave;
+    if (p >= it.n_packs) return;
+    uint32_t layer0, nlayers, dc;
+    if (!bound_path_pass<REAL>(dyn_lds, it, p, lane, layer0, nlayers, dc)) return;
     // k_grad_lb (kernels/elementwise.hpp), its two expressions, for the pack's layers
     const REAL* const gm = grad_lb + it.src_b;
     REAL* const olo = grad_lo + (size_t)it.src + layer0;

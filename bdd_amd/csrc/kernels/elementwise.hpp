@@ -802,13 +802,12 @@ __global__ void k_grad_distribute(const REAL* __restrict__ g_lo, const REAL* __r
     if (l < n) out[l] = mm_binned[lpos[l]] > REAL(0) ? g_hi[l] : -g_lo[l];
 }
 // grad_cost_perturbation (:1079-1102): update_costs gives every layer of variable v the share pert[v] / nr_bdds(v); one thread per variable
-// sums its layers in the order of the variable -> layer table
+// sums its layers in the order of the variable -> layer table.  (The sums and the quotient are written once, as ew_grad_perturb:
+// k_small_grad_perturb_batch, kernels/batchsol.hpp, evaluates the same ones on a member's part of the batch's arrays.)
 template <typename REAL>
-__global__ void k_grad_perturb(const REAL* __restrict__ g_lo, const REAL* __restrict__ g_hi, const uint32_t* __restrict__ var_ptr,
-                               const uint32_t* __restrict__ var_layers, REAL* __restrict__ out_lo, REAL* __restrict__ out_hi, uint32_t n_vars)
+__device__ __forceinline__ void ew_grad_perturb(const REAL* __restrict__ g_lo, const REAL* __restrict__ g_hi, const uint32_t* __restrict__ var_ptr,
+                                                const uint32_t* __restrict__ var_layers, uint32_t v, REAL& out_lo, REAL& out_hi)
 {
-    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= n_vars) return;
     const uint32_t k0 = var_ptr[v], k1 = var_ptr[v + 1];
     REAL s0 = 0, s1 = 0;
     for (uint32_t k = k0; k < k1; ++k) {
@@ -816,8 +815,19 @@ __global__ void k_grad_perturb(const REAL* __restrict__ g_lo, const REAL* __rest
         s1 += g_hi[var_layers[k]];
     }
     const REAL nb = REAL(k1 > k0 ? k1 - k0 : 1u);
-    out_lo[v] = s0 / nb;
-    out_hi[v] = s1 / nb;
+    out_lo = s0 / nb;
+    out_hi = s1 / nb;
+}
+template <typename REAL>
+__global__ void k_grad_perturb(const REAL* __restrict__ g_lo, const REAL* __restrict__ g_hi, const uint32_t* __restrict__ var_ptr,
+                               const uint32_t* __restrict__ var_layers, REAL* __restrict__ out_lo, REAL* __restrict__ out_hi, uint32_t n_vars)
+{
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_vars) return;
+    REAL s0, s1;
+    ew_grad_perturb<REAL>(g_lo, g_hi, var_ptr, var_layers, v, s0, s1);
+    out_lo[v] = s0;
+    out_hi[v] = s1;
 }
 
 }  // namespace bddmma

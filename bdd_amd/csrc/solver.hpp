@@ -218,6 +218,13 @@ struct BatchBase {
     // nr_variables entries one behind the other
     virtual int perturb_primal_costs(double delta, uint32_t round, uint32_t seed, uint32_t* counts, char* sol, void* c0, void* c1) = 0;
     virtual int rounding(double init_delta, double growth, uint64_t num_itr_lb, uint64_t num_rounds, uint32_t seed, char* sol, int* found, uint64_t* rounds) = 0;
+    // SolverBase::bdds_solution (unsorted) / update_costs (both vectors full length or null) / grad_cost_perturbation of every member, one
+    // launch per kernel instantiation present (kernels/batchsol.hpp; include/bdd_mma.h: bddmma_bdds_solution_batch,
+    // bddmma_update_costs_batch, bddmma_grad_cost_perturbation_batch); per-variable arrays: the members' nr_variables entries one behind
+    // the other, layer arrays as in learned_iterations
+    virtual int bdds_solution(char* sol, int on_device) = 0;
+    virtual int update_costs(const void* lo, const void* hi, int elem_precision, int on_device) = 0;
+    virtual int grad_cost_perturbation(const void* grad_lo, const void* grad_hi, void* grad_lo_pert, void* grad_hi_pert, int on_device) = 0;
     // the batch stream behind everything queued on `other` so far / the reverse, by an event the batch owns; the host does not wait
     virtual int stream_wait(hipStream_t other) = 0;
     virtual int stream_signal(hipStream_t other) = 0;

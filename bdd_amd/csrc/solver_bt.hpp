@@ -12,6 +12,7 @@
 #include "kernels/batchmm.hpp"
 #include "kernels/batchsm.hpp"
 #include "kernels/batchround.hpp"
+#include "kernels/batchsol.hpp"
 #include "kernels/smallhist.hpp"
 
 namespace bddmma {
@@ -47,7 +48,7 @@ struct BatchT final : BatchBase {
         for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1, ev_order})
             if (e) (void)hipEventDestroy(e);
         if (d_items) (void)hipFree(d_items);
-        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad, (void*)d_bm_items, (void*)d_bm_stage, (void*)d_bm_bad, (void*)d_bsm_items, (void*)d_bsm_stage, (void*)d_br_items, (void*)d_br_words})
+        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad, (void*)d_bm_items, (void*)d_bm_stage, (void*)d_bm_bad, (void*)d_bsm_items, (void*)d_bsm_stage, (void*)d_br_items, (void*)d_br_words, (void*)d_bp_items, (void*)d_bp_stage, (void*)d_bp_bad})
             if (q) (void)hipFree(q);
         if (d_ctl) (void)hipFree(d_ctl);
         if (h_ctl) (void)hipHostFree(h_ctl);
@@ -1468,6 +1469,173 @@ struct BatchT final : BatchBase {
             if ((rc = run_plain(num_itr_lb, 1e-7, 0.0001, std::numeric_limits<double>::max(), nullptr, mask.data()))) return rc;
         }
         return BDDMMA_OK;
+    }
+    // ---- per-BDD solutions, cost updates and the gradient of a cost perturbation, all members at once (kernels/batchsol.hpp:
+    // k_small_solution_batch, k_small_update_batch, k_small_grad_perturb_batch; the kernels compile in solver_bp_f32.hip / _f64.hip).
+    // The solution kernel takes the bound gradient's items, groups and LDS (bb_prepare: one launch per wave count present) and, for host
+    // output, its staging buffer; the two per-variable kernels have items of their own in the caller's order, one launch for all.  Their
+    // host arrays pass through one staging buffer the batch owns; it and the check word are allocated before any member is touched.
+    std::vector<SolutionFn<REAL>> bp_sol_fn;   // per entry of bb_groups
+    PerturbItem<REAL>* d_bp_items = nullptr;
+    unsigned char* d_bp_stage = nullptr;
+    uint32_t* d_bp_bad = nullptr;
+    uint64_t bp_layers = 0, bp_vars = 0;       // values of all members' layers / variables
+    bool bp_ready = false;
+
+    int bp_sol_prepare(bool host_arrays)
+    {
+        if (int rc = bb_prepare(false, host_arrays)) return rc;   // (its staging buffer holds bb_bdds + 2 bb_layers values: more than bb_layers bytes)
+        if (bp_sol_fn.size() == bb_groups.size()) return BDDMMA_OK;
+        std::vector<SolutionFn<REAL>> fns;
+        for (const BbGroup& g : bb_groups) {
+            fns.push_back(solution_fn<REAL>((int)(g.threads / 64u)));
+            // the pack's region is the bound gradient's (kernels/batchbound.hpp: bound_region_bytes), g.lds the group's largest n_packs of them
+            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(fns.back()), g.lds)) return rc;
+        }
+        bp_sol_fn = std::move(fns);
+        return BDDMMA_OK;
+    }
+    int bdds_solution(char* sol, int on_dev) override
+    {
+        int rc;
+        if (!sol) { err = "batch bdds_solution: null output pointer"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if ((rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bp_sol_prepare(!on_dev))) return rc;
+        if ((rc = join_in())) { (void)join_out(); return rc; }
+        char* const o = on_dev ? sol : reinterpret_cast<char*>(d_bb_stage);
+        hipError_t e = hipSuccess;
+        for (size_t k = 0; k < bb_groups.size() && e == hipSuccess; ++k) {
+            const BbGroup& G = bb_groups[k];
+            hipLaunchKernelGGL(bp_sol_fn[k], dim3(G.count), dim3(G.threads), G.lds, stream, (const BoundItem<REAL>*)(d_bb_items + G.first), o);
+            e = hipGetLastError();
+        }
+        if (!on_dev) {
+            if (e == hipSuccess) e = hipMemcpyAsync(sol, o, bb_layers, hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        }
+        const int rc2 = join_out();
+        if (e != hipSuccess) { err = std::string("batch bdds_solution: ") + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        return rc2;
+    }
+    // host_arrays: the call needs the staging buffer — update_costs: lo | hi, bp_vars values of up to 8 bytes each; the gradient:
+    // grad_lo | grad_hi | lo_pert | hi_pert
+    int bp_prepare(bool host_arrays)
+    {
+        const uint32_t n = (uint32_t)m.size();
+        if (!bp_ready) {
+            uint64_t total = 0, total_v = 0;
+            std::vector<PerturbItem<REAL>> items(n);
+            for (uint32_t i = 0; i < n; ++i) {
+                const S* s = m[i];
+                items[i] = PerturbItem<REAL>{s->d_lohi, s->d_var, s->d_nbdds, s->d_var_ptr, s->d_var_layers, (uint32_t)s->n_layers, (uint32_t)s->n_vars,
+                                             (uint32_t)total, (uint32_t)total_v};
+                total += s->n_layers;
+                total_v += s->n_vars;
+            }
+            if (total > 0xFFFFFFFFull || total_v > 0xFFFFFFFFull) { err = "batch update_costs: too many layers"; return BDDMMA_ERR_UNSUPPORTED; }
+            if (!d_bp_items) HIPCHK(hipMalloc((void**)&d_bp_items, n * sizeof(PerturbItem<REAL>)));
+            if (!d_bp_bad) HIPCHK(hipMalloc((void**)&d_bp_bad, sizeof(uint32_t)));
+            HIPCHK(hipMemcpy(d_bp_items, items.data(), n * sizeof(PerturbItem<REAL>), hipMemcpyHostToDevice));
+            bp_layers = total;
+            bp_vars = total_v;
+            bp_ready = true;
+        }
+        if (host_arrays && !d_bp_stage)
+            HIPCHK(hipMalloc((void**)&d_bp_stage, std::max<uint64_t>(std::max<uint64_t>(2 * bp_vars * sizeof(double), 2 * (bp_layers + bp_vars) * sizeof(REAL)), 16)));
+        return BDDMMA_OK;
+    }
+    template <typename TIN>
+    int update_both(const void* lo, const void* hi, int on_dev)
+    {
+        const TIN* a[2] = {(const TIN*)lo, (const TIN*)hi};
+        hipError_t e = hipSuccess;
+        if (!on_dev)
+            for (int k = 0; k < 2 && e == hipSuccess; ++k)
+                if (a[k]) {
+                    TIN* const st = reinterpret_cast<TIN*>(d_bp_stage) + (uint64_t)k * bp_vars;
+                    e = hipMemcpyAsync(st, a[k], bp_vars * sizeof(TIN), hipMemcpyHostToDevice, stream);
+                    a[k] = st;
+                }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL((perturb_update_fn<REAL, TIN>()), dim3((uint32_t)m.size()), dim3(256), 0, stream, (const PerturbItem<REAL>*)d_bp_items, a[0], a[1]);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess && !on_dev) e = hipStreamSynchronize(stream);   // the caller may reuse its arrays on return
+        // the host-side state after SolverT::update_costs
+        for (S* s : m) s->costs_changed();
+        const int rc2 = join_out();
+        if (e != hipSuccess) { err = std::string("batch update_costs: ") + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        return rc2;
+    }
+    int update_costs(const void* lo, const void* hi, int elem_precision, int on_dev) override
+    {
+        int rc;
+        if ((rc = check_state())) return rc;
+        if (!lo && !hi) return BDDMMA_OK;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bp_prepare(!on_dev))) return rc;
+        if ((rc = members_in())) return rc;
+        // ---- the members are touched from here on
+        return elem_precision == BDDMMA_F64 ? update_both<double>(lo, hi, on_dev) : update_both<float>(lo, hi, on_dev);
+    }
+    int grad_cost_perturbation(const void* grad_lo, const void* grad_hi, void* lo_pert, void* hi_pert, int on_dev) override
+    {
+        int rc;
+        const char* const me = "batch grad_cost_perturbation";
+        const uint32_t n = (uint32_t)m.size();
+        if (!grad_lo || !grad_hi || !lo_pert || !hi_pert) { err = std::string(me) + ": null pointer"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if ((rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bp_prepare(!on_dev))) return rc;   // (the members' variable -> layer tables exist since their construction)
+        // the argument check, before any output is touched: host values here, device values by one launch for all members (the batch
+        // stream is behind whatever the caller ordered it behind: bddmma_stream_wait_batch) and the call's one read.  bad: 2 * member + array
+        uint32_t bad = 0xFFFFFFFFu;
+        if (!on_dev) {
+            const REAL* h[2] = {(const REAL*)grad_lo, (const REAL*)grad_hi};
+            uint64_t at = 0;
+            for (uint32_t i = 0; i < n && bad == 0xFFFFFFFFu; ++i) {
+                for (uint32_t k = 0; k < 2u && bad == 0xFFFFFFFFu; ++k)
+                    for (uint64_t l = 0; l < m[i]->n_layers; ++l)
+                        if (!std::isfinite(h[k][at + l])) { bad = 2u * i + k; break; }
+                at += m[i]->n_layers;
+            }
+        } else {
+            HIPCHK(hipMemsetAsync(d_bp_bad, 0xFF, sizeof(uint32_t), stream));
+            hipLaunchKernelGGL(perturb_check_fn<REAL>(), dim3(n), dim3(256), 0, stream, (const PerturbItem<REAL>*)d_bp_items, (const REAL*)grad_lo, (const REAL*)grad_hi, d_bp_bad);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&bad, d_bp_bad, sizeof(bad), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+        if (bad != 0xFFFFFFFFu) {
+            err = "batch member " + std::to_string(bad / 2u) + ": some of its " + ((bad & 1u) ? "grad_hi" : "grad_lo") + " are not finite";
+            return BDDMMA_ERR_INVALID_ARGUMENT;
+        }
+        if ((rc = members_in())) return rc;   // (no member's state is read beyond its layout; the order is that of every batch call)
+        const REAL *glo = (const REAL*)grad_lo, *ghi = (const REAL*)grad_hi;
+        REAL *olo = (REAL*)lo_pert, *ohi = (REAL*)hi_pert;
+        hipError_t e = hipSuccess;
+        if (!on_dev) {
+            REAL* const st = reinterpret_cast<REAL*>(d_bp_stage);
+            e = hipMemcpyAsync(st, grad_lo, bp_layers * sizeof(REAL), hipMemcpyHostToDevice, stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(st + bp_layers, grad_hi, bp_layers * sizeof(REAL), hipMemcpyHostToDevice, stream);
+            glo = st;
+            ghi = st + bp_layers;
+            olo = st + 2 * bp_layers;
+            ohi = olo + bp_vars;
+        }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(perturb_grad_fn<REAL>(), dim3(n), dim3(256), 0, stream, (const PerturbItem<REAL>*)d_bp_items, glo, ghi, olo, ohi);
+            e = hipGetLastError();
+        }
+        if (!on_dev) {
+            if (e == hipSuccess) e = hipMemcpyAsync(lo_pert, olo, bp_vars * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(hi_pert, ohi, bp_vars * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        }
+        const int rc2 = join_out();
+        if (e != hipSuccess) { err = std::string(me) + ": " + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        return rc2;
     }
     int stream_wait(hipStream_t other) override
     {

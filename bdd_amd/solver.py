@@ -901,6 +901,62 @@ class bdd_hip_batch:
         sols = [[float(x) for x in sol[off[i]:off[i + 1]]] if found[i] else [] for i in range(len(nv))]
         return (sols, [int(r) for r in rounds]) if return_rounds else sols
 
+    # ---- per-BDD solutions, cost updates and the gradient of a cost perturbation (include/bdd_mma.h: bddmma_bdds_solution_batch and the two
+    # entries behind it)
+    def bdds_solution_vec(self, out=None):
+        """bdds_solution_vec() of every member, one workgroup per member: the arg-min path of every BDD as int8 0 / 1 per layer, the
+        members' [nr_layers] one behind the other in the members' order.  out: an int8 device buffer, written in the batch stream's order
+        (the host does not wait); without it a new NumPy int8 array."""
+        n = sum(s.nr_layers() for s in self.solvers)
+        if out is not None:
+            assert _is_dev(out), "out: a device buffer"
+            self._check(self._L.bddmma_bdds_solution_batch(self._h, _dev_ptr(out, n, np.int8), 1), self._h)
+            return out
+        out = np.zeros(n, np.int8)
+        self._check(self._L.bddmma_bdds_solution_batch(self._h, _ptr(out), 0), self._h)
+        return out
+
+    def update_costs(self, cost_delta_0, cost_delta_1):
+        """update_costs(cost_delta_0_i, cost_delta_1_i) of every member i in one launch: the members' [nr_variables] one behind the other in
+        the members' order, every layer of a variable gets its value / nr_bdds(variable).  Device tensors of the members' precision take
+        the device path (the host does not wait); host arrays are passed as float64, as the member method passes them.  None leaves
+        that side of every member's costs as it is."""
+        nv = sum(s.nr_variables() for s in self.solvers)
+        given = [x for x in (cost_delta_0, cost_delta_1) if x is not None]
+        dev = bool(given) and _is_dev(given[0])
+        if any(_is_dev(x) != dev for x in given):
+            raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: the arrays of a batch call must all be on the host or all "
+                                   "on the device")
+        s0 = self.solvers[0]
+        if dev:
+            ptrs = [None if x is None else _dev_ptr(x, nv, s0.value_type) for x in (cost_delta_0, cost_delta_1)]
+            self._check(self._L.bddmma_update_costs_batch(self._h, *ptrs, s0._prec, 1), self._h)
+            return
+        arrays = [None if x is None else np.ascontiguousarray(x, dtype=np.float64) for x in (cost_delta_0, cost_delta_1)]
+        for x in arrays:
+            assert x is None or x.size == nv, f"update_costs: expected {nv} values, got {x.size}"
+        self._check(self._L.bddmma_update_costs_batch(self._h, *(_ptr(x) for x in arrays), capi.F64, 0), self._h)
+
+    def grad_cost_perturbation(self, grad_lo, grad_hi, out=None):
+        """grad_cost_perturbation(grad_lo_i, grad_hi_i) of every member i in one launch: (grad_lo_pert, grad_hi_pert), the members'
+        REAL[nr_variables] one behind the other; grad_lo / grad_hi: the members' REAL[nr_layers] one behind the other.  Device tensors
+        need out = (lo_pert, hi_pert) device buffers, NumPy arrays give two new NumPy arrays."""
+        n = sum(s.nr_layers() for s in self.solvers)
+        nv = sum(s.nr_variables() for s in self.solvers)
+        vt = self.solvers[0].value_type
+        call = self._L.bddmma_grad_cost_perturbation_batch
+        if _is_dev(grad_lo) or _is_dev(grad_hi):
+            assert _is_dev(grad_lo) and _is_dev(grad_hi), "the arrays of a batch call must all be on the host or all on the device"
+            assert out is not None and len(out) == 2 and all(_is_dev(x) for x in out), "device gradients need device output buffers: out=(lo_pert, hi_pert)"
+            self._check(call(self._h, _dev_ptr(grad_lo, n, vt), _dev_ptr(grad_hi, n, vt), _dev_ptr(out[0], nv, vt), _dev_ptr(out[1], nv, vt), 1), self._h)
+            return out[0], out[1]
+        g = [np.ascontiguousarray(x, dtype=vt) for x in (grad_lo, grad_hi)]
+        for x in g:
+            assert x.size == n, f"expected {n} values, got {x.size}"
+        lo, hi = np.zeros(nv, vt), np.zeros(nv, vt)
+        self._check(call(self._h, _ptr(g[0]), _ptr(g[1]), _ptr(lo), _ptr(hi), 0), self._h)
+        return lo, hi
+
     # ---- ordering against other streams (include/bdd_mma.h: bddmma_stream_wait_batch / bddmma_stream_signal_batch)
     def stream_wait(self, hip_stream=0):
         """what the batch's calls queue from now on starts after everything queued so far on `hip_stream` (a raw hipStream_t as an

@@ -679,6 +679,37 @@ int bddmma_perturb_primal_costs_batch(bddmma_batch* b, double cur_delta, uint32_
 int bddmma_incremental_mm_agreement_rounding_batch(bddmma_batch* b, double init_delta, double delta_growth_rate, uint64_t num_itr_lb, uint64_t num_rounds,
                                                    uint32_t seed, char* sol, int* found, uint64_t* rounds);
 
+/* Per-BDD solutions, cost updates and the gradient of a cost perturbation for a batch (kernels/batchsol.hpp), one launch each; named
+ * after the per-member calls they are.  Layer arrays are the members' [nr_layers] in the public layer order, per-variable arrays the
+ * members' [nr_variables], each one behind the other in the members' order at bddmma_batch_create.  The on_device flag, host staging
+ * (one buffer the batch owns, one host synchronisation), device ordering (the batch's stream; with device arrays the host does not wait,
+ * except for the one word the gradient's argument check reads back) and the refusals are those of the batch entry points above: b == NULL
+ * or a required null array is BDDMMA_ERR_INVALID_ARGUMENT, BDDMMA_ERR_STATE as for every batch call, each decided before any member or
+ * output is touched and after whatever has to be allocated has been allocated.  Results and every member's state afterwards are
+ * bit-equal to the per-member calls in float and in double.
+ *
+ * bddmma_bdds_solution_batch: bddmma_bdds_solution(member i, sorted 0, its part of sol, ..) for every member i: one workgroup per member,
+ * a wave per pack, runs the arg-min path of every BDD out of LDS (the path pass of bddmma_grad_lower_bound_per_bdd_batch, so the same
+ * tie rule) and writes the decision of every layer as a char, 0 where no node of the layer is on the path; one launch per wave count
+ * present.  sol: char per layer; there is no sorted form.  Members whose costs-to-terminal are stale get their own backward sweep first;
+ * afterwards the backward state is valid, the forward state what it was, and nothing else has changed. */
+int bddmma_bdds_solution_batch(bddmma_batch* b, char* sol, int on_device);
+/* bddmma_update_costs(member i, its part of lo, nr_variables(i), its part of hi, nr_variables(i), elem_precision, on_device) for every
+ * member i in one launch: every layer of a variable gets lo[variable] / nr_bdds(variable) resp. hi[..], quotient and sum in double and
+ * rounded once, as that call forms them.  lo / hi: full-length per-variable arrays of elem_precision (BDDMMA_F32 / BDDMMA_F64); either may
+ * be NULL and that side is then untouched on every member; both NULL: BDDMMA_OK, nothing is done.  No value is checked, as
+ * bddmma_update_costs checks none.  State afterwards, per member, that of the per-member call: both sweep states invalid and the cached
+ * bound dropped; deferred differences and delta are untouched.  There is no L-BFGS form. */
+int bddmma_update_costs_batch(bddmma_batch* b, const void* lo /* or NULL */, const void* hi /* or NULL */, int elem_precision, int on_device);
+/* bddmma_grad_cost_perturbation(member i, its parts, ..) for every member i in one launch: per variable the sum of grad_lo resp. grad_hi
+ * over its layers, in the order of the member's variable -> layer table, divided by max(nr_bdds, 1).  grad_lo / grad_hi: REAL per layer,
+ * read where the caller has them; the outputs: REAL per variable.  A value of grad_lo or grad_hi that is not finite:
+ * BDDMMA_ERR_INVALID_ARGUMENT, bddmma_batch_last_error naming the first offending member and, of its arrays, the first in the per-member
+ * call's order (grad_lo, then grad_hi), the outputs untouched (host values are checked on the host, device values by one check launch
+ * for all members).  No member's state is read beyond its layout, and none changes. */
+int bddmma_grad_cost_perturbation_batch(bddmma_batch* b, const void* grad_lo, const void* grad_hi, void* grad_lo_pert_out, void* grad_hi_pert_out,
+                                        int on_device);
+
 /* ---- checkpoint (bdd_cuda_base.cu:1486-1550) ------------------------------ */
 int bddmma_save(const bddmma_solver* s, const char* path);
 int bddmma_load(bddmma_solver** out, int device, const char* path);
