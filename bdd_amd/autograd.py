@@ -271,17 +271,20 @@ class DualIterations(torch.autograd.Function):
     (lo, hi, def_mm, sol_avg, lb_first_diff_avg, lb_second_diff_avg).
 
     forward   learned_iterations on every solver, from the given costs and deferred differences — for a bdd_hip_batch whose members are all
-              fused_small_learned(), with improvement_slope <= 0, three batch calls and none on a member: ONE
+              fused_small_learned(), three batch calls and none on a member: ONE
               batch.set_solver_costs, ONE batch.learned_iterations(_history) and ONE batch.get_solver_costs (the same results: bit-equal in float,
-              and in double wherever no variable sits in more than two BDDs).  With compute_history_for_itrs > 0 the same three calls
+              and in double wherever no variable sits in more than two BDDs).  With improvement_slope > 0 the middle call is ONE
+              batch.learned_iterations_stopping where every member is fused_small_stop(): the stopping rule runs inside the members'
+              workgroups and the call returns each member's count.  With compute_history_for_itrs > 0 the same three calls
               where every member is fused_small_history() and num_iterations >= compute_history_for_itrs (what the reference asserts):
               the history steps run inside the members' workgroups.  omega is a tensor: one value (the scalar
               call) or one per layer (learned_iterations' omega_vec).  With improvement_slope > 0 the solvers may stop at different
-              counts; each count is remembered.  The last three outputs are None unless compute_history_for_itrs > 0 (they start as
+              counts; each count is remembered (ctx.iterations_done), in the batched form from the call's returned counts.  The last three outputs are None unless compute_history_for_itrs > 0 (they start as
               zeros: an entry the history does not reach keeps that) and are not differentiable.
     backward  bddmma_grad_learned_iterations per solver with track_grad_for_num_itr = min(iterations done, grad_dual_itr_max_itr) and
               track_grad_after_itr = done - that: the untracked iterations are treated as constants, as in the reference.  For a
-              bdd_hip_batch whose members are all fused_small_learned() and ran the same number of iterations, ONE
+              bdd_hip_batch whose members are all fused_small_learned() and ran the same number of iterations (with different counts — a
+              stopping rule — it stays this loop: a batch call with per-member counts does not exist), ONE
               batch.set_solver_costs and ONE batch.grad_iterations (bddmma_grad_learned_iterations_batch: one workgroup per member)
               instead of that loop, with the same results (bit-equal in float, and in double wherever no variable
               sits in more than two BDDs).  Gradients for
@@ -311,18 +314,25 @@ class DualIterations(torch.autograd.Function):
             ctx.mark_non_differentiable(sol_avg, lb1, lb2)
         omega_scalar = None if per_layer_omega else float(omega.reshape(-1)[0].item())
         done = []
-        batched = z.batch is not None and not float(improvement_slope) > 0 and all(s.fused_small_learned() for s in z.solvers)
+        stopping = float(improvement_slope) > 0   # the rule inside the members' workgroups: every member fused_small_stop()
+        batched = z.batch is not None and all(s.fused_small_stop() if stopping else s.fused_small_learned() for s in z.solvers)
         if batched and history > 0:   # the history inside the members' workgroups; as the reference asserts, no more of it than iterations
             batched = int(num_iterations) >= history and all(s.fused_small_history() for s in z.solvers)
         if batched:
             hist = dict(compute_history_for_itr=history, history_avg_beta=float(history_avg_beta), sol_avg=sol_avg, lb_first_diff_avg=lb1,
                         lb_second_diff_avg=lb2) if history > 0 else {}
+            done = [int(num_iterations)] * len(z.solvers)
             with _Ordered([z.batch]):   # batch calls only: each orders itself against the members' streams
                 z.batch.set_solver_costs(lo_costs_batch, hi_costs_batch, def_mm_batch)
-                z.batch.learned_iterations_history(dist_weights_batch, int(num_iterations), omega=0.5 if per_layer_omega else omega_scalar,
-                                                   omega_vec=omega if per_layer_omega else None, **hist)
+                if stopping:
+                    done = z.batch.learned_iterations_stopping(dist_weights_batch, int(num_iterations), omega=0.5 if per_layer_omega else omega_scalar,
+                                                               improvement_slope=float(improvement_slope), omega_vec=omega if per_layer_omega else None,
+                                                               **hist)
+                else:
+                    z.batch.learned_iterations_history(dist_weights_batch, int(num_iterations), omega=0.5 if per_layer_omega else omega_scalar,
+                                                       omega_vec=omega if per_layer_omega else None, **hist)
                 z.batch.get_solver_costs(out=(lo, hi, mm))
-            ctx.iterations_done, ctx.omega_scalar = [int(num_iterations)] * len(z.solvers), omega_scalar
+            ctx.iterations_done, ctx.omega_scalar = done, omega_scalar
             return lo, hi, mm, sol_avg, lb1, lb2
         with _Ordered(z.solvers):
             for s, l, b in zip(z.solvers, z.slices(z.layers), z.slices(z.bdds)):

@@ -68,6 +68,7 @@ SIGNATURES = {
     "bddmma_fused_small": (_I, [_V]),
     "bddmma_fused_small_learned": (_I, [_V]),
     "bddmma_fused_small_history": (_I, [_V]),
+    "bddmma_fused_small_stop": (_I, [_V]),
     "bddmma_nontemporal_loads": (_I, [_V]),
     "bddmma_potentials_on_chip": (_I, [_V]),
     "bddmma_onchip_hops": (_I, [_V]),
@@ -127,6 +128,7 @@ SIGNATURES = {
     "bddmma_batch_iterations": (_I, [_V, _D, _U64]),
     "bddmma_learned_iterations_batch": (_I, [_V, _V, _V, _D, _U64, _I]),
     "bddmma_learned_iterations_history_batch": (_I, [_V, _V, _V, _D, _U64, _V, _V, _V, _U64, _D, _I]),
+    "bddmma_learned_iterations_stop_batch": (_I, [_V, _V, _V, _D, _U64, _D, _V, _V, _V, _U64, _D, _I, _V]),
     "bddmma_grad_learned_iterations_batch": (_I, [_V, _V, _V, _D, _V, _V, _V, _V, _V, _U64, _U64, _U64, _I]),
     "bddmma_set_solver_costs_batch": (_I, [_V, _V, _V, _V, _I]),
     "bddmma_get_solver_costs_batch": (_I, [_V, _V, _V, _V, _I]),

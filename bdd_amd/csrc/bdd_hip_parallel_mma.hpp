@@ -83,6 +83,8 @@ class bdd_hip_parallel_mma {
     size_t nr_layers() const { return bddmma_nr_layers(h_); }
     // a bdd_hip_batch can run this solver's learned iterations with their history inside one workgroup (bddmma_fused_small_history)
     bool fused_small_history() const { return bddmma_fused_small_history(h_) == 1; }
+    // a bdd_hip_batch can run this solver's stopping rule (improvement_slope > 0) inside its workgroup too (bddmma_fused_small_stop)
+    bool fused_small_stop() const { return bddmma_fused_small_stop(h_) == 1; }
     size_t nr_bdd_nodes() const { return bddmma_nr_bdd_nodes(h_); }
     size_t nr_hops() const { return bddmma_nr_hops(h_); }
     size_t nr_bdds(const size_t var) const
@@ -505,6 +507,31 @@ class bdd_hip_batch {
     {
         check(bddmma_learned_iterations_history_batch(b_, dev_dist_weights, dev_omega_vec, omega, num_itr, dev_sol_avg, dev_lb_first_diff_avg,
                                                       dev_lb_second_diff_avg, compute_history_for_itr, history_avg_beta, 1));
+    }
+    // ... and with the stopping rule of the per-solver learned_iterations (improvement_slope > 0) inside the members' workgroups: returns the
+    // members' counts of iterations run.  The history arrays may be null / empty with compute_history_for_itr == 0.  Every member must be
+    // fused_small_stop() (include/bdd_mma.h: bddmma_learned_iterations_stop_batch).
+    std::vector<size_t> learned_iterations_stopping(const std::vector<REAL>& dist_weights, const size_t num_itr, const REAL omega, const double improvement_slope,
+                                                    const std::vector<REAL>* omega_vec = nullptr, const size_t compute_history_for_itr = 0,
+                                                    const REAL history_avg_beta = 0.9, std::vector<REAL>* sol_avg = nullptr,
+                                                    std::vector<REAL>* lb_first_diff_avg = nullptr, std::vector<REAL>* lb_second_diff_avg = nullptr)
+    {
+        std::vector<uint64_t> done(size());
+        check(bddmma_learned_iterations_stop_batch(b_, dist_weights.data(), omega_vec ? omega_vec->data() : nullptr, omega, num_itr, improvement_slope,
+                                                   sol_avg ? sol_avg->data() : nullptr, lb_first_diff_avg ? lb_first_diff_avg->data() : nullptr,
+                                                   lb_second_diff_avg ? lb_second_diff_avg->data() : nullptr, compute_history_for_itr, history_avg_beta, 0,
+                                                   done.data()));
+        return std::vector<size_t>(done.begin(), done.end());
+    }
+    std::vector<size_t> learned_iterations_stopping_dev(const REAL* dev_dist_weights, const size_t num_itr, const REAL omega, const double improvement_slope,
+                                                        const REAL* dev_omega_vec = nullptr, const size_t compute_history_for_itr = 0,
+                                                        const REAL history_avg_beta = 0.9, REAL* dev_sol_avg = nullptr, REAL* dev_lb_first_diff_avg = nullptr,
+                                                        REAL* dev_lb_second_diff_avg = nullptr)
+    {
+        std::vector<uint64_t> done(size());
+        check(bddmma_learned_iterations_stop_batch(b_, dev_dist_weights, dev_omega_vec, omega, num_itr, improvement_slope, dev_sol_avg, dev_lb_first_diff_avg,
+                                                   dev_lb_second_diff_avg, compute_history_for_itr, history_avg_beta, 1, done.data()));
+        return std::vector<size_t>(done.begin(), done.end());
     }
     // grad_iterations(...) of every member with its part of every device array (bdd_hip_parallel_mma::grad_iterations; the members' arrays
     // one behind the other), one workgroup per member: dev_grad_omega has size() entries, the concatenated per-layer array with

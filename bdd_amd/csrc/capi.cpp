@@ -157,6 +157,7 @@ int bddmma_solve_sweep_kind(const bddmma_solver* s) { return s && s->impl ? s->i
 int bddmma_fused_small(const bddmma_solver* s) { return s && s->impl ? (s->impl->fused_small ? 1 : 0) : -1; }
 int bddmma_fused_small_learned(const bddmma_solver* s) { return s && s->impl ? (s->impl->fused_small_learned ? 1 : 0) : -1; }
 int bddmma_fused_small_history(const bddmma_solver* s) { return s && s->impl ? (s->impl->fused_small_history ? 1 : 0) : -1; }
+int bddmma_fused_small_stop(const bddmma_solver* s) { return s && s->impl ? (s->impl->fused_small_stop ? 1 : 0) : -1; }
 int bddmma_nontemporal_loads(const bddmma_solver* s) { return s && s->impl ? (s->impl->nt_loads ? 1 : 0) : -1; }
 int bddmma_potentials_on_chip(const bddmma_solver* s) { return s && s->impl ? (s->impl->pot_on_chip ? 1 : 0) : -1; }
 int bddmma_onchip_hops(const bddmma_solver* s) { return s && s->impl ? s->impl->onchip_hops : -1; }
@@ -456,6 +457,15 @@ int bddmma_learned_iterations_history_batch(bddmma_batch* b, const void* dist_we
     return guarded_batch(b, [&](BatchBase* i) {
         return i->learned_iterations_history(dist_weights, omega_vec, omega, num_itr, sol_avg, lb_first_diff_avg, lb_second_diff_avg, compute_history_for_itr,
                                              history_avg_beta, on_device);
+    });
+}
+int bddmma_learned_iterations_stop_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec, double omega, uint64_t num_itr,
+                                         double improvement_slope, void* sol_avg, void* lb_first_diff_avg, void* lb_second_diff_avg,
+                                         uint64_t compute_history_for_itr, double history_avg_beta, int on_device, uint64_t* iterations_done)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        return i->learned_iterations_stop(dist_weights, omega_vec, omega, num_itr, improvement_slope, sol_avg, lb_first_diff_avg, lb_second_diff_avg,
+                                          compute_history_for_itr, history_avg_beta, on_device, iterations_done);
     });
 }
 int bddmma_grad_learned_iterations_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec, double omega, void* grad_lo, void* grad_hi,

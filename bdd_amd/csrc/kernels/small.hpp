@@ -1,5 +1,6 @@
 // kernels/small.hpp — instances that fit ONE workgroup: whole MMA iterations inside one launch (k_iterate_small, k_iterate_small_batch),
-// and whole learned iterations (k_learned_small, k_learned_small_batch; with their history step: k_learned_small_hist_batch, kernels/smallhist.hpp).
+// and whole learned iterations (k_learned_small, k_learned_small_batch; with their history step: k_learned_small_hist_batch, kernels/smallhist.hpp;
+// with the stopping rule on the bound's slope: k_learned_small_stop_batch, k_learned_small_hist_stop_batch, kernels/smallstop.hpp).
 // Part of kernels.hpp (include that, not this file: the parts build on each other in its order).
 #pragma once
 
@@ -163,6 +164,48 @@ __device__ __forceinline__ REAL small_ema(REAL avg, REAL cur, REAL beta)
     }
 }
 
+// STOP (k_learned_small_stop_batch, k_learned_small_hist_stop_batch, kernels/smallstop.hpp: bddmma_learned_iterations_stop_batch): the stopping
+// rule of SolverT::learned_iterations (solver_impl.hpp; bdd_cuda_learned_mma.cu:185-270) inside the launch.  A member's stop block lives in
+// global memory and is reached through its item: the slope, the call's two counts, the bound on entry and the set-once initial change (not
+// finite: unset) are the call's; the rest is in-out across the launches of one call.  A launch whose block says `done` returns before it touches anything, so the
+// member's state stays what its own last launch left.
+struct SmallStopBlock {
+    double slope, lb_initial, initial_change;
+    double lb_prev, lb_post;
+    uint64_t num_itr, cfi;     // the call's num_itr and compute_history_for_itr
+    uint64_t tracked, iters;   // history steps made / iterations run by the call so far
+    uint32_t converged, done;
+};
+// (A member that is not done has run every iteration of the call's earlier launches: `iters` is also the call's index of the launch's
+// first iteration, so a launch takes nothing but the block.)
+// The rule's working values between the iterations of a launch: static LDS, written and read by lane 0 of wave 0 only — but for `stop`
+// (read by everyone behind the barrier that follows the test) and for trk / step, which the test of iteration i writes for iteration i + 1
+// into the slot of that iteration's parity: everyone reads the slot of iteration i behind its backward sweep's barrier, possibly while
+// wave 0 is already writing the other one.
+struct SmallStopWork {
+    double lb_post, initial, slope;
+    uint64_t num_itr, cfi, tracked, iters;
+    uint32_t converged, stop;
+    uint32_t trk[2], step[2];   // is the iteration tracked (bdd_cuda_learned_mma.cu:211) / the history steps of the call before it, saturated at 3
+};
+constexpr uint32_t SMALL_STOP_LDS = 96;
+static_assert(sizeof(SmallStopWork) <= SMALL_STOP_LDS, "the admission rule (SolverT::small_stop_ok) reserves SMALL_STOP_LDS bytes");
+// The instantiations that exist: every one but the history form of 16 waves in double with the records in L2, which sits at 128 VGPRs without
+// the rule and would spill one register into scratch with it.  A member that would need it is not admitted
+// (bddmma_fused_small_stop is 0), with or without a history in the call.
+template <typename REAL>
+constexpr bool small_stop_built(int nw, bool rl) { return !(sizeof(REAL) == 8 && nw == 16 && !rl); }
+template <bool STOP>
+__device__ __forceinline__ SmallStopWork* small_stop_work()
+{
+    if constexpr (STOP) {
+        __shared__ SmallStopWork w;
+        return &w;
+    } else {
+        return nullptr;
+    }
+}
+
 // The workgroup's work, shared by k_iterate_small (one instance per launch) and k_iterate_small_batch (one instance per workgroup).
 // NW waves, pack p on wave p (n_packs <= NW); RL: the packs' records live in LDS too (1 KiB per hop), else they stream from L2 eight hops ahead
 // LEARNED (k_learned_small, k_learned_small_batch): n learned iterations,
@@ -173,13 +216,18 @@ __device__ __forceinline__ REAL small_ema(REAL avg, REAL cur, REAL beta)
 // omega from its layer's slot.  The plain exchange behind the last backward sweep and the plain epilogue leave what the four-launch path
 // leaves: the last backward pass's differences deferred, delta their isotropic exchange, the bound's partial sums.  No run_solver (run.ctl
 // is null there), so no early return at all.
-template <typename REAL, int NW, bool RL, bool LEARNED = false, bool RECORD = false, bool HISTORY = false>
+// STOP: the stopping rule behind every iteration (SmallStopBlock above): the bound's partial sums are taken every iteration, wave 0 reduces
+// them in k_lb_reduce's shape and its lane 0 applies the rule in double; the iteration that stops leaves through the exit exchange and the
+// epilogue, as the per-member loop does.  With HISTORY the tracked window is the rule's: hs->hist_from / tracked are not read.
+template <typename REAL, int NW, bool RL, bool LEARNED = false, bool RECORD = false, bool HISTORY = false, bool STOP = false>
 __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<REAL>& d, const PackDev& pk, REAL omega, uint32_t n_iters, const RunStep& run,
-                                              const SmallLearn<REAL>* ln = nullptr, const SmallRecord<REAL>* rec = nullptr, const SmallHist<REAL>* hs = nullptr)
+                                              const SmallLearn<REAL>* ln = nullptr, const SmallRecord<REAL>* rec = nullptr, const SmallHist<REAL>* hs = nullptr,
+                                              SmallStopBlock* const* stp = nullptr)
 {
     static_assert(!RECORD || LEARNED, "only the learned iterations are recorded");
     static_assert(!HISTORY || LEARNED, "only the learned iterations have a history");
     static_assert(!(HISTORY && RECORD), "the history form is not recorded");
+    static_assert(!STOP || (LEARNED && !RECORD), "the stopping rule is the learned iterations', and its form is not recorded");
     constexpr uint32_t S = sizeof(REAL);
     constexpr uint32_t NT = 64 * NW;
     using P2 = typename Pair<REAL>::type;
@@ -190,6 +238,11 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
     // run_solver: launches queued behind the iteration that met a criterion do nothing (DevPtrs::stop / run_iter = this launch's first iteration)
     if constexpr (!LEARNED)
         if (d.stop != nullptr && *d.stop <= d.run_iter) return;
+    // (STOP: stp is the address of the block's address in the member's item — the block is reached by scalar loads where it is used, so that
+    // nothing of it lives in registers through the solve sweeps)
+    if constexpr (STOP)
+        if ((*stp)->done != 0u) return;   // (uniform) stopped by an earlier launch of the call
+    SmallStopWork* const ws = small_stop_work<STOP>();
     const REAL INF = inf_v<REAL>();
     const uint32_t region = small_region_bytes(S, sm.ns, sm.nl), dstride = small_stage_stride(sm.nl);
     const uint32_t ll_dummy = sm.nl * 2u * S;   // the dummy pair of a pack's {lo, hi} array and of its staging area
@@ -262,6 +315,33 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
     RunCtl c{};
     if constexpr (!LEARNED)
         if (run.ctl != nullptr && tid == 0) c = *run.ctl;
+    if constexpr (STOP) {
+        if (wave == 0) {
+            // the call's first launch: the bound on entry from the partial sums the member's last backward sweep left (the caller has made them
+            // valid), in k_lb_reduce's shape — SolverT::learned_iterations' lower_bound() in front of its loop
+            SmallStopBlock* const b = *stp;
+            const bool first = b->iters == 0;   // (uniform)
+            double t = 0.0;
+            if (first) {
+                t = (uint32_t)lane < sm.n_packs ? d.lb_partial[pk.lb_base + (uint32_t)lane] : 0.0;
+                for (int off2 = 32; off2 > 0; off2 >>= 1) t += __shfl_down(t, off2);
+            }
+            if (lane == 0) {
+                if (first) b->lb_initial = t;
+                ws->lb_post = first ? t : b->lb_post;
+                ws->initial = b->initial_change;
+                ws->slope = b->slope;
+                ws->num_itr = b->num_itr;
+                ws->cfi = b->cfi;
+                ws->tracked = b->tracked;
+                ws->iters = b->iters;
+                ws->converged = b->converged;
+                ws->stop = 0u;
+                ws->trk[0] = (b->cfi > 0 && (b->cfi >= b->num_itr - b->iters || b->converged != 0u)) ? 1u : 0u;
+                ws->step[0] = (uint32_t)(b->tracked < 3 ? b->tracked : 3);
+            }
+        }
+    }
     __syncthreads();
 
     // The exchange (compute_delta + normalize_delta + the broadcast to the variable's layers, bdd_cuda_parallel_mma.cu:358-430,191-197): a
@@ -637,7 +717,7 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
             }
 #undef SMALL_HOP
             // lower bound contribution of this pack: sum of root costs-from-terminal (bdd_cuda_base.cu:1243-1251); every node of the first hop is a root
-            if ((!LEARNED && run.ctl != nullptr) || it + 1 == n_iters) {   // (uniform) the bound: run_solver's tests, or the state the launch leaves
+            if ((!LEARNED && run.ctl != nullptr) || STOP || it + 1 == n_iters) {   // (uniform) the bound: run_solver's tests, the stopping rule, or the state the launch leaves
             const u4v rroot = RL ? lds_ld<u4v>(dyn_lds, rl + (uint32_t)lane * 16u) : __builtin_amdgcn_raw_buffer_load_b128(rr, (uint32_t)lane * 16u, rbase * 16u, 0);
             double lb = (RL ? (rroot[2] & 0xFFFFu) != ll_dummy : rroot[3] != RES2_PAD) ? (double)lds_ld<REAL>(dyn_lds, wb + (rroot[2] >> 16)) : 0.0;
             for (int off2 = 32; off2 > 0; off2 >>= 1) lb += __shfl_down(lb, off2);
@@ -645,11 +725,55 @@ __device__ __forceinline__ void small_iterate(const SmallDev& sm, const DevPtrs<
             }
         }
         __syncthreads();
-        if constexpr (HISTORY) {
+        if constexpr (HISTORY && STOP) {
+            if (__builtin_amdgcn_readfirstlane(ws->trk[it & 1u]) != 0u) {   // (uniform) tracked: the tail window, or converged by an earlier iteration's test
+                history(__builtin_amdgcn_readfirstlane(ws->step[it & 1u]));
+                __syncthreads();   // the next exchange writes the staging pairs of every pack
+            }
+        } else if constexpr (HISTORY) {
             if (it >= hs->hist_from) {   // (uniform)
                 history(hs->tracked + (it - hs->hist_from));
                 __syncthreads();   // the next exchange writes the staging pairs of every pack
             }
+        }
+        if constexpr (STOP) {
+            if (wave == 0) {
+                // the bound of the iteration in the shape of k_lb_reduce, then SolverT::learned_iterations' lines behind its history step
+                double t = (uint32_t)lane < sm.n_packs ? lbp[lane] : 0.0;
+                for (int off2 = 32; off2 > 0; off2 >>= 1) t += __shfl_down(t, off2);
+                if (lane == 0) {
+                    const uint64_t g = ws->iters, num_itr = ws->num_itr, cfi = ws->cfi;
+                    const uint64_t tracked = ws->tracked + ws->trk[it & 1u];
+                    const double lb_prev = ws->lb_post;
+                    double initial = ws->initial;
+                    if (g == 0 && !(__builtin_fabs(initial) < __builtin_huge_val())) initial = __builtin_fabs(lb_prev - t);   // set_initial_lb_change: once per solver (lb_prev is the bound on entry)
+                    uint32_t conv = ws->converged;
+                    if (conv == 0u && __builtin_fabs(lb_prev - t) < ws->slope * initial) conv = 1u;
+                    const bool stop = conv != 0u && tracked == cfi;
+                    ws->lb_post = t;
+                    ws->initial = initial;
+                    ws->tracked = tracked;
+                    ws->iters = g + 1;
+                    ws->converged = conv;
+                    ws->stop = stop ? 1u : 0u;
+                    ws->trk[(it + 1u) & 1u] = (cfi > 0 && (cfi >= num_itr - (g + 1) || conv != 0u)) ? 1u : 0u;
+                    ws->step[(it + 1u) & 1u] = (uint32_t)(tracked < 3 ? tracked : 3);
+                    if (stop || it + 1 == n_iters) {   // the block for the call's next launch, or for the host
+                        SmallStopBlock* const b = *stp;
+                        b->lb_prev = lb_prev;
+                        b->lb_post = t;
+                        b->initial_change = initial;
+                        b->tracked = tracked;
+                        b->iters = g + 1;
+                        b->converged = conv;
+                        b->done = (stop || g + 1 == num_itr) ? 1u : 0u;
+                    }
+                }
+            }
+            // A barrier of its own: the next use of the decision is the choice between the next iteration's weighted exchange and the exit
+            // exchange, and the former overwrites the differences the latter reads — it cannot wait for that iteration's first barrier.
+            __syncthreads();
+            if (__builtin_amdgcn_readfirstlane(ws->stop) != 0u) { ++it; break; }   // (uniform) the iteration that stopped is complete
         }
         if constexpr (!LEARNED) {
 #ifdef BDDMMA_EXP_SMALL_SKIP

@@ -82,6 +82,7 @@ struct SolverBase {
     bool fused_small = false;   // whole iterations in one launch (diagnostics: bddmma_fused_small)
     bool fused_small_learned = false;   // ... and whole learned iterations (bddmma_fused_small_learned)
     bool fused_small_history = false;   // ... and their history step, in a batch (bddmma_fused_small_history)
+    bool fused_small_stop = false;      // ... and the stopping rule on the bound's slope, in a batch (bddmma_fused_small_stop)
     bool nt_loads = false;      // the solve sweeps' non-temporal instantiation (diagnostics: bddmma_nontemporal_loads)
     bool pot_on_chip = false;   // iteration()'s solve sweeps rebuild F and T on chip (diagnostics: bddmma_potentials_on_chip)
     int onchip_hops = 0;        // ... the hop capacity of the kernels that do: 0, 10, 12 or 16 (diagnostics: bddmma_onchip_hops)
@@ -187,6 +188,11 @@ struct BatchBase {
     virtual int learned_iterations_history(const void* dist_weights, const void* omega_vec, double omega, uint64_t num_itr, void* sol_avg,
                                            void* lb_first_diff_avg, void* lb_second_diff_avg, uint64_t compute_history_for_itr, double history_avg_beta,
                                            int on_device) = 0;
+    // SolverBase::learned_iterations(w_i, num_itr, omega, improvement_slope, history) of every member with the member's count of iterations
+    // run in iterations_done[i]: the stopping rule inside the member's workgroup (include/bdd_mma.h: bddmma_learned_iterations_stop_batch)
+    virtual int learned_iterations_stop(const void* dist_weights, const void* omega_vec, double omega, uint64_t num_itr, double improvement_slope,
+                                        void* sol_avg, void* lb_first_diff_avg, void* lb_second_diff_avg, uint64_t compute_history_for_itr,
+                                        double history_avg_beta, int on_device, uint64_t* iterations_done) = 0;
     // SolverBase::grad_learned_iterations of every member with its part of every array, one workgroup per member in one launch
     // (include/bdd_mma.h: bddmma_grad_learned_iterations_batch)
     virtual int grad_learned_iterations(const void* dist_weights, const void* omega_vec, double omega, void* grad_lo, void* grad_hi, void* grad_mm,

@@ -14,6 +14,7 @@
 #include "kernels/batchround.hpp"
 #include "kernels/batchsol.hpp"
 #include "kernels/smallhist.hpp"
+#include "kernels/smallstop.hpp"
 
 namespace bddmma {
 
@@ -48,7 +49,7 @@ struct BatchT final : BatchBase {
         for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1, ev_order})
             if (e) (void)hipEventDestroy(e);
         if (d_items) (void)hipFree(d_items);
-        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad, (void*)d_bm_items, (void*)d_bm_stage, (void*)d_bm_bad, (void*)d_bsm_items, (void*)d_bsm_stage, (void*)d_br_items, (void*)d_br_words, (void*)d_bp_items, (void*)d_bp_stage, (void*)d_bp_bad})
+        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_st_items, (void*)d_st_blocks, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad, (void*)d_bm_items, (void*)d_bm_stage, (void*)d_bm_bad, (void*)d_bsm_items, (void*)d_bsm_stage, (void*)d_br_items, (void*)d_br_words, (void*)d_bp_items, (void*)d_bp_stage, (void*)d_bp_bad})
             if (q) (void)hipFree(q);
         if (d_ctl) (void)hipFree(d_ctl);
         if (h_ctl) (void)hipHostFree(h_ctl);
@@ -287,6 +288,8 @@ struct BatchT final : BatchBase {
     REAL* d_hs_stage = nullptr;
     uint64_t hs_bdds = 0;          // BDDs of all members
     bool hs_ready = false;
+    std::vector<SmallHistItem<REAL>> hs_items;   // what d_hs_items was filled with, and the member of each (learned_iterations_stop builds on both)
+    std::vector<uint32_t> hs_ord;
 
     int hs_prepare()
     {
@@ -325,6 +328,8 @@ struct BatchT final : BatchBase {
         HIPCHK(hipMemcpy(d_hs_items, items.data(), n * sizeof(SmallHistItem<REAL>), hipMemcpyHostToDevice));
         hs_fn = std::move(fns);
         hs_bdds = total_b;
+        hs_items = std::move(items);
+        hs_ord = std::move(ord);
         return BDDMMA_OK;
     }
     int launch_learned_hist(REAL omega, uint32_t n_iters, bool ov, uint32_t hist_from, uint32_t tracked)
@@ -342,9 +347,10 @@ struct BatchT final : BatchBase {
     {
         return learned_iterations_history(w, omega_vec, omega, num_itr, nullptr, nullptr, nullptr, 0, 0.0, on_dev);
     }
-    // cfi == 0: the call without a history, launch for launch what it was
-    int learned_iterations_history(const void* w, const void* omega_vec, double omega, uint64_t num_itr, void* sol_avg, void* lb1_avg, void* lb2_avg, uint64_t cfi,
-                                   double beta_d, int on_dev) override
+    // What every learned call of a batch starts with: the refusals — each before any member is touched; `stop`: the stopping form's admission
+    // on top — the preparation on first use, and the one kernel that checks every member's values and moves them into place, with the
+    // host's wait for its verdict.  The batch stream is ordered behind the members' on return.
+    int learned_begin(const void* w, const void* omega_vec, void* sol_avg, void* lb1_avg, void* lb2_avg, uint64_t cfi, int on_dev, bool stop)
     {
         int rc;
         const uint32_t n = (uint32_t)m.size();
@@ -355,7 +361,10 @@ struct BatchT final : BatchBase {
         }
         if ((rc = check_state())) return rc;
         for (uint32_t i = 0; i < n; ++i)
-            if (cfi > 0 && !m[i]->small_hist_ok) {
+            if (stop && !m[i]->small_stop_ok) {
+                err = "batch member " + std::to_string(i) + ": learned iterations with the stopping rule do not fit one workgroup (bddmma_fused_small_stop is 0)";
+                return BDDMMA_ERR_UNSUPPORTED;
+            } else if (cfi > 0 && !m[i]->small_hist_ok) {
                 err = "batch member " + std::to_string(i) + ": learned iterations with their history do not fit one workgroup (bddmma_fused_small_history is 0)";
                 return BDDMMA_ERR_UNSUPPORTED;
             } else if (!m[i]->small_ln_ok) {
@@ -367,9 +376,13 @@ struct BatchT final : BatchBase {
             if ((rc = ln_prepare())) return rc;
             ln_ready = true;
         }
-        if (cfi > 0 && !hs_ready) {
+        if ((cfi > 0 || stop) && !hs_ready) {
             if ((rc = hs_prepare())) return rc;
             hs_ready = true;
+        }
+        if (stop && !st_ready) {
+            if ((rc = st_prepare())) return rc;
+            st_ready = true;
         }
         const bool ov = omega_vec != nullptr;
         // host inputs: checked here, before anything is copied
@@ -416,6 +429,16 @@ struct BatchT final : BatchBase {
             (void)join_out();
             return BDDMMA_ERR_INVALID_ARGUMENT;
         }
+        return BDDMMA_OK;
+    }
+    // cfi == 0: the call without a history, launch for launch what it was
+    int learned_iterations_history(const void* w, const void* omega_vec, double omega, uint64_t num_itr, void* sol_avg, void* lb1_avg, void* lb2_avg, uint64_t cfi,
+                                   double beta_d, int on_dev) override
+    {
+        int rc;
+        const uint32_t n = (uint32_t)m.size();
+        if ((rc = learned_begin(w, omega_vec, sol_avg, lb1_avg, lb2_avg, cfi, on_dev, false))) return rc;
+        const bool ov = omega_vec != nullptr;
         if (num_itr == 0) return join_out();
         // set_initial_lb_change, once per solver: the bounds before and after the first iteration, enqueued on the member's stream and fetched
         // at the end — so the first iteration is a launch of its own when a member still wants it (n then m learned iterations are n + m)
@@ -487,6 +510,123 @@ struct BatchT final : BatchBase {
                 if ((rc = m[i]->lower_bound_fetch(0, &a)) || (rc = m[i]->lower_bound_fetch(1, &b))) { err = m[i]->err; return rc; }
                 m[i]->initial_lb_change = std::abs(a - b);
             }
+        return BDDMMA_OK;
+    }
+
+    // ---- ... that stop on the bound's slope (kernels/smallstop.hpp: k_learned_small_stop_batch, k_learned_small_hist_stop_batch; the kernels
+    // compile in solver_ss_f32.hip / _f64.hip).  Items in the history items' order, each with the address of its member's stop block
+    // (kernels/small.hpp: SmallStopBlock); st_host is the blocks' host copy, in the same order: written before a call's first launch, read
+    // back behind its last.
+    static constexpr uint32_t STOP_CHUNK = 32;   // iterations per launch: a member that has stopped idles through the rest of its launch's
+                                                 // siblings only, and a launch queued behind its stop returns at its first instruction
+    using StFn = typename S::SmallStopFn;
+    std::vector<StFn> st_fn, st_hist_fn;   // per learned group: without / with the history step
+    SmallStopItem<REAL>* d_st_items = nullptr;
+    SmallStopBlock* d_st_blocks = nullptr;
+    std::vector<SmallStopBlock> st_host;
+    bool st_ready = false;
+
+    int st_prepare()
+    {
+        const uint32_t n = (uint32_t)m.size();
+        if (!d_st_items) HIPCHK(hipMalloc((void**)&d_st_items, n * sizeof(SmallStopItem<REAL>)));
+        if (!d_st_blocks) HIPCHK(hipMalloc((void**)&d_st_blocks, n * sizeof(SmallStopBlock)));
+        std::vector<SmallStopItem<REAL>> items(n);
+        for (uint32_t j = 0; j < n; ++j) items[j] = SmallStopItem<REAL>{hs_items[j], d_st_blocks + j};
+        std::vector<StFn> fns, hfns;
+        for (const LnGroup& g : ln_groups) {
+            const S* s = m[hs_ord[g.first]];
+            fns.push_back(S::ss_batch_fn(s->small_nw, s->small_ln_rl, false));
+            hfns.push_back(S::ss_batch_fn(s->small_nw, s->small_ln_rl, true));
+            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(fns.back()), g.lds)) return rc;
+            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(hfns.back()), g.lds)) return rc;
+        }
+        HIPCHK(hipMemcpy(d_st_items, items.data(), n * sizeof(SmallStopItem<REAL>), hipMemcpyHostToDevice));
+        st_fn = std::move(fns);
+        st_hist_fn = std::move(hfns);
+        st_host.assign(n, SmallStopBlock{});
+        return BDDMMA_OK;
+    }
+    // the next n_iters iterations of the call, for the members that have not stopped
+    int launch_learned_stop(REAL omega, uint32_t n_iters, bool ov, bool hist)
+    {
+        for (size_t k = 0; k < ln_groups.size(); ++k) {
+            const LnGroup& g = ln_groups[k];
+            hipLaunchKernelGGL(hist ? st_hist_fn[k] : st_fn[k], dim3(g.count), dim3(g.threads), g.lds, stream, (const SmallStopItem<REAL>*)(d_st_items + g.first), omega,
+                               n_iters, ov ? 1u : 0u);
+            HIPCHK(hipGetLastError());
+        }
+        for (S* s : m) s->small_launched();
+        return BDDMMA_OK;
+    }
+    // The per-member call with improvement_slope > 0 for every member: the rule runs in the member's workgroup behind every iteration, the
+    // chunks of STOP_CHUNK iterations are queued without waiting, and the host waits once, for the stop blocks (and any host outputs).
+    int learned_iterations_stop(const void* w, const void* omega_vec, double omega, uint64_t num_itr, double slope, void* sol_avg, void* lb1_avg, void* lb2_avg,
+                                uint64_t cfi, double beta_d, int on_dev, uint64_t* done) override
+    {
+        int rc;
+        const uint32_t n = (uint32_t)m.size();
+        if (!done) { err = "batch learned_iterations: iterations_done is null"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if (!(slope > 0)) {   // never stops (NaN included): the call with a fixed window
+            if ((rc = learned_iterations_history(w, omega_vec, omega, num_itr, sol_avg, lb1_avg, lb2_avg, cfi, beta_d, on_dev))) return rc;
+            for (uint32_t i = 0; i < n; ++i) done[i] = num_itr;
+            return BDDMMA_OK;
+        }
+        if ((rc = learned_begin(w, omega_vec, sol_avg, lb1_avg, lb2_avg, cfi, on_dev, true))) return rc;
+        const bool ov = omega_vec != nullptr;
+        for (uint32_t i = 0; i < n; ++i) done[i] = 0;
+        if (num_itr == 0) return join_out();
+        const char* const me = "batch learned_iterations: ";
+        // the members' costs-to-terminal and the partial sums of their bounds valid, the batch stream behind them; then the blocks of this call
+        if ((rc = join_in())) { (void)join_out(); return rc; }
+        for (uint32_t j = 0; j < n; ++j) {
+            SmallStopBlock b{};
+            b.slope = slope;
+            b.num_itr = num_itr;
+            b.cfi = cfi;
+            b.initial_change = m[hs_ord[j]]->initial_lb_change;
+            st_host[j] = b;
+        }
+        hipError_t e = hipMemcpyAsync(d_st_blocks, st_host.data(), n * sizeof(SmallStopBlock), hipMemcpyHostToDevice, stream);
+        // The history's outputs as in learned_iterations_history: host content to the device first — an entry the history does not reach
+        // keeps it — and back behind the last launch.
+        const uint64_t hist_values = cfi > 0 ? ln_total + 2 * hs_bdds : 0;
+        REAL *o_sol = (REAL*)sol_avg, *o_lb1 = (REAL*)lb1_avg, *o_lb2 = (REAL*)lb2_avg;
+        if (cfi > 0 && e == hipSuccess) {
+            if (!on_dev) {
+                o_sol = d_hs_stage; o_lb1 = d_hs_stage + ln_total; o_lb2 = o_lb1 + hs_bdds;
+                e = hipMemcpyAsync(o_sol, sol_avg, ln_total * sizeof(REAL), hipMemcpyHostToDevice, stream);
+                if (e == hipSuccess) e = hipMemcpyAsync(o_lb1, lb1_avg, hs_bdds * sizeof(REAL), hipMemcpyHostToDevice, stream);
+                if (e == hipSuccess) e = hipMemcpyAsync(o_lb2, lb2_avg, hs_bdds * sizeof(REAL), hipMemcpyHostToDevice, stream);
+            }
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL((k_stop_items_call<REAL>), dim3(cdiv(n, 256)), dim3(256), 0, stream, d_st_items, n, o_sol, o_lb1, o_lb2, (REAL)beta_d);
+                e = hipGetLastError();
+            }
+        }
+        if (e != hipSuccess) { err = std::string(me) + hipGetErrorString(e); (void)join_out(); return BDDMMA_ERR_DEVICE; }
+        uint64_t g0 = 0;
+        while (g0 < num_itr && !rc) {
+            const uint32_t chunk = (uint32_t)std::min<uint64_t>(num_itr - g0, STOP_CHUNK);
+            rc = launch_learned_stop((REAL)omega, chunk, ov, cfi > 0);
+            g0 += chunk;
+        }
+        const int rc2 = join_out();   // also behind a failed launch: what was queued stays ordered
+        if (rc || rc2) return rc ? rc : rc2;
+        // behind the last launch on the batch stream: the one synchronisation, for the stop blocks and any host outputs
+        e = hipMemcpyAsync(st_host.data(), d_st_blocks, n * sizeof(SmallStopBlock), hipMemcpyDeviceToHost, stream);
+        if (hist_values && !on_dev) {
+            if (e == hipSuccess) e = hipMemcpyAsync(sol_avg, o_sol, ln_total * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(lb1_avg, o_lb1, hs_bdds * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(lb2_avg, o_lb2, hs_bdds * sizeof(REAL), hipMemcpyDeviceToHost, stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) { err = std::string(me) + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        for (uint32_t j = 0; j < n; ++j) {
+            S* s = m[hs_ord[j]];
+            done[hs_ord[j]] = st_host[j].iters;
+            if (!std::isfinite(s->initial_lb_change)) s->initial_lb_change = st_host[j].initial_change;   // set_initial_lb_change: once per solver
+        }
         return BDDMMA_OK;
     }
 

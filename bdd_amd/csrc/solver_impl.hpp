@@ -77,6 +77,7 @@ struct PullSweep {
 template <typename REAL> struct GradSmallItem;   // kernels/gradsmall.hpp
 template <typename REAL> struct GradSmallIO;
 template <typename REAL> struct SmallHistItem;   // kernels/smallhist.hpp
+template <typename REAL> struct SmallStopItem;   // kernels/smallstop.hpp
 template <typename REAL>
 struct SolverT final : SolverBase {
     // device buffers
@@ -198,6 +199,7 @@ struct SolverT final : SolverBase {
     // budget) + omega per layer.  The kernels live in solver_sl_f32.hip / _f64.hip: sl_prepare() resolves this
     // solver's and raises its dynamic-LDS limit on the first call that launches it.
     bool small_ln_ok = false, small_ln_rl = false, sl_ready = false;
+    bool small_stop_ok = false;   // ... and the stopping rule (kernels/small.hpp: STOP): SMALL_STOP_LDS bytes of static LDS beside the learned form's
     bool small_hist_ok = false;   // the learned form with its history step (kernels/small.hpp: HISTORY); no LDS beyond the learned form's
     uint32_t small_ln_lds = 0;
     SmallDev small_ln{};
@@ -701,6 +703,10 @@ struct SolverT final : SolverBase {
                     // the .y halves of the staging pairs, so it needs no LDS of its own; a thread per BDD holds the bounds.
                     small_hist_ok = small_hist_fits((uint64_t)n_bdds, (uint32_t)small_nw);
                     fused_small_history = small_hist_ok;
+                    // The stopping rule keeps its working values in static LDS beside the dynamic area; a call may ask for a history, so
+                    // the history form must be there too — and compiled without scratch (small_stop_built).
+                    small_stop_ok = small_hist_ok && lbytes + SMALL_STOP_LDS + 512 <= lds_cu && small_stop_built<REAL>(small_nw, small_ln_rl);
+                    fused_small_stop = small_stop_ok;
                 }
             }
         }
@@ -987,6 +993,10 @@ struct SolverT final : SolverBase {
     // solver_sh_f32.hip / _f64.hip.
     using SmallHistFn = void (*)(const SmallHistItem<REAL>*, REAL, uint32_t, uint32_t, uint32_t, uint32_t);
     static SmallHistFn sh_batch_fn(int nw, bool rl);
+    // The learned iterations that stop on the bound's slope, for a batch (kernels/smallstop.hpp; BatchT::learned_iterations_stop): the kernels
+    // live in solver_ss_f32.hip / _f64.hip.
+    using SmallStopFn = void (*)(const SmallStopItem<REAL>*, REAL, uint32_t, uint32_t);
+    static SmallStopFn ss_batch_fn(int nw, bool rl, bool hist);
     bool ov_ready = false;
     // One sweep: the wide and the narrow packs (one launch where `mixed`; forward only with mixed_fwd), then the huge ones.
     int launch_sweep(bool bwd, const Sweep& s, const REAL* delta_lay, REAL omega, int kclass, bool ov = false)

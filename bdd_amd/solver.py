@@ -99,6 +99,10 @@ class bdd_hip_parallel_mma:
         """True when bdd_hip_batch.learned_iterations_history can run this solver's history steps (compute_history_for_itr > 0) inside
         its workgroup as well"""
         return bool(self._L.bddmma_fused_small_history(self._h))
+    def fused_small_stop(self) -> bool:
+        """True when a bdd_hip_batch runs this solver's stopping rule (improvement_slope > 0) inside its workgroup too
+        (bddmma_fused_small_stop; bdd_hip_batch.learned_iterations_stopping)."""
+        return bool(self._L.bddmma_fused_small_stop(self._h))
 
     def nontemporal_loads(self) -> bool:
         """the solve sweeps run in the instantiation that loads potentials and staging tables non-temporally (footprint beyond the caches' reach)"""
@@ -669,6 +673,12 @@ class bdd_hip_batch:
         if int(compute_history_for_itr) == 0:
             self._check(self._L.bddmma_learned_iterations_batch(self._h, w, ov, float(omega), int(num_itr), w_dev), self._h)
             return
+        outs = self._history_outs(n, w_dev, sol_avg, lb_first_diff_avg, lb_second_diff_avg)
+        self._check(self._L.bddmma_learned_iterations_history_batch(self._h, w, ov, float(omega), int(num_itr), *outs, int(compute_history_for_itr),
+                                                                     float(history_avg_beta), w_dev), self._h)
+
+    def _history_outs(self, n, w_dev, sol_avg, lb_first_diff_avg, lb_second_diff_avg):
+        s0 = self.solvers[0]
         nb = sum(s.nr_bdds() for s in self.solvers)
         outs = []
         for x, k, what in ((sol_avg, n, "sol_avg"), (lb_first_diff_avg, nb, "lb_first_diff_avg"), (lb_second_diff_avg, nb, "lb_second_diff_avg")):
@@ -680,8 +690,30 @@ class bdd_hip_batch:
                 raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: the arrays of a batch call must all be on the host or all "
                                        "on the device")
             outs.append(p)
-        self._check(self._L.bddmma_learned_iterations_history_batch(self._h, w, ov, float(omega), int(num_itr), *outs, int(compute_history_for_itr),
-                                                                     float(history_avg_beta), w_dev), self._h)
+        return outs
+
+    def learned_iterations_stopping(self, dist_weights, num_itr, omega=0.5, improvement_slope=1e-6, omega_vec=None, compute_history_for_itr=0,
+                                    history_avg_beta=0.9, sol_avg=None, lb_first_diff_avg=None, lb_second_diff_avg=None):
+        """learned_iterations(w_i, num_itr, omega, improvement_slope, history...) of every member i — the per-solver method with its stopping
+        rule — inside the members' workgroups; returns the members' counts of iterations run, as that method does for one.  Arrays as in
+        learned_iterations_history (the history arrays are needed with compute_history_for_itr > 0 only).  With improvement_slope > 0 every
+        member must be fused_small_stop(); improvement_slope <= 0 is learned_iterations_history and every count is num_itr.
+        include/bdd_mma.h: bddmma_learned_iterations_stop_batch."""
+        import ctypes
+        s0 = self.solvers[0]
+        n = sum(s.nr_layers() for s in self.solvers)
+        w, w_dev = s0._learned_buf(dist_weights, n, "dist_weights")
+        ov = None
+        if omega_vec is not None:
+            ov, ov_dev = s0._learned_buf(omega_vec, n, "omega_vec")
+            if ov_dev != w_dev:
+                raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: dist_weights and omega_vec must both be on the host or "
+                                       "both on the device")
+        outs = [None, None, None] if int(compute_history_for_itr) == 0 else self._history_outs(n, w_dev, sol_avg, lb_first_diff_avg, lb_second_diff_avg)
+        done = (ctypes.c_uint64 * len(self.solvers))()
+        self._check(self._L.bddmma_learned_iterations_stop_batch(self._h, w, ov, float(omega), int(num_itr), float(improvement_slope), *outs,
+                                                                  int(compute_history_for_itr), float(history_avg_beta), w_dev, done), self._h)
+        return [int(x) for x in done]
 
     def grad_iterations(self, dist_weights, grad_lo, grad_hi, grad_mm, omega=0.5, track_grad_after_itr=0, track_grad_for_num_itr=1, num_caches=1,
                         omega_vec=None, out=None):

@@ -180,13 +180,17 @@ int bddmma_solve_sweep_kind(const bddmma_solver* s);
 int bddmma_fused_small(const bddmma_solver* s);
 /* 1 when bddmma_learned_iterations / _omega_vec run whole learned iterations inside one launch too (k_learned_small): bddmma_fused_small
  * holds and the learned layout — the plain one plus an omega per layer — fits the CU's LDS as well.  With improvement_slope <= 0 the iterations that compute_history_for_itr does not reach then run fused; with a stopping rule
- * (improvement_slope > 0) every iteration keeps the four launches.  variant_flags bit 19 turns it off together with bddmma_fused_small. */
+ * (improvement_slope > 0) every iteration of this call keeps the four launches (a batch: bddmma_learned_iterations_stop_batch).  variant_flags bit 19 turns it off together with bddmma_fused_small. */
 int bddmma_fused_small_learned(const bddmma_solver* s);
 /* 1 when bddmma_learned_iterations_history_batch can also run the history step of a tracked iteration (the per-BDD bounds, every BDD's
  * arg-min path and the moving averages) inside this solver's workgroup: bddmma_fused_small_learned holds and the solver has a thread per
  * BDD.  The step needs no LDS of its own — its marks live in entries that are dead between a backward sweep and the next exchange — so today
  * this is 1 wherever bddmma_fused_small_learned is. */
 int bddmma_fused_small_history(const bddmma_solver* s);
+/* 1 when bddmma_learned_iterations_stop_batch can run this solver's stopping rule (improvement_slope > 0) inside its workgroup too:
+ * bddmma_fused_small_history holds and the rule's working values — a few words of static LDS beside the learned layout — fit the CU's LDS as
+ * well. */
+int bddmma_fused_small_stop(const bddmma_solver* s);
 /* 1 when the narrow packs' solve sweeps run in the instantiation that loads what a sweep reads once (potentials, staging tables) non-temporally. */
 int bddmma_nontemporal_loads(const bddmma_solver* s);
 /* 1 when the solve sweeps of bddmma_iteration / _iterations / _run_solver rebuild the costs-from-root and costs-to-terminal on chip instead of
@@ -518,6 +522,31 @@ int bddmma_learned_iterations_batch(bddmma_batch* b, const void* dist_weights, c
 int bddmma_learned_iterations_history_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec /* or NULL */, double omega,
                                             uint64_t num_itr, void* sol_avg, void* lb_first_diff_avg, void* lb_second_diff_avg,
                                             uint64_t compute_history_for_itr, double history_avg_beta, int on_device);
+/* bddmma_learned_iterations_history_batch with the stopping rule of bddmma_learned_iterations: for every member i,
+ * bddmma_learned_iterations(member i, w_i, .., num_itr, omega, improvement_slope, its part of the three history arrays,
+ * compute_history_for_itr, history_avg_beta, .., &iterations_done[i]) — or its omega_vec form.  iterations_done: host, uint64_t[bddmma_batch_size],
+ * member i's count of iterations run in entry i.
+ * The rule runs inside the member's workgroup behind every iteration (csrc/kernels/small.hpp, STOP): the bound is reduced in the shape of
+ * bddmma_lower_bound, so it is that call's value bit for bit, and one lane applies the lines of the per-member loop in double — the set-once
+ * initial change taken at the call's iteration 0 where it is unset; converged once the bound's change falls below improvement_slope times
+ * it; stop when converged and the history has made compute_history_for_itr steps.  An iteration is tracked when it is one of the last
+ * compute_history_for_itr of num_itr or an earlier iteration's test has set converged, so the tracked window is not known when a launch
+ * starts.  A member that stops leaves through the exit exchange, as the per-member loop does; the call's launches — chunks of 32 iterations,
+ * queued without waiting — return at once for it afterwards, and its state stays what its own last launch left.  The host waits once per
+ * call, for the members' counts (with any host outputs), next to the wait for the check of the values; the first iteration needs no
+ * launch of its own in this form, as the initial change is taken in the workgroup.
+ * improvement_slope <= 0 or NaN never stops: that call IS bddmma_learned_iterations_history_batch, and every count is num_itr.
+ * Results: as bddmma_learned_iterations_history_batch states them, counts included — in float, and in double wherever no variable sits in more
+ * than two BDDs, every member's count, state, outputs and initial change are the per-member call's bit for bit; elsewhere in double a
+ * decision that is borderline within the exchange's summation order may fall differently.
+ * Everything bddmma_learned_iterations_history_batch promises holds: its refusals, its ordering, the check of the values in one launch, the
+ * outputs' "an entry the history does not reach keeps its content", the set-once initial change.  Added refusals:
+ * BDDMMA_ERR_INVALID_ARGUMENT for iterations_done == NULL; with improvement_slope > 0, BDDMMA_ERR_UNSUPPORTED, naming the member, where
+ * bddmma_fused_small_stop is 0.  Every refusal is decided before any member, output or initial change is touched. */
+int bddmma_learned_iterations_stop_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec /* or NULL */, double omega,
+                                         uint64_t num_itr, double improvement_slope, void* sol_avg, void* lb_first_diff_avg,
+                                         void* lb_second_diff_avg, uint64_t compute_history_for_itr, double history_avg_beta, int on_device,
+                                         uint64_t* iterations_done /* host, [bddmma_batch_size] */);
 /* bddmma_grad_learned_iterations(member i, its part of every array, ..) for every member i, with the same two iteration counts for all
  * members: ONE workgroup per member runs the whole call in one launch per kernel instantiation present — the tracked iterations once,
  * recording what their reverse reads, then the reverse (kernels/gradsmall.hpp) — where the per-member call issues about 25 launches and
