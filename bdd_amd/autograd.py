@@ -145,13 +145,14 @@ class _Ordered:
         return False
 
 
-def _batch_first(call, *args, **kwargs):
+def _batch_first(call, *args, also=(), **kwargs):
     """the first call of a batched path: False when the batch refuses it with BDDMMA_ERR_STATE — a member that has (had) an L-BFGS
-    wrapper, for instance, with which the list form works; the refusal has touched nothing, so the caller runs the list form instead."""
+    wrapper, for instance, with which the list form works — or with one of the codes in `also`; the refusal has touched nothing, so the
+    caller runs the list form instead."""
     try:
         call(*args, **kwargs)
     except capi.BddMmaError as e:
-        if str(e).startswith(f"bdd_mma error {capi.ERR_STATE}:"):
+        if any(str(e).startswith(f"bdd_mma error {code}:") for code in (capi.ERR_STATE, *also)):
             return False
         raise
     return True
@@ -283,11 +284,12 @@ class DualIterations(torch.autograd.Function):
               zeros: an entry the history does not reach keeps that) and are not differentiable.
     backward  bddmma_grad_learned_iterations per solver with track_grad_for_num_itr = min(iterations done, grad_dual_itr_max_itr) and
               track_grad_after_itr = done - that: the untracked iterations are treated as constants, as in the reference.  For a
-              bdd_hip_batch whose members are all fused_small_learned() and ran the same number of iterations (with different counts — a
-              stopping rule — it stays this loop: a batch call with per-member counts does not exist), ONE
-              batch.set_solver_costs and ONE batch.grad_iterations (bddmma_grad_learned_iterations_batch: one workgroup per member)
-              instead of that loop, with the same results (bit-equal in float, and in double wherever no variable
-              sits in more than two BDDs).  Gradients for
+              bdd_hip_batch whose members are all fused_small_learned(), ONE batch.set_solver_costs and ONE batch.grad_iterations
+              (bddmma_grad_learned_iterations_batch: one workgroup per member) where they ran the same number of iterations, or ONE
+              batch.grad_iterations_counts (bddmma_grad_learned_iterations_counts_batch: every member with its own two counts) where
+              they did not — a stopping rule —, instead of that loop, with the same results (bit-equal in float, and in double wherever
+              no variable sits in more than two BDDs); with different counts a BDDMMA_ERR_STATE or BDDMMA_ERR_UNSUPPORTED refusal, which
+              has touched nothing, gives the loop.  Gradients for
               lo, hi, def_mm, dist_weights and omega; one omega shared by several solvers gets the sum of their values, added in list
               order in the solvers' precision (on the torch side in both forms).  State contract of that call: a solver holds the saved input state on entry (set here) and
               again on return, both sweep states invalid; it refuses with BDDMMA_ERR_STATE (BddMmaError) while an L-BFGS wrapper is
@@ -358,15 +360,25 @@ class DualIterations(torch.autograd.Function):
         scalar = ctx.omega_scalar is not None
         g_om = torch.zeros(len(z.solvers), dtype=z.dtype, device=omega.device) if scalar else torch.zeros_like(omega)
         done = ctx.iterations_done
-        batched = z.batch is not None and len(set(done)) == 1 and all(s.fused_small_learned() for s in z.solvers)
-        if batched:   # one workgroup per member, every member's arrays at once; g_om[i] is member i's own sum
+        fused = z.batch is not None and all(s.fused_small_learned() for s in z.solvers)
+        batched = False
+        if fused and len(set(done)) == 1:   # one workgroup per member, every member's arrays at once; g_om[i] is member i's own sum
+            batched = True
             with _Ordered([z.batch]):
                 z.batch.set_solver_costs(lo_costs_batch, hi_costs_batch, def_mm_batch)
                 n = min(done[0], ctx.grad_dual_itr_max_itr)
                 z.batch.grad_iterations(dist_weights_batch, g_lo, g_hi, g_mm, omega=ctx.omega_scalar if scalar else 0.5,
                                         track_grad_after_itr=done[0] - n, track_grad_for_num_itr=n, num_caches=ctx.num_caches,
                                         omega_vec=None if scalar else omega, out=(g_w, g_om))
-        else:
+        elif fused:   # the members stopped at different counts: the same two calls, every member with its own
+            tracked = [min(d, ctx.grad_dual_itr_max_itr) for d in done]
+            with _Ordered([z.batch]):
+                batched = _batch_set_costs(z.batch, lo_costs_batch, hi_costs_batch, def_mm_batch)
+                if batched:
+                    batched = _batch_first(z.batch.grad_iterations_counts, dist_weights_batch, g_lo, g_hi, g_mm, [d - n for d, n in zip(done, tracked)],
+                                           tracked, omega=ctx.omega_scalar if scalar else 0.5, num_caches=ctx.num_caches,
+                                           omega_vec=None if scalar else omega, out=(g_w, g_om), also=(capi.ERR_UNSUPPORTED,))
+        if not batched:
             with _Ordered(z.solvers):
                 for i, (s, l) in enumerate(zip(z.solvers, z.slices(z.layers))):
                     s.set_solver_costs(lo_costs_batch[l], hi_costs_batch[l], def_mm_batch[l])

@@ -130,6 +130,7 @@ SIGNATURES = {
     "bddmma_learned_iterations_history_batch": (_I, [_V, _V, _V, _D, _U64, _V, _V, _V, _U64, _D, _I]),
     "bddmma_learned_iterations_stop_batch": (_I, [_V, _V, _V, _D, _U64, _D, _V, _V, _V, _U64, _D, _I, _V]),
     "bddmma_grad_learned_iterations_batch": (_I, [_V, _V, _V, _D, _V, _V, _V, _V, _V, _U64, _U64, _U64, _I]),
+    "bddmma_grad_learned_iterations_counts_batch": (_I, [_V, _V, _V, _D, _V, _V, _V, _V, _V, C.POINTER(_U64), C.POINTER(_U64), _U64, _I]),
     "bddmma_set_solver_costs_batch": (_I, [_V, _V, _V, _V, _I]),
     "bddmma_get_solver_costs_batch": (_I, [_V, _V, _V, _V, _I]),
     "bddmma_stream_wait_batch": (_I, [_V, _V]),

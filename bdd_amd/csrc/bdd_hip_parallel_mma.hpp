@@ -545,6 +545,19 @@ class bdd_hip_batch {
                                                    dev_grad_dist_weights_out, dev_grad_omega, (uint64_t)track_grad_after_itr,
                                                    (uint64_t)track_grad_for_num_itr, (uint64_t)num_caches, 1));
     }
+    // ... with every member's own two counts (size() entries each): the backward of learned_iterations_stopping_dev, whose members stop at
+    // different iterations.  A member whose tracked count is 0 is left untouched.  Contract: bddmma_grad_learned_iterations_counts_batch.
+    void grad_iterations_counts_dev(const REAL* dev_dist_weights, REAL* dev_grad_lo, REAL* dev_grad_hi, REAL* dev_grad_mm, REAL* dev_grad_dist_weights_out,
+                                    REAL* dev_grad_omega, REAL omega_scalar, const std::vector<size_t>& track_grad_after_itr,
+                                    const std::vector<size_t>& track_grad_for_num_itr, int num_caches, const REAL* dev_omega_vec = nullptr)
+    {
+        if (track_grad_after_itr.size() != size() || track_grad_for_num_itr.size() != size())
+            throw std::invalid_argument("grad_iterations_counts: one count of each kind per member");
+        if (num_caches < 0) throw std::invalid_argument("grad_iterations_counts: negative count");
+        const std::vector<uint64_t> after(track_grad_after_itr.begin(), track_grad_after_itr.end()), tracked(track_grad_for_num_itr.begin(), track_grad_for_num_itr.end());
+        check(bddmma_grad_learned_iterations_counts_batch(b_, dev_dist_weights, dev_omega_vec, (double)omega_scalar, dev_grad_lo, dev_grad_hi, dev_grad_mm,
+                                                          dev_grad_dist_weights_out, dev_grad_omega, after.data(), tracked.data(), (uint64_t)num_caches, 1));
+    }
     // set_solver_costs followed by backward_run / get_solver_costs of every member in one launch each, with the members' REAL[nr_layers]
     // one behind the other in the members' order.  Device pointers as in bdd_hip_parallel_mma (any of them may be null: that part is
     // skipped; the host does not wait), or host vectors (empty: skipped).  Contract: bddmma_set_solver_costs_batch / bddmma_get_solver_costs_batch.

@@ -477,6 +477,15 @@ int bddmma_grad_learned_iterations_batch(bddmma_batch* b, const void* dist_weigh
                                           track_grad_for_num_itr, num_caches, on_device);
     });
 }
+int bddmma_grad_learned_iterations_counts_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec, double omega, void* grad_lo, void* grad_hi,
+                                                void* grad_mm, void* grad_dist_weights_out, void* grad_omega_out, const uint64_t* track_grad_after_itr,
+                                                const uint64_t* track_grad_for_num_itr, uint64_t num_caches, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        return i->grad_learned_iterations_counts(dist_weights, omega_vec, omega, grad_lo, grad_hi, grad_mm, grad_dist_weights_out, grad_omega_out,
+                                                 track_grad_after_itr, track_grad_for_num_itr, num_caches, on_device);
+    });
+}
 int bddmma_set_solver_costs_batch(bddmma_batch* b, const void* lo, const void* hi, const void* mm, int on_device)
 {
     return guarded_batch(b, [&](BatchBase* i) { return i->set_solver_costs(lo, hi, mm, on_device); });

@@ -1,6 +1,7 @@
 // kernels/gradsmall.hpp — the backward of the learned iterations for a batch of one-workgroup instances in ONE launch
-// (bddmma_grad_learned_iterations_batch; BatchT::grad_learned_iterations, solver_bt.hpp).  Behind kernels.hpp and graditer.hpp; the kernel
-// itself is instantiated in solver_gs_f32.hip / solver_gs_f64.hip only.
+// (bddmma_grad_learned_iterations_batch; BatchT::grad_learned_iterations, solver_bt.hpp), and with every member's own iteration counts
+// (bddmma_grad_learned_iterations_counts_batch; BatchT::grad_learned_iterations_counts: the two kernels at the end).  Behind kernels.hpp and
+// graditer.hpp; the kernels themselves are instantiated in solver_gs_f32.hip / solver_gs_f64.hip only.
 //
 // Workgroup b runs member b through what SolverT::gi_grad_learned_iterations does with ~25 launches and copies per tracked iteration; every
 // launch or copy of that path is a phase between two __syncthreads() here:
@@ -113,8 +114,11 @@ __global__ void __launch_bounds__(256) k_grad_small_load(const GradSmallItem<REA
         if (b & (1u << k)) atomicMin(bad + k, it.member);
 }
 
+// One member's whole call in its workgroup: shared by k_grad_small_batch (one n for the launch) and k_grad_small_counts_batch (the member's own).
+// (`item` by pointer and dereferenced below the thread indices, where the kernel used to do it: the form that moves k_grad_small_batch's
+// instruction streams least — profiles/batch_grad_counts_isa.txt.)
 template <typename REAL, int NW, bool RL>
-__global__ void __launch_bounds__(64 * NW) k_grad_small_batch(const GradSmallItem<REAL>* __restrict__ items, REAL omega, uint32_t n, uint32_t use_ov, GradSmallIO<REAL> io)
+__device__ __forceinline__ void grad_small_body(const GradSmallItem<REAL>* __restrict__ item, REAL omega, uint32_t n, uint32_t use_ov, const GradSmallIO<REAL>& io)
 {
     constexpr uint32_t NT = 64 * NW;
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
@@ -122,7 +126,7 @@ __global__ void __launch_bounds__(64 * NW) k_grad_small_batch(const GradSmallIte
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63u;
 
     // ---- forward over the tracked iterations, once, recording
-    const GradSmallItem<REAL>& it = items[blockIdx.x];
+    const GradSmallItem<REAL>& it = *item;
     {
         const SmallRecord<REAL> rec{it.ws + gs_fixed_values(it.ls, it.ss, it.vs), it.ls, it.ss};
         SmallLearn<REAL> ln = it.fw.ln;
@@ -219,6 +223,60 @@ __global__ void __launch_bounds__(64 * NW) k_grad_small_batch(const GradSmallIte
         }
         if (tid == 0) io.gom[it.member] = (REAL)sh[0];
     }
+}
+template <typename REAL, int NW, bool RL>
+__global__ void __launch_bounds__(64 * NW) k_grad_small_batch(const GradSmallItem<REAL>* __restrict__ items, REAL omega, uint32_t n, uint32_t use_ov, GradSmallIO<REAL> io)
+{
+    grad_small_body<REAL, NW, RL>(items + blockIdx.x, omega, n, use_ov, io);
+}
+
+// bddmma_grad_learned_iterations_counts_batch (BatchT::grad_learned_iterations_counts): every member with its own two counts, uint32 arrays on
+// the device in the caller's member order, read by scalar loads at a uniform address.
+//
+// The untracked iterations in front: member i runs min(chunk, after[i] - first) learned iterations where after[i] > first — launched over
+// first = 0, chunk, 2 chunk, .. up to the largest after[i]; two launches of a and b iterations leave what one of a + b leaves.  A member that
+// is through (or whose tracked count is 0: the host gives it after[i] = 0) returns at its first instruction: a learned launch of 0
+// iterations would still run the exit exchange and the epilogue.  Same items, groups and dynamic LDS as the kernels above.
+template <typename REAL, int NW, bool RL>
+__global__ void __launch_bounds__(64 * NW) k_grad_small_untracked_batch(const GradSmallItem<REAL>* __restrict__ items, REAL omega, uint32_t use_ov, uint32_t first,
+                                                                        uint32_t chunk, const uint32_t* __restrict__ after)
+{
+    const GradSmallItem<REAL>& it = items[blockIdx.x];
+    const uint32_t a = after[it.member];
+    if (a <= first) return;
+    const uint32_t left = a - first;
+    SmallLearn<REAL> ln = it.fw.ln;
+    if (!use_ov) ln.omega_lay = nullptr;
+    small_iterate<REAL, NW, RL, true>(it.fw.sm, it.fw.d, it.fw.pk, omega, left < chunk ? left : chunk, RunStep{}, &ln);
+}
+// The call itself: k_grad_small_batch's body with n = tracked[member].  A member whose count is 0 is the per-member call with n == 0: its
+// in-out arrays pass through (a copy onto themselves with device arrays, into the staging buffer's output half with host arrays), both
+// outputs are zero, and nothing of the member is written — k_grad_small_load has only read it, so there is nothing to put back.
+// The call's arrays come from memory (`iop`, behind the counts in the buffer the host copies once per call), not as twenty words of kernel
+// arguments that are live from the first instruction.  The empty asm hides from the optimiser that n is not 0 behind the test: knowing it,
+// it reshapes the body's loops and takes 7 to 9 VGPRs more than k_grad_small_batch (the 16-wave streaming form: 76 bytes of scratch for 36).
+template <typename REAL, int NW, bool RL>
+__global__ void __launch_bounds__(64 * NW) k_grad_small_counts_batch(const GradSmallItem<REAL>* __restrict__ items, REAL omega, uint32_t use_ov, const GradSmallIO<REAL>* __restrict__ iop,
+                                                                     const uint32_t* __restrict__ tracked)
+{
+    const GradSmallIO<REAL>& io = *iop;
+    const GradSmallItem<REAL>& it = items[blockIdx.x];
+    const uint32_t n = tracked[it.member];
+    if (n == 0) {
+        for (uint32_t l = threadIdx.x; l < it.L; l += 64 * NW) {
+            const size_t g = (size_t)it.src + l;
+            io.lo[g] = io.in_lo[g];
+            io.hi[g] = io.in_hi[g];
+            io.mm[g] = io.in_mm[g];
+            io.gw[g] = REAL(0);
+            if (use_ov) io.gom[g] = REAL(0);
+        }
+        if (!use_ov && threadIdx.x == 0) io.gom[it.member] = REAL(0);
+        return;
+    }
+    uint32_t n_body = n;
+    asm volatile("" : "+s"(n_body));
+    grad_small_body<REAL, NW, RL>(&it, omega, n_body, use_ov, io);
 }
 
 }  // namespace bddmma

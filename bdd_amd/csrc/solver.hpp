@@ -198,6 +198,11 @@ struct BatchBase {
     virtual int grad_learned_iterations(const void* dist_weights, const void* omega_vec, double omega, void* grad_lo, void* grad_hi, void* grad_mm,
                                         void* grad_dist_weights_out, void* grad_omega_out, uint64_t track_grad_after_itr, uint64_t track_grad_for_num_itr,
                                         uint64_t num_caches, int on_device) = 0;
+    // ... with member i's own two counts in track_grad_after_itr[i] / track_grad_for_num_itr[i] (host arrays; include/bdd_mma.h:
+    // bddmma_grad_learned_iterations_counts_batch)
+    virtual int grad_learned_iterations_counts(const void* dist_weights, const void* omega_vec, double omega, void* grad_lo, void* grad_hi, void* grad_mm,
+                                               void* grad_dist_weights_out, void* grad_omega_out, const uint64_t* track_grad_after_itr,
+                                               const uint64_t* track_grad_for_num_itr, uint64_t num_caches, int on_device) = 0;
     // SolverBase::set_solver_costs followed by backward_run of every member / SolverBase::get_solver_costs of every member, one launch per
     // kernel instantiation present; the arrays as in learned_iterations, each may be null (include/bdd_mma.h: bddmma_set_solver_costs_batch)
     virtual int set_solver_costs(const void* lo, const void* hi, const void* mm, int on_device) = 0;

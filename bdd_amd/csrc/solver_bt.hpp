@@ -49,7 +49,7 @@ struct BatchT final : BatchBase {
         for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1, ev_order})
             if (e) (void)hipEventDestroy(e);
         if (d_items) (void)hipFree(d_items);
-        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_st_items, (void*)d_st_blocks, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad, (void*)d_bm_items, (void*)d_bm_stage, (void*)d_bm_bad, (void*)d_bsm_items, (void*)d_bsm_stage, (void*)d_br_items, (void*)d_br_words, (void*)d_bp_items, (void*)d_bp_stage, (void*)d_bp_bad})
+        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_st_items, (void*)d_st_blocks, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_gs_cnt, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad, (void*)d_bm_items, (void*)d_bm_stage, (void*)d_bm_bad, (void*)d_bsm_items, (void*)d_bsm_stage, (void*)d_br_items, (void*)d_br_words, (void*)d_bp_items, (void*)d_bp_stage, (void*)d_bp_bad})
             if (q) (void)hipFree(q);
         if (d_ctl) (void)hipFree(d_ctl);
         if (h_ctl) (void)hipHostFree(h_ctl);
@@ -637,6 +637,8 @@ struct BatchT final : BatchBase {
     using GsFn = typename S::GradSmallFn;
     struct GsGroup {
         GsFn fn;
+        typename S::GradSmallUntrackedFn fn_untracked;   // the call with per-member counts (grad_learned_iterations_counts)
+        typename S::GradSmallCountsFn fn_counts;
         uint32_t threads, lds, first, count;
     };
     std::vector<GsGroup> gs_groups;
@@ -645,6 +647,8 @@ struct BatchT final : BatchBase {
     GradSmallItem<REAL>* d_gs_items = nullptr;
     REAL *d_gs_ws = nullptr, *d_gs_io = nullptr; // the workspace; host arguments and results on the device: 5 inputs | 5 outputs
     uint32_t* d_gs_bad = nullptr;                // k_grad_small_load's five words
+    uint32_t* d_gs_cnt = nullptr;                // the call with per-member counts: tracked[n] | after[n] (member order) | the call's GradSmallIO
+    std::vector<uint32_t> gs_cnt;                // ... and what it is copied from
     uint64_t gs_n_rec = 0, gs_total = 0;         // tracked iterations the workspace holds; values of all members' layers
     bool gs_ready = false;
 
@@ -677,7 +681,8 @@ struct BatchT final : BatchBase {
             it.src = (uint32_t)ln_src[ord[j]];
             it.member = ord[j];
             if (groups_.empty() || key(ord[j]) != key(ord[groups_.back().first]))
-                groups_.push_back(GsGroup{S::gs_batch_fn(s->small_nw, s->small_ln_rl), 64u * (uint32_t)s->small_nw, 0u, j, 0u});
+                groups_.push_back(GsGroup{S::gs_batch_fn(s->small_nw, s->small_ln_rl), S::gs_untracked_fn(s->small_nw, s->small_ln_rl),
+                                          S::gs_counts_fn(s->small_nw, s->small_ln_rl), 64u * (uint32_t)s->small_nw, 0u, j, 0u});
             GsGroup& g = groups_.back();
             // the forward's LDS, or a wave's arrays of the reverse sweeps per pack, or the 256 doubles of the scalar omega's sum
             const uint32_t rev = (uint32_t)(s->nb_.n_packs * gi_lds_bytes(sizeof(REAL), s->pack_width));
@@ -686,12 +691,16 @@ struct BatchT final : BatchBase {
         }
         for (const GsGroup& g : groups_) {
             if (g.lds > m[0]->lds_cu) { err = "batch grad_learned_iterations: the reverse sweeps do not fit the LDS"; return BDDMMA_ERR_UNSUPPORTED; }
-            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(g.fn), g.lds)) return rc;
+            for (const void* fn : {reinterpret_cast<const void*>(g.fn), reinterpret_cast<const void*>(g.fn_untracked), reinterpret_cast<const void*>(g.fn_counts)})
+                if (int rc = raise_lds_limit(fn, g.lds)) return rc;
         }
         gs_total = ln_total;
         HIPCHK(hipMalloc((void**)&d_gs_items, n * sizeof(GradSmallItem<REAL>)));
         HIPCHK(hipMalloc((void**)&d_gs_io, (10 * gs_total + n) * sizeof(REAL)));
         HIPCHK(hipMalloc((void**)&d_gs_bad, 5 * sizeof(uint32_t)));
+        static_assert(sizeof(GradSmallIO<REAL>) % sizeof(uint32_t) == 0 && alignof(GradSmallIO<REAL>) <= 8, "io sits behind 2 n words: 8-byte aligned");
+        gs_cnt.assign(2 * n + sizeof(GradSmallIO<REAL>) / sizeof(uint32_t), 0u);
+        HIPCHK(hipMalloc((void**)&d_gs_cnt, gs_cnt.size() * sizeof(uint32_t)));
         gs_groups = std::move(groups_);
         return BDDMMA_OK;
     }
@@ -719,14 +728,19 @@ struct BatchT final : BatchBase {
         HIPCHK(hipMemcpy(d_gs_items, gs_items.data(), gs_items.size() * sizeof(GradSmallItem<REAL>), hipMemcpyHostToDevice));
         return BDDMMA_OK;
     }
-    int grad_learned_iterations(const void* w, const void* omega_vec, double omega, void* grad_lo, void* grad_hi, void* grad_mm, void* grad_w_out,
-                                void* grad_omega_out, uint64_t after, uint64_t n_track, uint64_t num_caches, int on_dev) override
+    // What both backward calls of a batch start with: the refusals, each before any member or output is touched; the preparation on first
+    // use and the workspace for the call's largest tracked count; the arrays of the call (`io`; host arrays through the staging buffer); and
+    // the one kernel that checks every array, moves the arguments into place and saves every member's entry state, with the host's wait
+    // for its verdict.  after / tracked: the per-member counts (both null: `n_track` tracked iterations for every member), on the device
+    // in d_gs_cnt — one copy with the call's io, in front of the check launch — when this returns; n_max: the largest tracked count.
+    int grad_begin(const char* me, const void* w, const void* omega_vec, double omega, void* grad_lo, void* grad_hi, void* grad_mm, void* grad_w_out,
+                   void* grad_omega_out, uint64_t n_track, const uint64_t* after, const uint64_t* tracked, bool counts, int on_dev, GradSmallIO<REAL>& io,
+                   uint64_t& n_max)
     {
-        (void)num_caches;   // every tracked iteration is recorded: nothing is replayed, and the result does not depend on it
         int rc;
-        const char* const me = "batch grad_learned_iterations";
         const uint32_t n = (uint32_t)m.size();
         if (!w || !grad_lo || !grad_hi || !grad_mm || !grad_w_out || !grad_omega_out) { err = std::string(me) + ": null pointer"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        if (counts && (!after || !tracked)) { err = "batch grad_learned_iterations_counts: null count array"; return BDDMMA_ERR_INVALID_ARGUMENT; }
         if ((rc = check_state())) return rc;
         for (uint32_t i = 0; i < n; ++i)
             if (!m[i]->small_ln_ok) {
@@ -735,21 +749,32 @@ struct BatchT final : BatchBase {
             }
         const bool ov = omega_vec != nullptr;
         if (!ov && !(omega >= 0.0 && omega < std::numeric_limits<double>::infinity())) { err = std::string(me) + ": omega is negative or not finite"; return BDDMMA_ERR_INVALID_ARGUMENT; }
-        if (n_track > 0xFFFFFFFFull) { err = std::string(me) + ": too many tracked iterations"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        n_max = n_track;
+        if (counts) {
+            n_max = 0;
+            for (uint32_t i = 0; i < n; ++i) {
+                if (tracked[i] > 0xFFFFFFFFull) { err = "batch member " + std::to_string(i) + ": too many tracked iterations"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+                n_max = std::max(n_max, tracked[i]);
+            }
+            for (uint32_t i = 0; i < n; ++i)   // (a member that tracks nothing runs nothing: its untracked count is not looked at)
+                if (tracked[i] > 0 && after[i] > 0xFFFFFFFFull) { err = "batch member " + std::to_string(i) + ": too many untracked iterations"; return BDDMMA_ERR_INVALID_ARGUMENT; }
+        } else if (n_track > 0xFFFFFFFFull) {
+            err = std::string(me) + ": too many tracked iterations";
+            return BDDMMA_ERR_INVALID_ARGUMENT;
+        }
         HIPCHK(hipSetDevice(device));
         if (!gs_ready) {
             if ((rc = gs_prepare())) return rc;
             gs_ready = true;
         }
-        if ((rc = gs_workspace(n_track))) return rc;
-        const uint64_t n_omega = ov ? gs_total : n;
+        if ((rc = gs_workspace(n_max))) return rc;
         // The batch stream behind everything queued on the members; then one kernel checks every array, moves the arguments into place and
         // saves every member's entry state.  No member's state is written before the check has been read.
         for (uint32_t i = 0; i < n; ++i) {
             HIPCHK(hipEventRecord(ev_in[i], m[i]->stream));
             HIPCHK(hipStreamWaitEvent(stream, ev_in[i], 0));
         }
-        GradSmallIO<REAL> io{};
+        io = GradSmallIO<REAL>{};
         if (on_dev) {
             io.w = (const REAL*)w; io.ov = (const REAL*)omega_vec;
             io.in_lo = (const REAL*)grad_lo; io.in_hi = (const REAL*)grad_hi; io.in_mm = (const REAL*)grad_mm;
@@ -764,6 +789,14 @@ struct BatchT final : BatchBase {
             io.w = dst[0]; io.ov = ov ? dst[1] : nullptr; io.in_lo = dst[2]; io.in_hi = dst[3]; io.in_mm = dst[4];
             REAL* const o = d_gs_io + 5 * gs_total;
             io.lo = o; io.hi = o + gs_total; io.mm = o + 2 * gs_total; io.gw = o + 3 * gs_total; io.gom = o + 4 * gs_total;
+        }
+        if (counts) {   // tracked[n] | after[n] | io, which k_grad_small_counts_batch reads from memory (kernels/gradsmall.hpp)
+            for (uint32_t i = 0; i < n; ++i) {
+                gs_cnt[i] = (uint32_t)tracked[i];
+                gs_cnt[n + i] = tracked[i] > 0 ? (uint32_t)after[i] : 0u;
+            }
+            std::memcpy(gs_cnt.data() + 2 * n, &io, sizeof(io));
+            HIPCHK(hipMemcpyAsync(d_gs_cnt, gs_cnt.data(), gs_cnt.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         }
         HIPCHK(hipMemsetAsync(d_gs_bad, 0xFF, 5 * sizeof(uint32_t), stream));
         hipLaunchKernelGGL(S::gs_load_fn(), dim3(n), dim3(256), 0, stream, (const GradSmallItem<REAL>*)d_gs_items, io, d_gs_bad);
@@ -783,8 +816,8 @@ struct BatchT final : BatchBase {
                 return BDDMMA_ERR_INVALID_ARGUMENT;
             }
         }
-        const hipMemcpyKind out_kind = on_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        if (n_track == 0) {   // the in-out arrays stay as they are, both outputs are zero
+        if (n_max == 0) {   // the in-out arrays stay as they are, both outputs are zero
+            const uint64_t n_omega = ov ? gs_total : n;
             if (on_dev) {
                 HIPCHK(hipMemsetAsync(grad_w_out, 0, gs_total * sizeof(REAL), stream));
                 HIPCHK(hipMemsetAsync(grad_omega_out, 0, n_omega * sizeof(REAL), stream));
@@ -794,6 +827,35 @@ struct BatchT final : BatchBase {
             }
             return join_out();
         }
+        return BDDMMA_OK;
+    }
+    // ... and end with: the results to host arrays, the members' streams behind the batch's
+    int grad_end(const char* me, int rc, bool ov, void* grad_lo, void* grad_hi, void* grad_mm, void* grad_w_out, void* grad_omega_out, int on_dev)
+    {
+        if (!rc && !on_dev) {
+            const uint64_t n_omega = ov ? gs_total : m.size();
+            const REAL* const o = d_gs_io + 5 * gs_total;
+            void* dst[5] = {grad_lo, grad_hi, grad_mm, grad_w_out, grad_omega_out};
+            for (int k = 0; k < 5 && !rc; ++k)
+                if (hipMemcpyAsync(dst[k], o + (uint64_t)k * gs_total, (k == 4 ? n_omega : gs_total) * sizeof(REAL), hipMemcpyDeviceToHost, stream) != hipSuccess) rc = BDDMMA_ERR_DEVICE;
+            if (!rc && hipStreamSynchronize(stream) != hipSuccess) rc = BDDMMA_ERR_DEVICE;
+            if (rc) err = std::string(me) + ": copying the results failed";
+        }
+        const int rc2 = join_out();
+        return rc ? rc : rc2;
+    }
+    int grad_learned_iterations(const void* w, const void* omega_vec, double omega, void* grad_lo, void* grad_hi, void* grad_mm, void* grad_w_out,
+                                void* grad_omega_out, uint64_t after, uint64_t n_track, uint64_t num_caches, int on_dev) override
+    {
+        (void)num_caches;   // every tracked iteration is recorded: nothing is replayed, and the result does not depend on it
+        int rc;
+        const char* const me = "batch grad_learned_iterations";
+        const uint32_t n = (uint32_t)m.size();
+        const bool ov = omega_vec != nullptr;
+        GradSmallIO<REAL> io{};
+        uint64_t n_max = 0;
+        if ((rc = grad_begin(me, w, omega_vec, omega, grad_lo, grad_hi, grad_mm, grad_w_out, grad_omega_out, n_track, nullptr, nullptr, false, on_dev, io, n_max))) return rc;
+        if (n_track == 0) return BDDMMA_OK;
         // ---- the members are touched from here on
         std::vector<char> dvar_valid(n);
         for (uint32_t i = 0; i < n; ++i) dvar_valid[i] = m[i]->delta_var_valid;
@@ -801,7 +863,7 @@ struct BatchT final : BatchBase {
         const REAL omega_r = (REAL)omega;
         uint64_t left = after;
         while (left && !rc) {   // the untracked iterations: the fused learned launches
-            const uint32_t chunk = (uint32_t)std::min<uint64_t>(left, 1u << 14);
+            const uint32_t chunk = (uint32_t)std::min<uint64_t>(left, GS_CHUNK);
             rc = launch_learned(omega_r, chunk, ov);
             left -= chunk;
         }
@@ -817,17 +879,57 @@ struct BatchT final : BatchBase {
             m[i]->costs_changed();
             m[i]->delta_var_valid = dvar_valid[i];
         }
-        if (!rc && !on_dev) {
-            const REAL* const o = d_gs_io + 5 * gs_total;
-            void* dst[5] = {grad_lo, grad_hi, grad_mm, grad_w_out, grad_omega_out};
-            for (int k = 0; k < 5 && !rc; ++k)
-                if (hipMemcpyAsync(dst[k], o + (uint64_t)k * gs_total, (k == 4 ? n_omega : gs_total) * sizeof(REAL), out_kind, stream) != hipSuccess) rc = BDDMMA_ERR_DEVICE;
-            if (!rc && hipStreamSynchronize(stream) != hipSuccess) rc = BDDMMA_ERR_DEVICE;
-            if (rc) err = std::string(me) + ": copying the results failed";
-        }
-        const int rc2 = join_out();
-        return rc ? rc : rc2;
+        return grad_end(me, rc, ov, grad_lo, grad_hi, grad_mm, grad_w_out, grad_omega_out, on_dev);
     }
+    // Every member with its own two counts (kernels/gradsmall.hpp: k_grad_small_untracked_batch, k_grad_small_counts_batch).  A member whose
+    // tracked count is 0 is not touched: no sweep, no iteration, no bookkeeping — its workgroups pass the in-out arrays through and zero
+    // its outputs.  The host waits where grad_learned_iterations waits.
+    int grad_learned_iterations_counts(const void* w, const void* omega_vec, double omega, void* grad_lo, void* grad_hi, void* grad_mm, void* grad_w_out,
+                                       void* grad_omega_out, const uint64_t* after, const uint64_t* tracked, uint64_t num_caches, int on_dev) override
+    {
+        (void)num_caches;
+        int rc;
+        const char* const me = "batch grad_learned_iterations";   // (the shared refusals keep their messages)
+        const uint32_t n = (uint32_t)m.size();
+        const bool ov = omega_vec != nullptr;
+        GradSmallIO<REAL> io{};
+        uint64_t n_max = 0;
+        if ((rc = grad_begin(me, w, omega_vec, omega, grad_lo, grad_hi, grad_mm, grad_w_out, grad_omega_out, 0, after, tracked, true, on_dev, io, n_max))) return rc;
+        if (n_max == 0) return BDDMMA_OK;
+        // ---- the members with a tracked count are touched from here on (join_in's sweeps for them alone)
+        std::vector<char> dvar_valid(n), idle(n);
+        uint32_t after_max = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            dvar_valid[i] = m[i]->delta_var_valid;
+            idle[i] = gs_cnt[i] == 0;
+            after_max = std::max(after_max, gs_cnt[n + i]);
+        }
+        run_mask = idle.data();
+        rc = join_in();
+        run_mask = nullptr;
+        if (rc) { (void)join_out(); return rc; }
+        const REAL omega_r = (REAL)omega;
+        for (uint64_t first = 0; first < after_max && !rc; first += GS_CHUNK)
+            for (const GsGroup& g : gs_groups) {
+                hipLaunchKernelGGL(g.fn_untracked, dim3(g.count), dim3(g.threads), g.lds, stream, (const GradSmallItem<REAL>*)(d_gs_items + g.first), omega_r,
+                                   ov ? 1u : 0u, (uint32_t)first, GS_CHUNK, (const uint32_t*)(d_gs_cnt + n));
+                if (hipGetLastError() != hipSuccess) { err = std::string(me) + ": launch failed"; rc = BDDMMA_ERR_DEVICE; break; }
+            }
+        if (!rc)
+            for (const GsGroup& g : gs_groups) {
+                hipLaunchKernelGGL(g.fn_counts, dim3(g.count), dim3(g.threads), g.lds, stream, (const GradSmallItem<REAL>*)(d_gs_items + g.first), omega_r, ov ? 1u : 0u,
+                                   reinterpret_cast<const GradSmallIO<REAL>*>(d_gs_cnt + 2 * n), (const uint32_t*)d_gs_cnt);
+                if (hipGetLastError() != hipSuccess) { err = std::string(me) + ": launch failed"; rc = BDDMMA_ERR_DEVICE; break; }
+            }
+        for (uint32_t i = 0; i < n; ++i)
+            if (!idle[i]) {
+                m[i]->small_launched();
+                m[i]->costs_changed();
+                m[i]->delta_var_valid = dvar_valid[i];
+            }
+        return grad_end(me, rc, ov, grad_lo, grad_hi, grad_mm, grad_w_out, grad_omega_out, on_dev);
+    }
+    static constexpr uint32_t GS_CHUNK = 1u << 14;   // untracked iterations per launch
 
     // ---- the members' solver costs, all at once (kernels/batchcosts.hpp: k_small_set_batch, k_small_get_batch; the kernels compile in
     // solver_bc_f32.hip / _f64.hip).  The set kernel is grouped by the members' wave count, as the iteration kernels are; bc_items[j].src is

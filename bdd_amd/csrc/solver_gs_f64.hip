@@ -4,4 +4,6 @@
 namespace bddmma {
 template SolverT<double>::GradSmallFn SolverT<double>::gs_batch_fn(int, bool);
 template SolverT<double>::GradSmallLoadFn SolverT<double>::gs_load_fn();
+template SolverT<double>::GradSmallUntrackedFn SolverT<double>::gs_untracked_fn(int, bool);
+template SolverT<double>::GradSmallCountsFn SolverT<double>::gs_counts_fn(int, bool);
 }  // namespace bddmma

@@ -989,6 +989,11 @@ struct SolverT final : SolverBase {
     using GradSmallLoadFn = void (*)(const GradSmallItem<REAL>*, GradSmallIO<REAL>, uint32_t*);
     static GradSmallFn gs_batch_fn(int nw, bool rl);
     static GradSmallLoadFn gs_load_fn();
+    // ... with per-member counts (BatchT::grad_learned_iterations_counts): the untracked iterations in front, and the call itself
+    using GradSmallUntrackedFn = void (*)(const GradSmallItem<REAL>*, REAL, uint32_t, uint32_t, uint32_t, const uint32_t*);
+    using GradSmallCountsFn = void (*)(const GradSmallItem<REAL>*, REAL, uint32_t, const GradSmallIO<REAL>*, const uint32_t*);
+    static GradSmallUntrackedFn gs_untracked_fn(int nw, bool rl);
+    static GradSmallCountsFn gs_counts_fn(int nw, bool rl);
     // The learned iterations with their history for a batch (kernels/smallhist.hpp; BatchT::learned_iterations_history): the kernels live in
     // solver_sh_f32.hip / _f64.hip.
     using SmallHistFn = void (*)(const SmallHistItem<REAL>*, REAL, uint32_t, uint32_t, uint32_t, uint32_t);

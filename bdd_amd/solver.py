@@ -747,6 +747,39 @@ class bdd_hip_batch:
         self._check(call(self._h, w, ov, float(omega), *(_ptr(x) for x in g + res), *tail, 0), self._h)
         return g[0], g[1], g[2], res[0], res[1]
 
+    def grad_iterations_counts(self, dist_weights, grad_lo, grad_hi, grad_mm, track_grad_after_itr, track_grad_for_num_itr, omega=0.5, num_caches=1,
+                               omega_vec=None, out=None):
+        """grad_iterations with every member's own two counts: track_grad_after_itr / track_grad_for_num_itr are sequences of
+        len(solvers) — what the backward of learned_iterations_stopping needs, whose members stop at different iterations.  Arrays, results
+        and `out` as in grad_iterations.  A member whose tracked count is 0 is left untouched: its parts of grad_lo / grad_hi / grad_mm stay,
+        its parts of the two outputs are zero.  include/bdd_mma.h: bddmma_grad_learned_iterations_counts_batch."""
+        import ctypes
+        s0 = self.solvers[0]
+        k = len(self.solvers)
+        assert len(track_grad_after_itr) == k and len(track_grad_for_num_itr) == k, f"expected {k} counts of each kind"
+        n = sum(s.nr_layers() for s in self.solvers)
+        n_om = n if omega_vec is not None else k
+        dev = _is_dev(grad_lo)
+        w, w_dev = s0._learned_buf(dist_weights, n, "dist_weights")
+        ov, ov_dev = s0._learned_buf(omega_vec, n, "omega_vec") if omega_vec is not None else (None, w_dev)
+        if w_dev != int(dev) or ov_dev != int(dev):
+            raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: the arrays of a batch call must all be on the host or all "
+                                   "on the device")
+        tail = ((ctypes.c_uint64 * k)(*(int(x) for x in track_grad_after_itr)), (ctypes.c_uint64 * k)(*(int(x) for x in track_grad_for_num_itr)),
+                int(num_caches))
+        call = self._L.bddmma_grad_learned_iterations_counts_batch
+        if dev:
+            assert out is not None and len(out) == 2, "device gradients need device output buffers: out=(grad_dist_weights, grad_omega)"
+            ptrs = [_dev_ptr(x, c, s0.value_type) for x, c in zip((grad_lo, grad_hi, grad_mm, out[0], out[1]), (n, n, n, n, n_om))]
+            self._check(call(self._h, w, ov, float(omega), *ptrs, *tail, 1), self._h)
+            return grad_lo, grad_hi, grad_mm, out[0], out[1]
+        g = [np.array(x, dtype=s0.value_type, order="C") for x in (grad_lo, grad_hi, grad_mm)]
+        for x in g:
+            assert x.size == n, f"expected {n} values, got {x.size}"
+        res = [np.zeros(n, s0.value_type), np.zeros(n_om, s0.value_type)]
+        self._check(call(self._h, w, ov, float(omega), *(_ptr(x) for x in g + res), *tail, 0), self._h)
+        return g[0], g[1], g[2], res[0], res[1]
+
     def _costs_args(self, arrays, what):
         """three per-layer arrays of a batch call (None: skipped) as pointers and the on_device flag; device tensors or NumPy, all of
         one kind"""

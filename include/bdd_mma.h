@@ -575,6 +575,29 @@ int bddmma_learned_iterations_stop_batch(bddmma_batch* b, const void* dist_weigh
 int bddmma_grad_learned_iterations_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec /* or NULL */, double omega,
                                          void* grad_lo, void* grad_hi, void* grad_mm, void* grad_dist_weights_out, void* grad_omega_out,
                                          uint64_t track_grad_after_itr, uint64_t track_grad_for_num_itr, uint64_t num_caches, int on_device);
+/* bddmma_grad_learned_iterations(member i, its part of every array, .., track_grad_after_itr[i], track_grad_for_num_itr[i], ..) for every
+ * member i: bddmma_grad_learned_iterations_batch with every member's own two counts — what the backward of
+ * bddmma_learned_iterations_stop_batch needs, whose members stop at different iterations.  Still one workgroup per member and one launch
+ * per kernel instantiation present for the call itself; the untracked iterations in front run in launches of up to 2^14 iterations, in
+ * which a member that has run its own count returns at once.  The two count arrays are copied to the device once per call.
+ * Arrays, grad_omega_out, on_device, results, state contract, ordering and workspace: as bddmma_grad_learned_iterations_batch states them,
+ * for the members whose tracked count is above 0.  The workspace is sized for the largest tracked count of the call and grows only when
+ * that exceeds every earlier call's, through either entry point.
+ * A member with track_grad_for_num_itr[i] == 0 is left untouched, as its per-member call leaves it: no iteration runs for it (its
+ * untracked count is not looked at), its arc costs, deferred differences and delta stay as they are, neither sweep state nor its cached
+ * bound is invalidated, its parts of grad_lo / grad_hi / grad_mm are unchanged, its part of grad_dist_weights_out and its entry (with
+ * omega_vec: its part) of grad_omega_out are zero.  Its arguments are checked like every member's.  All tracked counts 0: no member is
+ * touched.
+ * Refusals: those of bddmma_grad_learned_iterations_batch with its messages and its order of checks, and BDDMMA_ERR_INVALID_ARGUMENT for
+ * a NULL count array, for a tracked count above 0xFFFFFFFF and, where the tracked count is above 0, for an untracked count above
+ * 0xFFFFFFFF — bddmma_batch_last_error naming the first such member.  Each is decided before any member's state or any output is touched.
+ * Every kernel instantiation of this call is built, so no member that bddmma_grad_learned_iterations_batch takes is refused here.
+ * num_caches is accepted and ignored, as there. */
+int bddmma_grad_learned_iterations_counts_batch(bddmma_batch* b, const void* dist_weights, const void* omega_vec /* or NULL */, double omega,
+                                                void* grad_lo, void* grad_hi, void* grad_mm, void* grad_dist_weights_out, void* grad_omega_out,
+                                                const uint64_t* track_grad_after_itr /* host, [bddmma_batch_size] */,
+                                                const uint64_t* track_grad_for_num_itr /* host, [bddmma_batch_size] */, uint64_t num_caches,
+                                                int on_device);
 /* bddmma_set_solver_costs(member i, its part of lo / hi / mm, ..) followed by bddmma_backward_run(member i) for every member i: one
  * workgroup per member scatters the member's values and runs its plain backward sweep out of LDS, one launch per wave count present —
  * where the per-member call is three copies, three kernels and a host synchronisation, and leaves the costs-to-terminal stale, so that
