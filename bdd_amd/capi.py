@@ -146,6 +146,7 @@ SIGNATURES = {
     "bddmma_batch_time_iterations": (_I, [_V, _D, _U64, C.POINTER(_D)]),
     "bddmma_batch_run_solver": (_I, [_V, _U64, _D, _D, _D, C.POINTER(RunResult)]),
     "bddmma_batch_lower_bounds": (_I, [_V, C.POINTER(_D)]),
+    "bddmma_lower_bound_batch": (_I, [_V, C.POINTER(_D), _I]),
     "bddmma_incremental_mm_agreement_rounding": (_I, [_V, _V, _D, _D, _U64, _U64, C.c_uint32, _I, _V, C.POINTER(_I)]),
     "bddmma_perturb_primal_costs_batch": (_I, [_V, _D, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), _V, _V, _V]),
     "bddmma_incremental_mm_agreement_rounding_batch": (_I, [_V, _D, _D, _U64, _U64, C.c_uint32, _V, C.POINTER(_I), C.POINTER(_U64)]),

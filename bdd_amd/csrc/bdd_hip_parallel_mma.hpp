@@ -734,6 +734,8 @@ class bdd_hip_batch {
         check(bddmma_batch_lower_bounds(b_, lb.data()));
         return lb;
     }
+    // ... into the caller's device array (double[size()]) on the batch's stream; the host does not wait (bddmma_lower_bound_batch)
+    void lower_bounds(double* out_device) { check(bddmma_lower_bound_batch(b_, out_device, 1)); }
     bddmma_batch* handle() { return b_; }
 
    private:

@@ -557,11 +557,18 @@ int bddmma_batch_run_solver(bddmma_batch* b, uint64_t max_iter, double tolerance
 {
     return guarded_batch(b, [&](BatchBase* i) { return i->run_plain(max_iter, tolerance, improvement_slope, time_limit, res); });
 }
+int bddmma_lower_bound_batch(bddmma_batch* b, double* out, int on_device)
+{
+    return guarded_batch(b, [&](BatchBase* i) {
+        if (!out) { i->err = "batch lower_bound: null output pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
+        return i->lower_bounds(out, on_device, true);
+    });
+}
 int bddmma_batch_lower_bounds(bddmma_batch* b, double* out)
 {
     return guarded_batch(b, [&](BatchBase* i) {
         if (!out) { i->err = "batch: null output pointer"; return (int)BDDMMA_ERR_INVALID_ARGUMENT; }
-        return i->lower_bounds(out);
+        return i->lower_bounds(out, 0, false);
     });
 }
 

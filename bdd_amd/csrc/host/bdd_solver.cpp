@@ -14,6 +14,8 @@
 #include <fstream>
 #include <iostream>
 #include <limits>
+#include <map>
+#include <memory>
 #include <set>
 #include <sstream>
 
@@ -43,12 +45,57 @@ std::string extension(const std::string& p)
     const size_t d = p.find_last_of('.'), s = p.find_last_of('/');
     return d == std::string::npos || (s != std::string::npos && d < s) ? "" : p.substr(d);
 }
+// the values solve_dual() and perturbation_rounding() pass on, with their defaults and their casts
+bdd_solver::fuse_settings settings_of(const json& config)
+{
+    bdd_solver::fuse_settings f;
+    f.f64 = config.string_or("precision", "double") == "double";
+    const json& tc = config["termination criteria"];
+    f.max_iter = (uint64_t)tc.number_or("maximum iterations", 1000);
+    f.tolerance = tc.number_or("minimum improvement", 1e-6);
+    f.slope = tc.number_or("improvement slope", 1e-9);
+    f.time_limit = tc.number_or("time limit", 3600);
+    f.rounding = config.contains("perturbation rounding");
+    if (f.rounding) {
+        const json& pr = config["perturbation rounding"];
+        f.init_delta = pr.number_or("initial perturbation", 0.1);
+        f.growth = pr.number_or("perturbation growth rate", 1.1);
+        f.inner = (uint64_t)pr.number_or("inner iterations", 100);
+        f.outer = (uint64_t)pr.number_or("outer iterations", 100);
+        f.seed = (uint32_t)pr.number_or("seed", 0);
+    }
+    return f;
+}
+std::string key_of(const json& config)
+{
+    if (!GPU_MMA.count(config.string_or("relaxation solver", "cuda parallel mma"))) return "";
+    const bdd_solver::fuse_settings f = settings_of(config);
+    char buf[384];
+    int n = std::snprintf(buf, sizeof buf, "%s|%llu|%.17g|%.17g|%.17g", f.f64 ? "f64" : "f32", (unsigned long long)f.max_iter, f.tolerance, f.slope, f.time_limit);
+    if (f.rounding && n > 0 && (size_t)n < sizeof buf)
+        std::snprintf(buf + n, sizeof buf - (size_t)n, "|round|%.17g|%.17g|%llu|%llu|%u", f.init_delta, f.growth, (unsigned long long)f.inner,
+                      (unsigned long long)f.outer, (unsigned)f.seed);
+    return buf;
+}
+json parse_config(const std::string& config)
+{
+    json c = json::parse(file_exists(config) ? slurp(config) : config);
+    if (!c.is_object()) throw std::runtime_error("configuration must be a JSON object");
+    return c;
+}
 }  // namespace
 
 bdd_solver::bdd_solver(const std::string& config, bool quiet, int device) : quiet_(quiet), device_(device)
 {
-    config_ = json::parse(file_exists(config) ? slurp(config) : config);
-    if (!config_.is_object()) throw std::runtime_error("configuration must be a JSON object");
+    config_ = parse_config(config);
+}
+
+std::string fuse_key(const std::string& config) { return key_of(parse_config(config)); }
+bdd_solver::fuse_settings bdd_solver::settings() const { return settings_of(config_); }
+std::string bdd_solver::fuse_key() const { return key_of(config_); }
+bool bdd_solver::fusable() const
+{
+    return constructed_ && lbfgs_ == nullptr && GPU_MMA.count(config_.string_or("relaxation solver", "cuda parallel mma")) != 0 && bddmma_fused_small(solver_) == 1;
 }
 
 bdd_solver::~bdd_solver()
@@ -162,9 +209,14 @@ bddmma_run_result bdd_solver::solve_dual()
     bddmma_run_result res{};
     check(bddmma_run_solver(solver_, lbfgs_, (uint64_t)tc.number_or("maximum iterations", 1000), tc.number_or("minimum improvement", 1e-6),
                             tc.number_or("improvement slope", 1e-9), tc.number_or("time limit", 3600), quiet_ ? 0 : 1, &res));
+    adopt_dual(res);
+    return res;
+}
+
+void bdd_solver::adopt_dual(const bddmma_run_result& res)
+{
     log("[bdd solver] Terminated dual optimization");
     result_ = res;
-    return res;
 }
 
 std::vector<char> bdd_solver::perturbation_rounding()
@@ -177,10 +229,17 @@ std::vector<char> bdd_solver::perturbation_rounding()
                                                    pr.number_or("perturbation growth rate", 1.1), (uint64_t)pr.number_or("inner iterations", 100),
                                                    (uint64_t)pr.number_or("outer iterations", 100), (uint32_t)pr.number_or("seed", 0),
                                                    quiet_ ? 0 : 1, sol.data(), &found));
+    adopt_rounding(sol.data(), found != 0);
+    return found ? solution_ : std::vector<char>{};
+}
+
+void bdd_solver::adopt_rounding(const char* sol_in, bool found)
+{
     if (!found) {
         log("[incremental primal rounding] No solution found");
-        return {};
+        return;
     }
+    std::vector<char> sol(sol_in, sol_in + bddmma_nr_variables(solver_));
     sol.resize(ilp_.nr_variables(), 0);  // auxiliary split variables are not part of the answer
     for (size_t v = 0; v < sol.size() && v < free_ones_.size(); ++v)
         if (free_ones_[v] >= 0) sol[v] = free_ones_[v];  // variables of the objective only: their better value (construct_solver)
@@ -190,10 +249,16 @@ std::vector<char> bdd_solver::perturbation_rounding()
     o.precision(12);
     o << "[incremental primal rounding] solution objective = " << solution_objective_;
     log(o.str());
-    return solution_;
 }
 
 void bdd_solver::solve()
+{
+    construct();
+    solve_dual();
+    perturbation_rounding();
+}
+
+void bdd_solver::construct()
 {
     if (!constructed_) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -234,8 +299,6 @@ void bdd_solver::solve()
         std::snprintf(buf, sizeof buf, "%.3f", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
         log(std::string("[bdd solver] set-up time = ") + buf + " s");
     }
-    solve_dual();
-    perturbation_rounding();
 }
 
 double bdd_solver::lower_bound()
@@ -285,31 +348,122 @@ static void share_layout_threads(size_t slots)
 
 std::vector<batch_result> solve_batch(const std::vector<std::string>& configs, const std::vector<int>& devices, bool quiet)
 {
+    return solve_batch(configs, devices, quiet, batch_options{});
+}
+
+namespace {
+// a constructed instance waiting for the others of its key
+struct parked {
+    size_t index;                     // of its config, and of its result
+    std::unique_ptr<bdd_solver> s;
+    double construct_seconds;
+};
+void take_results(bdd_solver& s, batch_result& r)
+{
+    r.lower_bound = s.lower_bound();
+    r.iterations = s.result().iterations;
+    r.has_primal = !s.solution().empty();
+    r.primal = s.solution_objective();
+    r.ok = true;
+}
+// One batch over the members of a key: the dual run, the rounding where the key has it, the members' results; then the batch and the
+// members are destroyed.  A failing batch call is every member's error.
+void flush(std::vector<parked>& group, std::vector<batch_result>& out, bool quiet)
+{
+    if (group.empty()) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    bddmma_batch* b = nullptr;
+    std::string failure;
+    try {
+        std::vector<bddmma_solver*> handles;
+        for (parked& p : group) handles.push_back(p.s->handle());
+        if (bddmma_batch_create(&b, handles.data(), handles.size()) != BDDMMA_OK) throw std::runtime_error(bddmma_batch_last_error(nullptr));
+        const bdd_solver::fuse_settings f = group.front().s->settings();
+        std::vector<bddmma_run_result> res(group.size());
+        if (bddmma_batch_run_solver(b, f.max_iter, f.tolerance, f.slope, f.time_limit, res.data()) != BDDMMA_OK) throw std::runtime_error(bddmma_batch_last_error(b));
+        for (size_t i = 0; i < group.size(); ++i) group[i].s->adopt_dual(res[i]);
+        if (f.rounding) {
+            std::vector<size_t> off(group.size() + 1, 0);
+            for (size_t i = 0; i < group.size(); ++i) off[i + 1] = off[i] + bddmma_nr_variables(handles[i]);
+            std::vector<char> sol(std::max<size_t>(off.back(), 1), 0);
+            std::vector<int> found(group.size(), 0);
+            if (bddmma_incremental_mm_agreement_rounding_batch(b, f.init_delta, f.growth, f.inner, f.outer, f.seed, sol.data(), found.data(), nullptr) != BDDMMA_OK)
+                throw std::runtime_error(bddmma_batch_last_error(b));
+            for (size_t i = 0; i < group.size(); ++i) group[i].s->adopt_rounding(sol.data() + off[i], found[i] != 0);
+        }
+        for (parked& p : group) {
+            batch_result& r = out[p.index];
+            try {
+                take_results(*p.s, r);
+            } catch (const std::exception& e) {
+                r.error = e.what();
+            }
+        }
+    } catch (const std::exception& e) {
+        failure = e.what();
+    }
+    if (b) bddmma_batch_destroy(b);
+    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (parked& p : group) {
+        batch_result& r = out[p.index];
+        if (!failure.empty()) {
+            r.ok = false;
+            r.error = failure;
+        }
+        r.fused = true;
+        r.seconds = p.construct_seconds + wall;
+        if (!quiet) {
+            std::ostringstream o;
+            o.precision(12);
+            o << "[bdd solver] fused batch of " << group.size() << ", config " << p.index << ": ";
+            if (r.ok) o << "iterations = " << r.iterations << ", lower bound = " << r.lower_bound;
+            else o << "error: " << r.error;
+            std::cout << o.str() << std::endl;
+        }
+        p.s.reset();
+    }
+    group.clear();
+}
+}  // namespace
+
+std::vector<batch_result> solve_batch(const std::vector<std::string>& configs, const std::vector<int>& devices, bool quiet, const batch_options& opt)
+{
     std::vector<batch_result> out(configs.size());
     if (devices.empty()) throw std::runtime_error("solve_batch: no devices");
+    if (opt.fuse_small && opt.max_group == 0) throw std::runtime_error("solve_batch: max_group must be at least 1");
     std::atomic<size_t> next{0};
     auto worker = [&](int device) {
         share_layout_threads(devices.size());
+        std::map<std::string, std::vector<parked>> keys;   // this thread's parked instances (one device: a batch's members share it)
         for (;;) {
             const size_t i = next.fetch_add(1);
-            if (i >= configs.size()) return;
+            if (i >= configs.size()) break;
             batch_result& r = out[i];
             r.config = configs[i];
             r.device = device;
             const auto t0 = std::chrono::steady_clock::now();
+            auto seconds = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
             try {
-                bdd_solver s(configs[i], quiet, device);
-                s.solve();
-                r.lower_bound = s.lower_bound();
-                r.iterations = s.result().iterations;
-                r.has_primal = !s.solution().empty();
-                r.primal = s.solution_objective();
-                r.ok = true;
+                // (a fused batch has no per-iteration log: its members are constructed quietly too when the farm is)
+                auto s = std::make_unique<bdd_solver>(configs[i], quiet, device);
+                if (opt.fuse_small) {
+                    s->construct();
+                    if (s->fusable()) {
+                        const std::string key = s->fuse_key();
+                        std::vector<parked>& group = keys[key];
+                        group.push_back(parked{i, std::move(s), seconds()});
+                        if (group.size() >= opt.max_group) flush(group, out, quiet);
+                        continue;
+                    }
+                }
+                s->solve();
+                take_results(*s, r);
             } catch (const std::exception& e) {
                 r.error = e.what();
             }
-            r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            r.seconds = seconds();
         }
+        for (auto& kv : keys) flush(kv.second, out, quiet);
     };
     std::vector<std::thread> th;
     for (int d : devices) th.emplace_back(worker, d);

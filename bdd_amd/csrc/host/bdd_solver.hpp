@@ -34,6 +34,26 @@ public:
     bddmma_run_result solve_dual();                              // :277-309
     std::vector<char> perturbation_rounding();                   // :318-380 (empty: none found / not requested)
     void solve();                                                // :477-495
+    // The stages of solve() for a caller that drives them itself (solve_batch with fuse_small): construct() is everything solve() does
+    // before solve_dual(); adopt_dual() / adopt_rounding() take the results of a dual run / a rounding made elsewhere on handle() — by the
+    // batch calls of include/bdd_mma.h — as solve_dual() and perturbation_rounding() take their own.
+    void construct();
+    // constructed, a GPU parallel mma solver without an L-BFGS wrapper, and one workgroup runs its iterations (bddmma_fused_small)
+    bool fusable() const;
+    // what two configs must share to run in one batch, with the defaults solve_dual() and perturbation_rounding() use
+    struct fuse_settings {
+        bool f64 = true;
+        uint64_t max_iter = 1000;
+        double tolerance = 1e-6, slope = 1e-9, time_limit = 3600;
+        bool rounding = false;
+        double init_delta = 0.1, growth = 1.1;
+        uint64_t inner = 100, outer = 100;
+        uint32_t seed = 0;
+    };
+    fuse_settings settings() const;
+    std::string fuse_key() const;                                // empty: an L-BFGS (or unknown) solver name, never fused
+    void adopt_dual(const bddmma_run_result& res);
+    void adopt_rounding(const char* sol, bool found);            // sol: char[bddmma_nr_variables(handle())]
 
     double lower_bound();                                        // incl. the objective constant
     std::vector<std::vector<std::array<double, 2>>> min_marginals();  // [var][bdd] -> {mm0, mm1}
@@ -75,9 +95,23 @@ struct batch_result {
     double lower_bound = 0, primal = 0, seconds = 0;
     bool has_primal = false;
     uint64_t iterations = 0;
+    bool fused = false;   // solved as a member of a batch (solve_batch with fuse_small)
 };
 // configs are handed to the device threads dynamically (a thread takes the next one when its GPU is free); devices may repeat
 std::vector<batch_result> solve_batch(const std::vector<std::string>& configs, const std::vector<int>& devices, bool quiet);
+// fuse_small: a device thread constructs each config it takes; an instance that is bdd_solver::fusable() is parked under its fuse_key()
+// and solved with the others of that key in one batch (bddmma_batch_create, bddmma_batch_run_solver,
+// bddmma_incremental_mm_agreement_rounding_batch) when the key holds max_group members or the queue is empty; every other instance is
+// solved at once, as without the option.  The results are those of the unfused farm; a fused member's `seconds` is its construction
+// time plus its batch's wall time, "time limit" is one clock per batch, and a batch prints one line per member instead of the
+// per-iteration log.
+struct batch_options {
+    bool fuse_small = false;
+    uint32_t max_group = 256;
+};
+std::vector<batch_result> solve_batch(const std::vector<std::string>& configs, const std::vector<int>& devices, bool quiet, const batch_options& opt);
+// bdd_solver::fuse_key() of a config (JSON text or the path of a JSON file) without constructing anything: needs no device
+std::string fuse_key(const std::string& config);
 
 struct bench_result {
     int device = -1;

@@ -2,7 +2,9 @@
 //     bdd_solver_cl <config.json | '{"input": "problem.lp", "relaxation solver": "cuda parallel mma", ...}'>
 // prints the final lower bound and, when "perturbation rounding" is configured, the primal objective.
 // Batch farm over the GPUs of a node (independent instances, one host thread per device, no collective):
-//     bdd_solver_cl --batch cfg1.json cfg2.json ... [--devices 0-7 | 0,2,5] [--quiet]
+//     bdd_solver_cl --batch cfg1.json cfg2.json ... [--devices 0-7 | 0,2,5] [--quiet] [--fuse-small [--max-group N]]
+//         --fuse-small: instances that fit one workgroup and share their settings run as batches of up to N (256) in one launch per
+//         step (bdd_solver.hpp: batch_options); every JSON line then says whether its instance was "fused"
 //     bdd_solver_cl --bench-set-cover V B k --iterations N [--warmup W] [--seeds 12345-12352] [--devices 0-7] [--precision float]
 // Both print one JSON line per instance; the benchmark adds the aggregate iterations/s (all instances / slowest instance's time).
 #include <cstdio>
@@ -66,6 +68,7 @@ int main(int argc, char** argv)
             std::string precision = "float";
             uint64_t iterations = 1000, warmup = 100;
             bool quiet = false;
+            bddmma_host::batch_options opt;
             for (size_t i = 1; i < args.size(); ++i) {
                 auto need = [&](const char* what) -> const std::string& {
                     if (i + 1 >= args.size()) throw std::runtime_error(std::string(what) + " needs a value");
@@ -77,6 +80,8 @@ int main(int argc, char** argv)
                 else if (args[i] == "--iterations") iterations = std::stoull(need("--iterations"));
                 else if (args[i] == "--warmup") warmup = std::stoull(need("--warmup"));
                 else if (args[i] == "--quiet") quiet = true;
+                else if (args[i] == "--fuse-small") opt.fuse_small = true;
+                else if (args[i] == "--max-group") opt.max_group = (uint32_t)std::stoull(need("--max-group"));
                 else pos.push_back(args[i]);
             }
             if (devices.empty()) devices = all_devices();
@@ -84,11 +89,12 @@ int main(int argc, char** argv)
             if (args[0] == "--batch") {
                 if (pos.empty()) throw std::runtime_error("--batch needs at least one config");
                 int failed = 0;
-                for (const auto& r : bddmma_host::solve_batch(pos, devices, quiet)) {
+                for (const auto& r : bddmma_host::solve_batch(pos, devices, quiet, opt)) {
                     std::printf("{\"config\": \"%s\", \"device\": %d, \"ok\": %s, \"lower_bound\": %.12g, \"iterations\": %llu, \"seconds\": %.4f", json_escape(r.config).c_str(),
                                 r.device, r.ok ? "true" : "false", r.lower_bound, (unsigned long long)r.iterations, r.seconds);
                     if (r.has_primal) std::printf(", \"primal\": %.12g", r.primal);
                     if (!r.ok) std::printf(", \"error\": \"%s\"", json_escape(r.error).c_str());
+                    if (opt.fuse_small) std::printf(", \"fused\": %s", r.fused ? "true" : "false");
                     std::printf("}\n");
                     failed += r.ok ? 0 : 1;
                 }
@@ -111,7 +117,7 @@ int main(int argc, char** argv)
             return failed ? 1 : 0;
         }
         if (argc != 2) {
-            std::cerr << "usage: " << argv[0] << " <config file | config json>\n       " << argv[0] << " --batch cfg... [--devices 0-7] [--quiet]\n       " << argv[0]
+            std::cerr << "usage: " << argv[0] << " <config file | config json>\n       " << argv[0] << " --batch cfg... [--devices 0-7] [--quiet] [--fuse-small [--max-group N]]\n       " << argv[0]
                       << " --bench-set-cover V B k --iterations N [--warmup W] [--seeds a-b] [--devices 0-7] [--precision float|double]\n";
             return 2;
         }

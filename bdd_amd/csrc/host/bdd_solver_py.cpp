@@ -182,6 +182,33 @@ PYBIND11_MODULE(bdd_solver_py, m)
             return d;
         });
 
+    // the batch farm (bdd_solver.hpp: solve_batch): independent configs over the devices, one dict per config in the configs' order
+    m.def(
+        "solve_batch",
+        [](const std::vector<py::object>& configs, const std::vector<int>& devices, bool quiet, bool fuse_small, uint32_t max_group) {
+            std::vector<std::string> texts;
+            for (const py::object& c : configs) texts.push_back(config_text(c));
+            bddmma_host::batch_options opt;
+            opt.fuse_small = fuse_small;
+            opt.max_group = max_group;
+            std::vector<bddmma_host::batch_result> res;
+            {
+                py::gil_scoped_release release;
+                res = bddmma_host::solve_batch(texts, devices, quiet, opt);
+            }
+            py::list out;
+            for (const auto& r : res) {
+                py::dict d;
+                d["config"] = r.config; d["device"] = r.device; d["ok"] = r.ok; d["error"] = r.error; d["lower_bound"] = r.lower_bound;
+                d["primal"] = r.primal; d["seconds"] = r.seconds; d["has_primal"] = r.has_primal; d["iterations"] = r.iterations; d["fused"] = r.fused;
+                out.append(d);
+            }
+            return out;
+        },
+        py::arg("configs"), py::arg("devices") = std::vector<int>{0}, py::arg("quiet") = true, py::arg("fuse_small") = false, py::arg("max_group") = 256);
+    // what two configs must share to run in one batch of solve_batch(fuse_small=True); "" for a solver that is never fused
+    m.def("fuse_key", [](const py::object& config) { return bddmma_host::fuse_key(config_text(config)); }, py::arg("config"));
+
     py::class_<hip_solver>(m, "bdd_hip_parallel_mma")
         .def(py::init([](const std::string& ilp_text, const std::string& precision, int device) { return hip_solver::from_ilp(ilp_text, precision, device); }),
              py::arg("ilp"), py::arg("precision") = "double", py::arg("device") = 0)

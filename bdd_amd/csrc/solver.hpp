@@ -179,7 +179,11 @@ struct BatchBase {
     // mask (may be null): size() entries in member order; a member whose entry is non-zero takes no part and keeps its state
     virtual int run_plain(uint64_t max_iter, double tolerance, double slope, double time_limit, bddmma_run_result* res, const char* mask = nullptr) = 0;
     virtual int time_iterations(double omega, uint64_t n, double* ms) = 0;   // iterations() between hipEvents on the batch stream; waits
-    virtual int lower_bounds(double* out) = 0;              // SolverBase::lower_bound of every member, the reductions in flight together
+    // SolverBase::lower_bound of every member: the stale members' backward sweeps and every member's reduction in one launch per wave count
+    // present (kernels/batchlb.hpp), one host wait.  on_device: the doubles go to the caller's device array on the batch's stream, the host
+    // does not wait and no cached bound is set.  check_members: the refusals of every batch call first (include/bdd_mma.h:
+    // bddmma_lower_bound_batch; bddmma_batch_lower_bounds passes false)
+    virtual int lower_bounds(double* out, int on_device = 0, bool check_members = false) = 0;
     // SolverBase::learned_iterations(w_i, num_itr, omega, slope 0, no history) of every member, or its omega_vec form; dist_weights /
     // omega_vec: the members' REAL[nr_layers] one behind the other in the caller's order (include/bdd_mma.h: bddmma_learned_iterations_batch)
     virtual int learned_iterations(const void* dist_weights, const void* omega_vec, double omega, uint64_t num_itr, int on_device) = 0;

@@ -8,6 +8,7 @@
 #include "solver_impl.hpp"
 #include "kernels/gradsmall.hpp"
 #include "kernels/batchcosts.hpp"
+#include "kernels/batchlb.hpp"
 #include "kernels/batchbound.hpp"
 #include "kernels/batchmm.hpp"
 #include "kernels/batchsm.hpp"
@@ -49,12 +50,13 @@ struct BatchT final : BatchBase {
         for (hipEvent_t e : {ev_out, ev_chunk[0], ev_chunk[1], ev_t0, ev_t1, ev_order})
             if (e) (void)hipEventDestroy(e);
         if (d_items) (void)hipFree(d_items);
-        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_st_items, (void*)d_st_blocks, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_gs_cnt, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad, (void*)d_bm_items, (void*)d_bm_stage, (void*)d_bm_bad, (void*)d_bsm_items, (void*)d_bsm_stage, (void*)d_br_items, (void*)d_br_words, (void*)d_bp_items, (void*)d_bp_stage, (void*)d_bp_bad})
+        for (void* q : {(void*)d_hs_items, (void*)d_hs_stage, (void*)d_st_items, (void*)d_st_blocks, (void*)d_ln_items, (void*)d_ln_tab, (void*)d_ln_in, (void*)d_ln_bad, (void*)d_gs_items, (void*)d_gs_ws, (void*)d_gs_io, (void*)d_gs_bad, (void*)d_gs_cnt, (void*)d_bc_items, (void*)d_bc_stage, (void*)d_bl_words, (void*)d_bb_items, (void*)d_bb_stage, (void*)d_bb_bad, (void*)d_bm_items, (void*)d_bm_stage, (void*)d_bm_bad, (void*)d_bsm_items, (void*)d_bsm_stage, (void*)d_br_items, (void*)d_br_words, (void*)d_bp_items, (void*)d_bp_stage, (void*)d_bp_bad})
             if (q) (void)hipFree(q);
         if (d_ctl) (void)hipFree(d_ctl);
         if (h_ctl) (void)hipHostFree(h_ctl);
         if (h_run) (void)hipHostFree(h_run);
         if (h_br_words) (void)hipHostFree(h_br_words);
+        if (h_bl_out) (void)hipHostFree(h_bl_out);
         if (stream) (void)hipStreamDestroy(stream);
     }
     uint64_t size() const override { return m.size(); }
@@ -940,6 +942,7 @@ struct BatchT final : BatchBase {
         uint32_t threads, lds, first, count;
     };
     std::vector<BcGroup> bc_groups;
+    std::vector<uint32_t> bc_order;            // item j of d_bc_items is member bc_order[j]
     CostsItem<REAL>* d_bc_items = nullptr;
     REAL* d_bc_stage = nullptr;
     uint64_t bc_total = 0, bc_stage_cap = 0;   // values of all members' layers; values the staging buffer holds
@@ -980,6 +983,7 @@ struct BatchT final : BatchBase {
             if (!d_bc_items) HIPCHK(hipMalloc((void**)&d_bc_items, n * sizeof(CostsItem<REAL>)));
             HIPCHK(hipMemcpy(d_bc_items, items.data(), n * sizeof(CostsItem<REAL>), hipMemcpyHostToDevice));
             bc_groups = std::move(groups_);
+            bc_order = std::move(ord);
             bc_total = total;
             bc_ready = true;
         }
@@ -1896,32 +1900,130 @@ struct BatchT final : BatchBase {
         return BDDMMA_OK;
     }
 
-    int lower_bounds(double* out) override
+    // ---- the members' lower bounds, all at once (kernels/batchlb.hpp: k_small_bound_batch; the kernel compiles in solver_bl_f32.hip /
+    // _f64.hip).  The items and the groups are those of the solver costs (bc_prepare); a call's flags (LB_SKIP / LB_SWEEP / LB_REDUCE) are
+    // kernel arguments, a group of more than LB_LAUNCH_ITEMS members is launched in slices.  The results of a host call arrive in pinned
+    // memory the batch owns, each with a sequence word behind it that the host polls (SolverT::wait_bound's reasons).
+    struct BlGroup {
+        BoundSumFn<REAL> fn;
+        uint32_t threads, lds, first, count;
+    };
+    std::vector<BlGroup> bl_groups;
+    std::vector<uint32_t> bl_modes;                    // item order
+    uint32_t* d_bl_words = nullptr;                    // item j -> its member's index in the caller's order
+    double *h_bl_out = nullptr, *d_bl_out = nullptr;   // pinned + its device address: n doubles, then n sequence words
+    uint64_t bl_seq = 0;
+    bool bl_ready = false;
+    // run_plain only: lower_bounds has put the batch stream behind the members' streams and left the join_out to its caller
+    bool bl_joined = false;
+    static constexpr uint32_t BL_STATIC_LDS = SMALL_MAX_PACKS * (uint32_t)sizeof(double);   // the kernel's `part`
+
+    int bl_prepare()
     {
-        HIPCHK(hipSetDevice(device));
-        std::vector<char> pending(m.size(), 0);
-        for (size_t i = 0; i < m.size(); ++i) {
-            if (masked(i)) continue;
-            S* s = m[i];
-            int rc = s->backward_run();
-            if (!rc && !s->lb_cached) {
-                rc = s->launch_bound(0);
-                pending[i] = 1;
-            }
-            if (rc) { err = s->err; return rc; }
+        if (int rc = bc_prepare(false)) return rc;
+        if (bl_ready) return BDDMMA_OK;
+        const uint32_t n = (uint32_t)m.size();
+        std::vector<BlGroup> groups_;
+        for (const BcGroup& g : bc_groups) {
+            if (g.lds + BL_STATIC_LDS > m[0]->lds_cu) { err = "batch lower_bound: the costs-to-terminal do not fit the LDS"; return BDDMMA_ERR_UNSUPPORTED; }
+            groups_.push_back(BlGroup{bound_sum_fn<REAL>((int)(g.threads / 64u)), g.threads, g.lds, g.first, g.count});
+            if (int rc = raise_lds_limit(reinterpret_cast<const void*>(groups_.back().fn), g.lds)) return rc;
         }
-        // the reductions run side by side on the members' streams; the host then collects them in order
-        for (size_t i = 0; i < m.size(); ++i) {
-            if (masked(i)) continue;   // (its entry of `out` stays)
-            S* s = m[i];
-            if (pending[i]) {
-                if (int rc = s->wait_bound(0)) { err = s->err; return rc; }
-                s->lb_cache = ((volatile double*)s->h_lb)[0];
-                s->lb_cached = true;
-            }
-            out[i] = s->lb_cache;
+        if (!d_bl_words) HIPCHK(hipMalloc((void**)&d_bl_words, n * sizeof(uint32_t)));
+        HIPCHK(hipMemcpy(d_bl_words, bc_order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (!h_bl_out) {
+            HIPCHK(hipHostMalloc((void**)&h_bl_out, 2 * (size_t)n * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent));
+            HIPCHK(hipHostGetDevicePointer((void**)&d_bl_out, h_bl_out, 0));
+            std::memset((void*)h_bl_out, 0, 2 * (size_t)n * sizeof(double));
         }
+        bl_modes.assign(n, 0u);
+        bl_groups = std::move(groups_);
+        bl_ready = true;
         return BDDMMA_OK;
+    }
+    // SolverT::lower_bound of every member that run_plain's mask leaves in: a stale member (where backward_run() would launch) sweeps in its
+    // workgroup, every member reduces.  A host call takes a cached bound from the cache, as the per-member call does (the reduction's
+    // result equals it), and leaves every member with its bound cached.
+    // leave_joined (run_plain, which joins out itself): the members' streams are not made to wait here; bl_joined says that this happened.
+    int lower_bounds(double* out, int on_dev = 0, bool check_members = false) override { return lower_bounds_impl(out, on_dev, check_members, false); }
+    int lower_bounds_impl(double* out, int on_dev, bool check_members, bool leave_joined)
+    {
+        int rc;
+        if (check_members && (rc = check_state())) return rc;
+        HIPCHK(hipSetDevice(device));
+        if ((rc = bl_prepare())) return rc;
+        const uint32_t n = (uint32_t)m.size();
+        bool any = false;
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t i = bc_order[j];
+            bl_modes[j] = masked(i) ? LB_SKIP : !m[i]->bwd_valid ? LB_SWEEP : LB_REDUCE;
+            any = any || bl_modes[j] != LB_SKIP;
+        }
+        if (!any) return BDDMMA_OK;
+        if ((rc = members_in())) return rc;
+        // ---- the members are touched from here on
+        hipError_t e = hipSuccess;
+        double* const dst = on_dev ? out : d_bl_out;
+        uint64_t* const seq_dev = on_dev ? nullptr : reinterpret_cast<uint64_t*>(d_bl_out + n);
+        volatile uint64_t* const seq_host = reinterpret_cast<volatile uint64_t*>(h_bl_out + n);
+        const uint64_t seq = ++bl_seq;
+        for (size_t g = 0; g < bl_groups.size() && e == hipSuccess; ++g) {
+            const BlGroup& G = bl_groups[g];
+            for (uint32_t first = G.first; first < G.first + G.count && e == hipSuccess; first += LB_LAUNCH_ITEMS) {
+                const uint32_t count = std::min(LB_LAUNCH_ITEMS, G.first + G.count - first);
+                LbFlags flags{};
+                uint32_t live = 0;
+                for (uint32_t k = 0; k < count; ++k) {
+                    flags.w[k >> 4] |= bl_modes[first + k] << ((k & 15u) * LB_MODE_BITS);
+                    live += bl_modes[first + k] != LB_SKIP;
+                }
+                if (!live) continue;
+                hipLaunchKernelGGL(G.fn, dim3(count), dim3(G.threads), G.lds, stream, (const CostsItem<REAL>*)(d_bc_items + first), (const uint32_t*)(d_bl_words + first), flags, dst,
+                                   seq_dev, seq);
+                e = hipGetLastError();
+            }
+        }
+        if (e == hipSuccess && !on_dev) {   // the one wait: every member's word, then a blocking wait after 2 ms without them
+            const auto t0 = std::chrono::steady_clock::now();
+            uint32_t spins = 0;
+            for (uint32_t j = 0; j < n && e == hipSuccess; ++j) {
+                if (bl_modes[j] == LB_SKIP) continue;
+                volatile uint64_t* w = seq_host + bc_order[j];
+                while (*w != seq) {
+                    cpu_relax();
+                    if ((++spins & 1023u) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2e-3) {
+                        e = hipStreamSynchronize(stream);
+                        if (e == hipSuccess && *w != seq) e = hipErrorUnknown;
+                        break;
+                    }
+                }
+            }
+            std::atomic_thread_fence(std::memory_order_acquire);
+        }
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t i = bc_order[j], mode = bl_modes[j];
+            if (mode == LB_SKIP) continue;   // (its entry of `out` stays)
+            S* s = m[i];
+            if (mode == LB_SWEEP) {   // launch_sweep(bwd) and backward_run(); behind a failure nothing is known to be valid
+                s->lb_cached = false;
+                ++s->lb_gen;
+                s->bwd_valid = s->lb_valid = e == hipSuccess;
+            }
+            if (e == hipSuccess && !on_dev) {
+                if (!s->lb_cached) {
+                    s->lb_cache = ((volatile double*)h_bl_out)[i];
+                    s->lb_cached = true;
+                }
+                out[i] = s->lb_cache;
+            }
+        }
+        if (e == hipSuccess && leave_joined) {
+            bl_joined = true;
+            return BDDMMA_OK;
+        }
+        const int rc2 = join_out();
+        if (e != hipSuccess) { err = std::string("batch lower_bound: ") + hipGetErrorString(e); return BDDMMA_ERR_DEVICE; }
+        return rc2;
     }
 
     // SolverT::run_plain for every member at once.  Chunks of SMALL_CHUNK iterations, the tests in each member's workgroup after every
@@ -1933,7 +2035,14 @@ struct BatchT final : BatchBase {
     {
         struct MaskScope {
             BatchT* b;
-            ~MaskScope() { b->run_mask = nullptr; }
+            ~MaskScope()
+            {
+                b->run_mask = nullptr;
+                if (b->bl_joined) {   // a return between lower_bounds and the run's own join_out
+                    b->bl_joined = false;
+                    (void)b->join_out();
+                }
+            }
         } scope{this};
         run_mask = mask;
         if (slope < 0.0 || slope >= 1.0 || time_limit < 0.0 || tolerance < 0.0) {
@@ -1947,7 +2056,8 @@ struct BatchT final : BatchBase {
         auto elapsed = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
         const uint32_t n = (uint32_t)m.size();
         std::vector<double> lb_initial(n);
-        if ((rc = lower_bounds(lb_initial.data()))) return rc;
+        // (with iterations to run the bounds' launch leaves the members' streams to the run's join_out; the batch stream is behind them then)
+        if ((rc = lower_bounds_impl(lb_initial.data(), 0, false, max_iter > 0))) return rc;
         constexpr uint64_t MASK = (1ull << 56) - 1;
         if (max_iter > 0) {
             for (uint32_t j = 0; j < n; ++j) {
@@ -1962,7 +2072,8 @@ struct BatchT final : BatchBase {
                 h_ctl[j] = c;
             }
             std::memset((void*)h_run, 0, n * sizeof(RunHost));
-            if ((rc = join_in())) return rc;
+            // no member is stale behind lower_bounds, and nothing has been queued on a member's stream since its members_in()
+            if (!bl_joined && (rc = join_in())) return rc;
             HIPCHK(hipMemcpyAsync(d_ctl, h_ctl, n * sizeof(RunCtl), hipMemcpyHostToDevice, stream));
             hipLaunchKernelGGL(k_run_begin_batch, dim3(cdiv(n, 256)), dim3(256), 0, stream, d_ctl, n, (uint64_t)(elapsed() * RUN_TICKS_PER_SECOND));
             HIPCHK(hipGetLastError());
@@ -1996,6 +2107,7 @@ struct BatchT final : BatchBase {
             for (size_t i = 0; i < m.size(); ++i)
                 if (!masked(i)) m[i]->run_stop = nullptr;
             if (!rc && e != hipSuccess) { err = std::string("run_solver: ") + hipGetErrorString(e); rc = BDDMMA_ERR_DEVICE; }
+            bl_joined = false;
             const int rc2 = join_out();
             if (rc || rc2) return rc ? rc : rc2;
             for (uint32_t j = 0; j < n; ++j) {

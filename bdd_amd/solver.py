@@ -1047,8 +1047,17 @@ class bdd_hip_batch:
         return [dict(iterations=int(r.iterations), lb_initial=r.lb_initial, lb_final=r.lb_final, seconds=r.seconds,
                      stop_reason=int(r.stop_reason)) for r in res]
 
-    def lower_bounds(self):
-        out = np.empty(len(self.solvers), dtype=np.float64)
+    def lower_bounds(self, out=None):
+        """lower_bound() of every member in one launch per wave count present: float64[len(solvers)] in the members' order.  out: a
+        device tensor of float64 — the bounds are written to it on the batch's stream, the host does not wait, and it is returned.
+        include/bdd_mma.h: bddmma_lower_bound_batch."""
+        n = len(self.solvers)
+        if out is not None:
+            if not _is_dev(out):
+                raise capi.BddMmaError(f"bdd_mma error {capi.ERR_INVALID_ARGUMENT}: lower_bounds(out=...) takes a device tensor")
+            self._check(self._L.bddmma_lower_bound_batch(self._h, C.cast(_dev_ptr(out, n, np.float64), C.POINTER(C.c_double)), 1), self._h)
+            return out
+        out = np.empty(n, dtype=np.float64)
         self._check(self._L.bddmma_batch_lower_bounds(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
         return out
 

@@ -689,8 +689,21 @@ int bddmma_batch_run_solver(bddmma_batch* b, uint64_t max_iter, double tolerance
 /* bddmma_batch_iterations bracketed by hipEvents on the batch's stream, from its first launch to its last; *ms = elapsed device time.
  * Waits for the launches (the measurement counterpart of bddmma_time_iterations). */
 int bddmma_batch_time_iterations(bddmma_batch* b, double omega, uint64_t n, double* ms);
-/* out[i] = bddmma_lower_bound(member i); the members' reductions are in flight together and the host collects them once */
+/* bddmma_lower_bound_batch(b, out, 0) without the BDDMMA_ERR_STATE refusals of the members' states (the name of the first batch calls, kept) */
 int bddmma_batch_lower_bounds(bddmma_batch* b, double* out);
+/* bddmma_lower_bound(member i, &out[i]) for every member i, in one launch per wave count present (kernels/batchlb.hpp: one workgroup per
+ * member, a wave per pack): a member whose costs-to-terminal are stale runs the plain backward sweep bddmma_lower_bound would run first
+ * inside its workgroup, and wave 0 sums the member's partial sums in that call's order, so out[i] is bit-equal to it in float and in
+ * double.  out: double[bddmma_batch_size] in the members' order at bddmma_batch_create.
+ * on_device 0: out is a host array; the results arrive in a pinned buffer the batch owns and the host waits once.  Every member's cached
+ * bound is set, as bddmma_lower_bound sets it.
+ * on_device 1: out is a device array written on the batch's stream; the host does not wait and no member's cached bound is set.  The
+ * ordering is that of the batch entry points above: the launch runs behind everything queued on every member's stream, and every
+ * member's stream waits for it.
+ * State of every member afterwards: its costs-to-terminal are valid (a later call runs no sweep for them).
+ * Refusals, decided before any member or output is touched: b == NULL or out == NULL is BDDMMA_ERR_INVALID_ARGUMENT; BDDMMA_ERR_STATE as for
+ * every batch call (an L-BFGS wrapper, profiling, a member inside run_solver; bddmma_batch_last_error names the member). */
+int bddmma_lower_bound_batch(bddmma_batch* b, double* out, int on_device);
 
 /* ---- primal rounding (src/bdd_solver/incremental_mm_agreement_rounding_cuda.cu:333-372) ------------------
  * incremental_mm_agreement_rounding_cuda(s, init_delta, delta_growth_rate, num_itr_lb, verbose, num_rounds):
