@@ -72,6 +72,7 @@ SIGNATURES = {
     "bddmma_nontemporal_loads": (_I, [_V]),
     "bddmma_potentials_on_chip": (_I, [_V]),
     "bddmma_onchip_hops": (_I, [_V]),
+    "bddmma_lane_sweeps": (_I, [_V]),
     "bddmma_precision": (_I, [_V]),
     "bddmma_device": (_I, [_V]),
     "bddmma_num_bdds_per_var": (_I, [_V, _V]),
@@ -172,6 +173,7 @@ SIGNATURES = {
     "bddmma_layout_res2_records": (_I, [_V, _I, _V, _V, _V]),
     "bddmma_layout_stream_records": (_I, [_V, _I, _V, _V, _V]),
     "bddmma_layout_layer_records": (_I, [_V, _I, _V, _V, _V]),
+    "bddmma_layout_lane_codes": (_I, [_V, _I, _V, _V, _V]),
     "bddmma_layout_seg_exchange": (_I, [_V, _I, _I, _V, _V, _V, _V]),
 }
 

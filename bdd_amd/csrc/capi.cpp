@@ -161,6 +161,7 @@ int bddmma_fused_small_stop(const bddmma_solver* s) { return s && s->impl ? (s->
 int bddmma_nontemporal_loads(const bddmma_solver* s) { return s && s->impl ? (s->impl->nt_loads ? 1 : 0) : -1; }
 int bddmma_potentials_on_chip(const bddmma_solver* s) { return s && s->impl ? (s->impl->pot_on_chip ? 1 : 0) : -1; }
 int bddmma_onchip_hops(const bddmma_solver* s) { return s && s->impl ? s->impl->onchip_hops : -1; }
+int bddmma_lane_sweeps(const bddmma_solver* s) { return s && s->impl ? (s->impl->lane_sweeps ? 1 : 0) : -1; }
 int bddmma_precision(const bddmma_solver* s) { return s && s->impl ? s->impl->precision : -1; }
 int bddmma_device(const bddmma_solver* s) { return s && s->impl ? s->impl->device : -1; }
 uint64_t bddmma_device_bytes(const bddmma_solver* s) { return s && s->impl ? s->impl->dev_bytes : 0; }
@@ -1005,6 +1006,19 @@ int bddmma_layout_layer_records(const bddmma_layout* l, int real_size, uint32_t*
     info[0] = R.ok ? 1u : 0u; info[1] = (uint32_t)R.rec.size();
     if (words && !R.rec.empty()) std::memcpy(words, R.rec.data(), R.rec.size() * sizeof(uint32_t));
     if (rec_off && !R.rec_off.empty()) std::memcpy(rec_off, R.rec_off.data(), R.rec_off.size() * sizeof(uint32_t));
+    return BDDMMA_OK;
+}
+
+int bddmma_layout_lane_codes(const bddmma_layout* l, int real_size, uint32_t* info, uint32_t* words, uint32_t* code_off)
+{
+    if (!l || !info || (real_size != 4 && real_size != 8)) return BDDMMA_ERR_INVALID_ARGUMENT;
+    LayerRecords R;
+    build_layer_records(l->L, (uint32_t)real_size, R);
+    LaneCodes K;
+    build_lane_codes(l->L, (uint32_t)real_size, R, K);
+    info[0] = K.ok ? 1u : 0u; info[1] = (uint32_t)K.words.size(); info[2] = K.affine ? 1u : 0u;
+    if (words && !K.words.empty()) std::memcpy(words, K.words.data(), K.words.size() * sizeof(uint32_t));
+    if (code_off && !K.code_off.empty()) std::memcpy(code_off, K.code_off.data(), K.code_off.size() * sizeof(uint32_t));
     return BDDMMA_OK;
 }
 

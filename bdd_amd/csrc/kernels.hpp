@@ -33,6 +33,7 @@
 #include "kernels/narrow2.hpp"
 #include "kernels/narrow3.hpp"
 #include "kernels/narrow4.hpp"
+#include "kernels/narrow5.hpp"
 #include "kernels/wide.hpp"
 #include "kernels/exchange.hpp"
 #include "kernels/small.hpp"

@@ -1788,6 +1788,68 @@ void build_layer_records(const HostLayout& L, uint32_t S, LayerRecords& out)
     out.ok = true;
 }
 
+void build_lane_codes(const HostLayout& L, uint32_t S, const LayerRecords& R, LaneCodes& out)
+{
+    out = LaneCodes();
+    const PackSet& N = L.narrow;
+    const uint32_t P = N.n_packs(), W = L.pack_width;
+    if (!R.ok || R.rec_off.size() != P) return;
+    std::unordered_map<uint32_t, uint32_t> seen;  // first record of a template -> its first lane record
+    std::vector<uint32_t> words, code_off(P, 0);
+    bool fits = true;
+    for (uint32_t p = 0; p < P; ++p) {
+        const uint32_t q0 = N.pack_hop_ptr[p], nh = N.pack_hop_ptr[p + 1] - q0;
+        const auto it = seen.find(R.rec_off[p]);
+        if (it != seen.end()) { code_off[p] = it->second; continue; }
+        const uint32_t first = (uint32_t)(words.size() / 4);
+        seen.emplace(R.rec_off[p], first);
+        code_off[p] = first;
+        words.resize(words.size() + 64 * 4, 0u);
+        if (nh > LCODE_HOPS) fits = false;
+        // hop 0 holds its layers' slots alone (the records do not say how many slots a hop has)
+        if (nh && N.hop_node_off[q0 + 1] - N.hop_node_off[q0] != N.hop_layer_off[q0 + 1] - N.hop_layer_off[q0]) return;
+        const uint32_t* rec = &R.rec[(size_t)R.rec_off[p] * 4];
+        for (uint32_t h = 0; h < nh; ++h) {
+            const uint32_t* r = rec + (size_t)h * 64 * 4;
+            const uint32_t* rn = h + 1 < nh ? r + 64 * 4 : nullptr;
+            for (uint32_t l = 0; l < 64; ++l) {
+                const uint32_t top = (W + 2 * l) * S, bot = top + S;
+                const uint32_t flags = r[4 * l + 2] >> 16;
+                const bool real = flags & LREC_REAL, two = flags & LREC_TWO;
+                if (two && !real) return;
+                if (h == 0 && real && (two || (r[4 * l + 2] & 0xFFFFu) != l * S)) return;
+                const uint32_t nflags = rn ? rn[4 * l + 2] >> 16 : 0u;
+                const uint32_t na = (nflags & LREC_REAL) ? rn[4 * l + 2] & 0xFFFFu : 0xFFFFFFFFu;  // node a of the lane's layer one hop down
+                const uint32_t nb = (nflags & LREC_REAL) && (nflags & LREC_TWO) ? na + S : 0xFFFFFFFFu;
+                uint32_t code = flags << 8;
+                for (uint32_t k = 0; k < 4; ++k) {
+                    const uint32_t off = (r[4 * l + k / 2] >> (16 * (k & 1))) & 0xFFFFu;
+                    const bool present = real && (k < 2 || two);
+                    uint32_t c;
+                    if (!present) {
+                        if (off != bot) return;
+                        c = LCODE_BOT;
+                    } else if (off == top) c = LCODE_TOP;
+                    else if (off == bot) c = LCODE_BOT;
+                    else if (off == na) c = LCODE_A;
+                    else if (off == nb) c = LCODE_B;
+                    else return;  // the arc ends in another lane's layer
+                    code |= c << (2 * k);
+                }
+                if (h < LCODE_HOPS) words[(size_t)(first + l) * 4 + h / 3] |= code << (10 * (h % 3));
+            }
+        }
+        // hops the template does not have: lanes without a layer
+        for (uint32_t h = nh; h < LCODE_HOPS; ++h)
+            for (uint32_t l = 0; l < 64; ++l) words[(size_t)(first + l) * 4 + h / 3] |= 0xFFu << (10 * (h % 3));
+    }
+    out.affine = true;
+    if (!fits || (uint64_t)words.size() * 4 >= (1ull << 31)) return;
+    out.words.swap(words);
+    out.code_off.swap(code_off);
+    out.ok = true;
+}
+
 void set_layout_threads(unsigned n) { g_layout_threads.store(n, std::memory_order_relaxed); }
 void set_thread_layout_threads(unsigned n) { t_layout_threads = n; }
 

@@ -329,6 +329,30 @@ struct LayerRecords {
 };
 void build_layer_records(const HostLayout& L, uint32_t real_size, LayerRecords& out);
 
+// ---- lane codes of the lane-per-BDD solve sweeps (kernels/narrow5.hpp) -------------------------------------------------------------------
+// PackBuilder::add appends every BDD's layer to every hop in BDD order and build_layer_records gives lane l the l-th layer of a hop, so in a
+// pack whose BDDs are ordered longest first lane l owns the layer of ONE BDD in every hop: each arc of that layer ends at node a or node b
+// of the lane's own layer one hop down or at the lane's own TOP / BOT entry, and a BDD's potentials never leave its lane.  A structure
+// template is LANE-AFFINE when, for every hop h and lane l,
+//   - a lane with a layer (LREC_REAL) has every arc of node a — and of node b where LREC_TWO — at (W + 2 l) S (TOP), (W + 2 l + 1) S (BOT)
+//     or, where hop h + 1 exists and lane l has a layer there, at that layer's node-a offset (A) or, if that layer has two nodes, at
+//     node-a offset + S (B); the arcs of an absent node b lie at BOT;
+//   - in hop 0 a lane with a layer has a one-node layer at slot l, and the hop has no other slots (the backward sweep's bound is the sum
+//     of the hop's slots in slot order);
+//   - a lane without a layer has all four arcs at BOT.
+// Where every template of the instance is lane-affine and has at most LCODE_HOPS hops, a lane's records shrink to 10 bits per hop — two bits
+// per arc (a.lo, a.hi, b.lo, b.hi, from bit 0 up) over LCODE_A .. LCODE_BOT, then the record's two flag bits (LREC_TWO, LREC_REAL) — three
+// hops per word from bit 0 up, four words per lane: one 16-byte load before the walks.  64 lanes per template, shared by its packs.
+constexpr uint32_t LCODE_A = 0u, LCODE_B = 1u, LCODE_TOP = 2u, LCODE_BOT = 3u;
+constexpr uint32_t LCODE_HOPS = 12;
+struct LaneCodes {
+    bool ok = false;                 // every template lane-affine and within LCODE_HOPS hops: words / code_off are filled
+    bool affine = false;             // every template lane-affine, whatever its length
+    std::vector<uint32_t> words;     // 4 words per lane, 64 lanes per template
+    std::vector<uint32_t> code_off;  // [narrow packs] first lane record (16 bytes) of the pack's template
+};
+void build_lane_codes(const HostLayout& L, uint32_t real_size, const LayerRecords& R, LaneCodes& out);
+
 // A per-layer vector given as a linear combination of stored ones (the L-BFGS direction, lbfgs.hip: q = g + sum_k cy[order[k]] Y[order[k]]
 // + sum_k cs[order[k]] S[order[k]], accumulated in double in that order and rounded to REAL once): what the wrapper hands to
 // SolverBase::projection_means_lincomb so that the direction is formed inside the first pass of its projection instead of being written

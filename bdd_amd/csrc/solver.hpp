@@ -85,6 +85,7 @@ struct SolverBase {
     bool fused_small_stop = false;      // ... and the stopping rule on the bound's slope, in a batch (bddmma_fused_small_stop)
     bool nt_loads = false;      // the solve sweeps' non-temporal instantiation (diagnostics: bddmma_nontemporal_loads)
     bool pot_on_chip = false;   // iteration()'s solve sweeps rebuild F and T on chip (diagnostics: bddmma_potentials_on_chip)
+    bool lane_sweeps = false;   // ... and they are the lane-per-BDD pair, kernels/narrow5.hpp (diagnostics: bddmma_lane_sweeps)
     int onchip_hops = 0;        // ... the hop capacity of the kernels that do: 0, 10, 12 or 16 (diagnostics: bddmma_onchip_hops)
     // run_solver (include/run_solver_util.h:10-77) around iteration(): termination tests on the device, see solver_impl.hpp
     virtual int run_plain(uint64_t max_iter, double tolerance, double slope, double time_limit, int verbose, bddmma_run_result* res) = 0;

@@ -211,6 +211,10 @@ struct SolverT final : SolverBase {
     uint32_t onchip_mode = 0;
     uint32_t *d_lrec = nullptr, *d_lrec_off = nullptr;
     uint32_t lrec_words = 0;
+    // ... and in registers alone, a lane per BDD (kernels/narrow5.hpp): the lane codes of layout.hpp: LaneCodes in place of the records
+    bool lane5 = false;
+    uint32_t *d_lcode = nullptr, *d_lcode_off = nullptr;
+    uint32_t lcode_words = 0;
     uint32_t huge_pack_width = 0;
     unsigned char* d_huge_scratch = nullptr;  // frontier arrays of the huge packs (global memory instead of LDS)
 
@@ -539,6 +543,7 @@ struct SolverT final : SolverBase {
         // layers are wider than two nodes or packs are staggered.  variant_flags bit 12: first generation; bit 13: records also where they are not
         // shared (the differential tests run the general form on random instances that way)
         uint32_t narrow2_static = 0;
+        LaneCodes lane_codes;  // of the third generation's records, where those are built (float)
         if (nb_.n_packs && !use_res && !wb_.n_packs && !(opts && (opts->variant_flags & 0x1000u))) {
             StreamRecords SR;
             build_stream_records(L, sizeof(REAL), SR);
@@ -568,6 +573,7 @@ struct SolverT final : SolverBase {
             !(opts && (opts->variant_flags & 0x41000u))) {
             LayerRecords LR;
             build_layer_records(L, sizeof(REAL), LR);
+            if constexpr (sizeof(REAL) == 4) build_lane_codes(L, sizeof(REAL), LR, lane_codes);
             const uint32_t n3_static = L.ex.waves_per_block * (4 * (128 + 128) * (uint32_t)sizeof(REAL) + 3 * 64 * 4);
             const bool forced = opts && (opts->variant_flags & 0x2000u);
             // ... and while the instance is small enough for the Infinity Cache to matter (same-box A/B against what the rules chose before,
@@ -616,6 +622,14 @@ struct SolverT final : SolverBase {
                 }
                 pot_on_chip = onchip_hc != 0;
                 onchip_hops = onchip_hc;
+                // ... walked in registers, a lane per BDD (kernels/narrow5.hpp), where both potentials are on chip and every structure
+                // template is lane-affine (layout.hpp: LaneCodes; packs of BDDs ordered longest first).  variant_flags bit 24: the LDS walks.
+                if ((onchip_hc == 10 || onchip_hc == 12) && onchip_mode == 0 && lane_codes.ok && !(opts && (opts->variant_flags & 0x1000000u))) {
+                    if ((rc = upload(&d_lcode, lane_codes.words))) return rc;
+                    if ((rc = upload(&d_lcode_off, lane_codes.code_off))) return rc;
+                    lcode_words = (uint32_t)lane_codes.words.size();
+                    lane5 = lane_sweeps = true;
+                }
             }
         }
         if (wb_.n_packs) {
@@ -875,6 +889,11 @@ struct SolverT final : SolverBase {
     // headline's 4 packs and 10 hops
     RecFn onchip_fn(bool bwd, bool rebuild, bool store) const
     {
+        if (lane5)  // k_fwd_narrow5 / k_bwd_narrow5: capacity 10 or 12, both potentials on chip (the rule of init())
+            return pick<4, 8>(wpb, [&](auto W) -> RecFn {
+                if (onchip_hc == 12) return bwd ? &k_bwd_narrow5<REAL, W.value, 12> : &k_fwd_narrow5<REAL, W.value, 12>;
+                return bwd ? &k_bwd_narrow5<REAL, W.value, 10> : &k_fwd_narrow5<REAL, W.value, 10>;
+            });
         if (onchip_hc == 16) return pick<4, 8>(wpb, [&](auto W) -> RecFn { return &k_bwd_narrow4<REAL, W.value, 16, true, true>; });
         if (onchip_hc == 12)
             return pick<4, 8>(wpb, [&](auto W) -> RecFn {
@@ -905,6 +924,7 @@ struct SolverT final : SolverBase {
                 const bool rebuild = onchip_mode == 0 || (onchip_mode == 1) == !bwd;  // forward rebuilds T, backward F
                 const bool store = onchip_mode != 0 && rebuild;  // the pairs that keep one potential on chip store the other one's partner: <1, 1> with <0, 0>
                 if constexpr (sizeof(REAL) == 4) s.rec = onchip_fn(bwd, rebuild, onchip_mode == 3 || store);
+                if (lane5) { s.rec_tab = d_lcode; s.rec_off = d_lcode_off; s.rec_words = lcode_words; }
                 s.reads_pot = !rebuild;
                 s.stores_pot = onchip_mode == 3 || store;
                 kern.onchip[bwd] = s;

@@ -115,6 +115,9 @@ class bdd_hip_parallel_mma:
     def onchip_hops(self) -> int:
         """hop capacity of the kernels behind potentials_on_chip(): 0 (off), 10 or 12 (F and T on chip), 16 (F on chip, T through memory)"""
         return int(self._L.bddmma_onchip_hops(self._h))
+    def lane_sweeps(self) -> bool:
+        """those sweeps keep a BDD's potentials in one lane and walk the hops in registers (csrc/kernels/narrow5.hpp; variant_flags bit 24: off)"""
+        return bool(self._L.bddmma_lane_sweeps(self._h))
     def device(self) -> int:
         """index of the GPU the solver lives on"""
         return int(self._L.bddmma_device(self._h))

@@ -112,7 +112,11 @@ typedef struct bddmma_options {
                                           start from the resident headers and have <= 16 hops rebuild both potentials on chip inside
                                           bddmma_iteration / _iterations / _run_solver, k_fwd_narrow4 / k_bwd_narrow4; a test hook: same results)
                                   bits 22, 23: of those sweeps only the one that rebuilds T (22) / F (23) on chip, the other potential through
-                                          memory (measurement hooks; built for 4 packs per workgroup and <= 10 hops, elsewhere as bit 21) */
+                                          memory (measurement hooks; built for 4 packs per workgroup and <= 10 hops, elsewhere as bit 21)
+                                  bit 24: no lane-per-BDD sweeps: those sweeps walk their hops through LDS, k_fwd_narrow4 / k_bwd_narrow4
+                                          (rule: where both potentials are on chip, capacity 10 or 12, and every structure template is
+                                          lane-affine, csrc/layout.hpp: LaneCodes, the walks stay in registers, k_fwd_narrow5 /
+                                          k_bwd_narrow5; a test hook: same results, bit for bit; bddmma_lane_sweeps reports the choice) */
     uint32_t pack_fill;        /* slots of a narrow pack's hop that further BDDs are packed into, in [2, pack_width] (default 0 = pack_width).
                                   Smaller values give more, emptier packs (more wavefronts for the same nodes); measured slower on every
                                   instance (NOTES.md section 6: the sweeps are bound by instructions issued, not by latency), kept for experiments */
@@ -200,6 +204,10 @@ int bddmma_potentials_on_chip(const bddmma_solver* s);
  * 12 (both potentials on chip: k_fwd_narrow4 with k_bwd_narrow4), 16 (the costs-from-root on chip, the costs-to-terminal through memory:
  * k_fwd_narrow3 with k_bwd_narrow4). */
 int bddmma_onchip_hops(const bddmma_solver* s);
+/* 1 when those sweeps keep a BDD's potentials in one lane's registers and walk the hops without LDS (csrc/kernels/narrow5.hpp: both
+ * potentials on chip, capacity 10 or 12, every structure template lane-affine; variant_flags bit 24 turns it off), else 0; -1 without a
+ * solver.  bddmma_onchip_hops, bddmma_potentials_on_chip and bddmma_solve_sweep_kind do not change with it. */
+int bddmma_lane_sweeps(const bddmma_solver* s);
 int bddmma_precision(const bddmma_solver* s);
 int bddmma_device(const bddmma_solver* s);
 /* nr_bdds(var): int32[nr_variables] (get_num_bdds_per_var, bdd_cuda_base.h:166) */
@@ -849,6 +857,10 @@ int bddmma_layout_stream_records(const bddmma_layout* l, int real_size, uint32_t
 /* ... and the per-layer records of the third-generation streaming sweeps (csrc/layout.hpp: LayerRecords; 64 records of 4 words per hop):
  * info[0] = usable (packs of 128 slots, layers of <= 2 nodes, <= 64 layers per hop, no staggered packs), [1] = number of 32-bit words. */
 int bddmma_layout_layer_records(const bddmma_layout* l, int real_size, uint32_t* info, uint32_t* words, uint32_t* rec_off);
+/* ... and the lane codes of the lane-per-BDD solve sweeps, derived from those records (csrc/layout.hpp: LaneCodes; 64 lanes of 4 words per
+ * structure template): info[0] = usable (every template lane-affine, <= 12 hops), [1] = number of 32-bit words, [2] = every template
+ * lane-affine whatever its length.  code_off (one per narrow pack): the first lane record of the pack's template. */
+int bddmma_layout_lane_codes(const bddmma_layout* l, int real_size, uint32_t* info, uint32_t* words, uint32_t* code_off);
 /* The schedule of the atomic-free exchange (csrc/layout.hpp: SegExchange) for workgroups of `threads` and values of real_size bytes:
  * info[0] = usable, [1] = 32-bit words of `bin` (4 per bin), [2] = 16-bit words of `perm`, [3] = 32-bit words of `thr` (2 per bin and
  * thread), [4] / [5] / [6] = entries / slots / groups of the largest bin.  The arrays may be NULL to query sizes. */
